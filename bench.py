@@ -1,16 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- Mcells/s of the Priority-Flood-equivalent fill on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--no-stages] [--no-host]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--dump-outputs DIR]
+                    [--full [--no-stages] [--no-host] [--cpu-sample S] [--cpu-full 0|1] ...]
 
 A step = one fill (rdgpu_fill_dev_f32 through the C-ABI) of one synthetic float32 DEM, G(seed) of
 SURVEY.md section 8d, already resident in HBM when the timed region starts.  At N=1 the workload is
 BASELINE configs[2] "40000x40000 float32 DEM, Priority-Flood (+ flat resolution) on 1 MI355X".  One JSON
-line on rank 0.  Besides `value` (the fill) the line carries
+line on rank 0.
+
+A plain run sets up, warms up, times the K fills, writes the last fill's output if --dump-outputs is given
+(the filled DEM as DIR/filled_dem.npy, float32; above DUMP_SAMPLE cells a fixed, seeded sample of it, with
+the sampled cells' row-major indices in DIR/filled_dem_cells.npy, float64) and prints the line: `value`,
+`ms_per_step` and the fill's configuration.  With --full the line also carries
 
   roofline       whole fill first (8 algorithmic bytes per cell ONCE for all of its kernels), then the
                  dominant raster kernel of the fill with its own launch time (HIP events on the launch stream,
                  taken in a separate instrumented pass -- the timed steps run without event recording)
+  kernels_ms_per_step  the fill's kernels from that instrumented pass
   stages         the rest of the path on the filled DEM (BASELINE configs[2] and [4]): D8 directions,
                  directions + flat resolution, d8_flow_accum, ResolveFlatsEpsilon, FA_D8 on the epsilon-resolved
                  DEM -- each with ms, Mcells/s, SURVEY 8d algorithmic bytes and the fraction of 8 TB/s
@@ -30,6 +37,12 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0
+#: pristine copies of the DEM held for the timed fills (the fill works in place): the steps run in rounds of at most
+#: this many back-to-back fills, the copies restored between rounds outside the clock (8 x 6.4 GB at the metric's size)
+STEP_POOL = 8
+#: --dump-outputs: cells of the filled DEM written when it has more (a sample drawn with DUMP_SEED, the same every run)
+DUMP_SAMPLE = 1 << 22
+DUMP_SEED = 20240607
 #: SURVEY.md section 8d, algorithmic bytes per cell
 STAGE_BYTES = {"d8_flow_directions": 5, "directions_plus_flat_resolution": 6, "d8_flow_accum": 9,
                "resolve_flats_epsilon": 8, "fa_d8": 20, "priority_flood_epsilon": 8, "priority_flood_flowdirs": 5,
@@ -316,7 +329,10 @@ def _differing(torch, out, which: str):
     path = os.path.join(ROOT, "tests", "golden", f"ref_s3_f2_{which}.npz")
     if not os.path.exists(path):
         return None
-    g = np.load(path)
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    from digest import load_golden   # (the sample is stored in pieces beside the file)
+
+    g = load_golden(path)
     if int(g["size"]) != out.shape[0] or out.shape[0] != out.shape[1]:
         return None
     k, stride = int(g["sample_k"]), int(g["sample_stride"])
@@ -364,6 +380,23 @@ def host_path(rd, torch, Z, reps: int = 2) -> dict:
     return out
 
 
+def dump_outputs(torch, W, directory: str) -> None:
+    """--dump-outputs: the last timed fill's output, what a caller of rdgpu_fill_dev_f32 receives.  Up to DUMP_SAMPLE
+    cells the whole filled DEM; above, its values at DUMP_SAMPLE cells drawn with DUMP_SEED (sorted, unique), and the
+    cells' row-major indices, so that two builds can be compared cell for cell."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    cells = W.numel()
+    if cells <= DUMP_SAMPLE:
+        np.save(os.path.join(directory, "filled_dem.npy"), W.cpu().numpy().astype(np.float32))
+        return
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, cells, DUMP_SAMPLE, dtype=np.int64))
+    vals = W.reshape(-1)[torch.from_numpy(idx).to(W.device)].cpu().numpy()
+    np.save(os.path.join(directory, "filled_dem.npy"), vals.astype(np.float32))
+    np.save(os.path.join(directory, "filled_dem_cells.npy"), idx.astype(np.float64))
+
+
 def main():
     if len(sys.argv) == 5 and sys.argv[1] == "--cpu-full-child":
         return cpu_full_child(sys.argv[2], int(sys.argv[3]), sys.argv[4])
@@ -374,10 +407,17 @@ def main():
     ap.add_argument("--size", type=int, default=40000, help="DEM is size x size cells")
     ap.add_argument("--cpu-sample", type=int, default=14000, help="window edge for the CPU baseline (0 = skip)")
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's filled DEM (or a fixed sample of it) to DIR as .npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel times and roofline, the stages "
+                         "after the fill, the host-pointer path and the CPU baseline (--cpu-sample and the options below apply to it)")
     ap.add_argument("--cpu-full", type=int, default=-1,
                     help="1: also run the compiled reference on the WHOLE DEM in a child process beside the GPU stages and report it "
                          "as cpu_baseline.value (minutes of one host core); 0: window only; default: on at the metric's size 40000")
-    ap.add_argument("--cpu-full-timeout", type=float, default=900.0, help="seconds the child gets before it is given up")
+    ap.add_argument("--cpu-full-timeout", type=float, default=420.0,
+                    help="seconds the child gets before it is given up (it takes 130 - 160 s; the whole --full run stays under "
+                         "10 minutes)")
     ap.add_argument("--no-stages", action="store_true", help="skip the directions / flat resolution / accumulation stages")
     ap.add_argument("--no-host", action="store_true", help="skip the host-pointer end-to-end measurement")
     ap.add_argument("--no-draining-mfd", action="store_true",
@@ -385,6 +425,8 @@ def main():
     ap.add_argument("--no-pf-flowdirs", action="store_true",
                     help="skip the PriorityFloodFlowdirs stage (324 more fills: the profiling passes' per-launch averages are the headline fill's)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # stdout must carry exactly ONE line, the JSON of rank 0.  Libraries print there too (RCCL: "Librccl path : ...",
     # flushed from the C stdio buffer at exit, on every rank), so file descriptor 1 is pointed at stderr for the
@@ -399,7 +441,6 @@ def main():
     import torch
 
     import richdem_amd as rd
-    from richdem_amd.roofline import fill_roofline
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -409,6 +450,11 @@ def main():
     torch.cuda.set_device(local_rank)
     if world > 1 or os.environ.get("RDGPU_BENCH_FORCE_SHARDED") == "1":   # the env switch runs the N>1 code path on 1 rank
         import torch.distributed as dist
+
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the single-GPU path's output; the row-block sharded path has none to write")
+        if not args.full:                     # the stages after the fill and the CPU baseline are --full's
+            args.no_stages, args.cpu_sample = True, 0
 
         # RCCL logs to stdout by default; route them to a file so stdout carries exactly one JSON line
         os.environ.setdefault("NCCL_DEBUG_FILE", "/tmp/rdgpu_rccl_%h_%p.log")
@@ -430,7 +476,7 @@ def main():
     cells = n * n
     Z = torch.empty((n, n), dtype=torch.float32, device="cuda")
     rd.synth_dem_dev(Z, seed=args.seed)
-    bufs = [Z.clone() for _ in range(args.steps)]   # fill is in place: one pristine copy per timed step
+    bufs = [Z.clone() for _ in range(min(args.steps, STEP_POOL))]   # fill is in place: one pristine copy per step of a round
     scratch = Z.clone()
     torch.cuda.synchronize()
 
@@ -439,38 +485,30 @@ def main():
         rd.fill_depressions_dev(scratch)
     torch.cuda.synchronize()
 
-    # the timed region: K fills, nothing else (no event recording)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for k in range(args.steps):
-        rd.fill_depressions_dev(bufs[k])
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+    # the timed region: K fills, nothing else (no event recording), in rounds of len(bufs) back-to-back fills; between
+    # rounds the copies are restored with the clock stopped
+    dt, done = 0.0, 0
+    while done < args.steps:
+        m = min(len(bufs), args.steps - done)
+        if done:
+            for b in bufs[:m]:
+                b.copy_(Z)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for k in range(m):
+            rd.fill_depressions_dev(bufs[k])
+        torch.cuda.synchronize()
+        dt += time.perf_counter() - t0
+        done += m
     stats = rd.fill_stats()
-    changed = float((bufs[0] != Z).float().mean())
-    W = bufs[0]                        # the filled DEM: input of the stages below
-    del bufs[1:]
-
-    # per-kernel times: a separate, instrumented pass (HIP events around every launch, on the launch stream)
-    prof_steps = 2
-    rd.profile_reset()
-    rd.profile_enable(True)
-    for _ in range(prof_steps):
-        scratch.copy_(Z)
-        rd.fill_depressions_dev(scratch)
-    torch.cuda.synchronize()
-    rd.profile_enable(False)
-    prof = rd.profile_totals()
-    del scratch
-
-    full = None
-    if args.cpu_sample > 0 and (args.cpu_full == 1 or (args.cpu_full < 0 and n == 40000)):
-        full = start_full_reference(Z, W, args.cpu_full_timeout)   # (after every timed fill; the stages below run beside it)
+    W = bufs[m - 1]                    # the last step's filled DEM: the dumped output, input of the stages below
+    changed = float((W != Z).float().mean())
+    bufs[:] = [W]
+    if args.dump_outputs:
+        dump_outputs(torch, W, args.dump_outputs)
 
     ms_step = dt * 1e3 / args.steps
     value = cells / 1e6 / (dt / args.steps)
-    roofline = fill_roofline(prof, stats, cells, prof_steps, dt / args.steps,
-                             os.path.join(ROOT, "profiles", "pmc_traffic.json"), n)
     out = {
         "metric": "Mcells/s Priority-Flood fill, 40k x 40k f32 DEM",
         "value": round(value, 2),
@@ -495,9 +533,33 @@ def main():
             "cells_raised_frac": round(changed, 4),
             "parallelism": "1 GPU",
         },
-        "roofline": roofline,
-        "kernels_ms_per_step": {k: round(v[0] / prof_steps, 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])},
     }
+    if not args.full:
+        emit(out)
+        return
+
+    # ---- --full: everything besides the headline fill ------------------------------------------------------------------
+    from richdem_amd.roofline import fill_roofline
+
+    # per-kernel times: a separate, instrumented pass (HIP events around every launch, on the launch stream)
+    prof_steps = 2
+    rd.profile_reset()
+    rd.profile_enable(True)
+    for _ in range(prof_steps):
+        scratch.copy_(Z)
+        rd.fill_depressions_dev(scratch)
+    torch.cuda.synchronize()
+    rd.profile_enable(False)
+    prof = rd.profile_totals()
+    del scratch
+
+    full = None
+    if args.cpu_sample > 0 and (args.cpu_full == 1 or (args.cpu_full < 0 and n == 40000)):
+        full = start_full_reference(Z, W, args.cpu_full_timeout)   # (after every timed fill; the stages below run beside it)
+
+    out["roofline"] = fill_roofline(prof, stats, cells, prof_steps, dt / args.steps,
+                                    os.path.join(ROOT, "profiles", "pmc_traffic.json"), n)
+    out["kernels_ms_per_step"] = {k: round(v[0] / prof_steps, 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])}
     if not args.no_stages:
         out["stages"] = {"fill": stage_entry(dt / args.steps, cells, 8)}
         out["stages"].update(run_stages(rd, torch, W, -9999.0, Z=Z, pf_flowdirs=not args.no_pf_flowdirs,
@@ -511,7 +573,6 @@ def main():
     if args.cpu_sample > 0:
         out["cpu_baseline"] = cpu_baseline(Z, args.cpu_sample, full)
     emit(out)
-
 
 if __name__ == "__main__":
     main()

@@ -65,3 +65,51 @@ def band_digests_torch(t, band_rows: int = BAND_ROWS) -> np.ndarray:
         out.append(x.sum(dtype=torch.int64))
     d = torch.stack(out).cpu().numpy()
     return d.view(np.uint64)
+
+
+#: every committed file stays below 1 MiB: save_golden keeps each .npz it writes below this many bytes
+GOLDEN_FILE_BYTES = 900 * 1024
+
+
+def save_golden(path: str, **arrays) -> None:
+    """np.savez_compressed(path, **arrays), except that every array whose compressed size is over half of GOLDEN_FILE_BYTES
+    is cut along its first axis into pieces of at most about GOLDEN_FILE_BYTES each, one per file <path stem>.part<i>.npz
+    beside `path`.  load_golden puts them back together."""
+    import glob
+    import os
+    import zlib
+
+    stem = path[:-4]
+    for old in glob.glob(glob.escape(stem) + ".part*.npz"):
+        os.remove(old)
+    main, pieces = {}, []
+    for k, a in arrays.items():
+        a = np.asarray(a)
+        z = len(zlib.compress(np.ascontiguousarray(a).tobytes(), 6))
+        if a.ndim == 0 or 2 * z <= GOLDEN_FILE_BYTES:
+            main[k] = a
+        else:
+            pieces += [(k, c) for c in np.array_split(a, -(-z // GOLDEN_FILE_BYTES))]
+    np.savez_compressed(path, **main)
+    written = [path]
+    for i, (k, c) in enumerate(pieces, 1):
+        written.append(f"{stem}.part{i}.npz")
+        np.savez_compressed(written[-1], **{k: c})
+    for p in written:
+        assert os.path.getsize(p) < 1 << 20, (p, os.path.getsize(p))
+
+
+def load_golden(path: str) -> dict:
+    """The arrays of a golden .npz written by save_golden: `path`'s own, with those of <path stem>.part1.npz, .part2.npz, ...
+    joined along the first axis in that order."""
+    import os
+
+    with np.load(path) as f:
+        out = {k: f[k] for k in f.files}
+    i = 1
+    while os.path.exists(f"{path[:-4]}.part{i}.npz"):
+        with np.load(f"{path[:-4]}.part{i}.npz") as f:
+            for k in f.files:
+                out[k] = np.concatenate([out[k], f[k]]) if k in out else f[k]
+        i += 1
+    return out

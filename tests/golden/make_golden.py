@@ -18,6 +18,8 @@
                         Inputs are stored too, so the tests do not depend on the generator.
 * ref_s3_digests.npz -- (--s3-digests) per-1000-row-band digests of the compiled reference's outputs on the
                         40000 x 40000 bench DEM: BASELINE configs[2] / [4] at full size (see s3_digests()).
+* ref_pyrichdem_names.json -- (--pyrichdem-names) the names the reference's Python package (richdem/__init__.py)
+                        takes from its extension module _richdem and from _richdem.depression_hierarchy.
 /root/reference does not exist on the GPU box; tests read only these .npz files.
 """
 import glob
@@ -299,7 +301,7 @@ def s3_f2(which, size=40000, seed=3):
     differ (an estimate of the differing fraction, with the blocks that hold a difference) instead of asserting zero;
     max_dep is asserted equal."""
     import time
-    from digest import BAND_ROWS, band_digests_np
+    from digest import BAND_ROWS, band_digests_np, save_golden
     oracle.build()
     R = oracle.ref
     assert R.available
@@ -339,7 +341,7 @@ def s3_f2(which, size=40000, seed=3):
     if which == "watersheds":
         g["labels"] = np.int64(out.max())
     path = os.path.join(HERE, f"ref_s3_f2_{which}.npz" if n == 40000 else f"ref_s3_f2_{which}_{n}.npz")
-    np.savez_compressed(path, **g)
+    save_golden(path, **g)                                                 # (samples over the size limit go to .part<i>.npz)
     print("wrote", path, round(secs, 1), "s", os.path.getsize(path), "bytes", flush=True)
 
 
@@ -366,7 +368,7 @@ def s2_dinf(size=10000, seed=2):
     exact equality is the common case, reported per band -- and both outputs at a fixed sample of cells, from which the GPU
     test builds the ULP histogram (tolerance: 1 float32 ULP, north_star)."""
     import time
-    from digest import BAND_ROWS, band_digests_np
+    from digest import BAND_ROWS, band_digests_np, save_golden
     oracle.build()
     R = oracle.ref
     assert R.available
@@ -392,8 +394,24 @@ def s2_dinf(size=10000, seed=2):
          "fa_tarboton_f32_bands": band_digests_np(fa32), "fa_tarboton_sample": fa.ravel()[pos], "fa_tarboton_max": np.float64(fa.max()),
          "ref_seconds/dinf_flow_directions": np.float64(round(t_ang, 2)), "ref_seconds/fa_tarboton": np.float64(round(t_fa, 2))}
     path = os.path.join(HERE, "ref_s2_dinf.npz" if n == 10000 else f"ref_s2_dinf_{n}.npz")
-    np.savez_compressed(path, **g)
+    save_golden(path, **g)                                                 # (samples over the size limit go to .part<i>.npz)
     print("wrote", path, t_ang, t_fa, os.path.getsize(path), flush=True)
+
+
+def pyrichdem_names():
+    """ref_pyrichdem_names.json: every _richdem.<name> and depression_hierarchy.<name> the reference's richdem/__init__.py
+    uses (tests/test_pybind_module.py checks the GPU module's surface against it)."""
+    import json
+    import re
+
+    src = open(os.path.join(REF, "wrappers", "pyrichdem", "richdem", "__init__.py")).read()
+    names = {"_richdem": sorted(set(re.findall(r"_richdem\.([A-Za-z_0-9]+)", src))),
+             "depression_hierarchy": sorted(set(re.findall(r"depression_hierarchy\.([A-Za-z_]+)", src)))}
+    path = os.path.join(HERE, "ref_pyrichdem_names.json")
+    with open(path, "w") as f:
+        json.dump(names, f, indent=1)
+        f.write("\n")
+    print("wrote", path, {k: len(v) for k, v in names.items()})
 
 
 if __name__ == "__main__":
@@ -415,6 +433,8 @@ if __name__ == "__main__":
         f2()
     elif "--variants" in sys.argv:
         variants()
+    elif "--pyrichdem-names" in sys.argv:
+        pyrichdem_names()
     else:
         main()
         f2()

@@ -9,7 +9,7 @@ import pytest
 from conftest import GOLDEN
 
 sys.path.insert(0, GOLDEN)
-from digest import band_digests_np, band_digests_torch  # noqa: E402
+from digest import band_digests_np, band_digests_torch, load_golden, save_golden  # noqa: E402
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64, np.uint8, np.int32])
@@ -50,3 +50,29 @@ def test_small_digest_set_matches_the_oracle_port(orc):
     assert np.array_equal(band_digests_np(E), g["resolve_flats_epsilon"])
     assert np.array_equal(band_digests_np(orc.port.fa_d8_lean(E, np.float32(-9999.0))), g["fa_d8"])
     assert np.array_equal(orc.port.fa_d8_lean(E[:700, :900], np.float32(-9999.0)), orc.port.fa_d8(E[:700, :900], np.float32(-9999.0)))
+
+
+def test_golden_files_over_the_size_limit_are_stored_in_pieces(tmp_path):
+    """save_golden cuts the arrays that would make a file of 1 MiB or more into .part<i>.npz pieces; load_golden returns
+    exactly what was saved."""
+    rng = np.random.default_rng(11)
+    g = {"size": np.int64(7), "bands": rng.integers(0, 2**63, 40, dtype=np.uint64),
+         "sample": rng.random(700_000).astype(np.float32), "dirs": rng.integers(0, 9, 3_000_000).astype(np.uint8)}
+    path = str(tmp_path / "g.npz")
+    save_golden(path, **g)
+    files = sorted(os.listdir(tmp_path))
+    assert len(files) > 2 and all(os.path.getsize(tmp_path / f) < 1 << 20 for f in files), files
+    back = load_golden(path)
+    assert set(back) == set(g)
+    for k in g:
+        assert back[k].dtype == g[k].dtype and back[k].shape == g[k].shape and np.array_equal(back[k], g[k]), k
+    save_golden(path, size=np.int64(1))                          # written again, smaller: no stale pieces are left
+    assert os.listdir(tmp_path) == ["g.npz"] and set(load_golden(path)) == {"size"}
+
+
+@pytest.mark.parametrize("name", ["ref_s2_dinf", "ref_s3_f2_epsilon", "ref_s3_f2_flowdirs"])
+def test_committed_goldens_load_whole(name):
+    g = load_golden(os.path.join(GOLDEN, name + ".npz"))
+    k = int(g["sample_k"])
+    samples = [v for key, v in g.items() if key.endswith("sample")]
+    assert samples and all(v.shape == (k,) for v in samples)

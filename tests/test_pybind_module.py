@@ -3,8 +3,8 @@
 without copying, carries NoData / georeferencing, raises for what is out of scope -- and the reference's own
 `richdem/__init__.py` imports and drives it unchanged (this container only: it reads /root/reference)."""
 import gc
+import json
 import os
-import re
 import subprocess
 import sys
 import textwrap
@@ -12,10 +12,12 @@ import textwrap
 import numpy as np
 import pytest
 
+from conftest import GOLDEN
+
 REF_PKG = "/root/reference/wrappers/pyrichdem"
 
-# every _richdem.<name> the reference's richdem/__init__.py touches (kept here so the check also runs where the
-# reference is absent; test_surface_matches_the_reference_package re-derives it from the source when it is present)
+# every _richdem.<name> the reference's richdem/__init__.py touches (test_surface_matches_the_reference_package checks
+# it against the names recorded from that file in tests/golden/ref_pyrichdem_names.json)
 SURFACE = """Array2D_double Array2D_float Array2D_int16_t Array2D_int32_t Array2D_int64_t Array2D_int8_t Array2D_uint16_t
 Array2D_uint32_t Array2D_uint64_t Array2D_uint8_t Array3D_float FA_D4 FA_D8 FA_FairfieldLeymarieD4 FA_FairfieldLeymarieD8
 FA_Freeman FA_Holmgren FA_OCallaghanD4 FA_OCallaghanD8 FA_Quinn FA_Rho4 FA_Rho8 FA_Tarboton FM_D4 FM_D8
@@ -47,14 +49,16 @@ def test_surface_is_complete(R):
     assert isinstance(R.rdHash(), str) and isinstance(R.rdCompileTime(), str)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PKG), reason="the reference tree is only present in the build container")
 def test_surface_matches_the_reference_package(R):
-    src = open(os.path.join(REF_PKG, "richdem", "__init__.py")).read()
-    used = set(re.findall(r"_richdem\.([A-Za-z_0-9]+)", src))
+    """Every name the reference's richdem/__init__.py takes from _richdem (tests/golden/ref_pyrichdem_names.json,
+    make_golden.py --pyrichdem-names) is bound."""
+    with open(os.path.join(GOLDEN, "ref_pyrichdem_names.json")) as f:
+        names = json.load(f)
+    used = set(names["_richdem"])
     assert used, "no _richdem uses found"
     assert not [n for n in sorted(used) if not hasattr(R, n)]
     assert used <= set(SURFACE)
-    for n in set(re.findall(r"depression_hierarchy\.([A-Za-z_]+)", src)):
+    for n in names["depression_hierarchy"]:
         assert hasattr(R.depression_hierarchy, n), n
 
 

@@ -16,7 +16,7 @@ import pytest
 from conftest import GOLDEN, ROOT
 
 sys.path.insert(0, GOLDEN)
-from digest import band_digests_torch  # noqa: E402
+from digest import band_digests_torch, load_golden  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +35,7 @@ def test_dinf_10k_against_the_compiled_reference(rd):
 
     path = os.path.join(GOLDEN, "ref_s2_dinf.npz")
     assert os.path.exists(path), "tests/golden/ref_s2_dinf.npz missing (make_golden.py --s2-dinf)"
-    g = np.load(path)
+    g = load_golden(path)
     n, rows = int(g["size"]), int(g["band_rows"])
     W = torch.empty((n, n), dtype=torch.float32, device="cuda")
     rd.synth_dem_dev(W, seed=int(g["seed"]))

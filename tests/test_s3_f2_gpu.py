@@ -25,7 +25,7 @@ import pytest
 from conftest import GOLDEN, ROOT
 
 sys.path.insert(0, GOLDEN)
-from digest import band_digests_torch  # noqa: E402
+from digest import band_digests_torch, load_golden  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -90,7 +90,7 @@ def _load(which):
     path = os.path.join(GOLDEN, f"ref_s3_f2_{which}.npz")
     if not os.path.exists(path):
         pytest.skip(f"{path} not generated (make_golden.py --s3-f2 {which})")
-    g = np.load(path)
+    g = load_golden(path)
     assert int(g["size"]) == 40000
     return g
 

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/../.."
 mkdir -p gpurun_out
 for cfg in "${@:-RDGPU_FILL_PAIRS_BPC=6}"; do
 for ab in 0 4 8 16 32 64; do
-  env $cfg RDGPU_FILL_PAIRS_ABLATE=$ab python bench.py --steps 3 --no-stages --no-host --cpu-sample 0 2>/dev/null | python -c "
+  env $cfg RDGPU_FILL_PAIRS_ABLATE=$ab python bench.py --full --steps 3 --no-stages --no-host --cpu-sample 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['kernels_ms_per_step']

@@ -3,7 +3,7 @@
 
     python tools/profile_round.py <tag> [--steps K] [--sq]
 
-runs, back to back and all on the same command (`python bench.py --steps K --warmup 1`):
+runs, back to back and all on the same command (`python bench.py --full --steps K --warmup 1`):
   1. the plain bench               -> gpurun_out/<tag>_fill40k_bench.json
   2. rocprofv3 --kernel-trace --stats  -> gpurun_out/<tag>_fill40k_kernel_stats.csv
   3. rocprofv3 --pmc FETCH_SIZE  and  4. rocprofv3 --pmc WRITE_SIZE (separate passes, kernel-trace only)
@@ -71,9 +71,9 @@ def git_sha():
 def main():
     tag = sys.argv[1]
     steps = sys.argv[sys.argv.index("--steps") + 1] if "--steps" in sys.argv else "3"
-    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "1"]
+    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", steps, "--warmup", "1"]
     # the profiling passes run the fill only, or (--path) the fill and the stages after it; never the host path
-    prof_tail = (["--steps", "1", "--warmup", "0", "--cpu-sample", "0", "--no-host", "--no-pf-flowdirs", "--no-draining-mfd"]
+    prof_tail = (["--full", "--steps", "1", "--warmup", "0", "--cpu-sample", "0", "--no-host", "--no-pf-flowdirs", "--no-draining-mfd"]
                  + ([] if "--path" in sys.argv else ["--no-stages"]))
     what = "path40k" if "--path" in sys.argv else "fill40k"
     os.makedirs(OUT, exist_ok=True)

@@ -277,7 +277,6 @@ RDGPU_DECL_WS(u64, uint64_t)
  *                              then rounds on the component-pair list it records)
  *   RDGPU_FILL_EDGE_CAP=<n>    capacity of that list in records (default min(12 per basin, cells/2)); a list
  *                              that does not fit falls back to raster passes
- *   RDGPU_FILL_DEDUP=0         do not merge the list's records per component pair between rounds
  *   RDGPU_FILL_ROUND_BATCH=<n> contraction rounds enqueued per stream synchronisation (default: all of them at once --
  *                              a fill synchronises twice, rdgpu_fill_stats::host_syncs) */
 /* Statistics of the last fill on this process (for DESIGN.md / bench.py reporting). */

@@ -556,16 +556,12 @@ __device__ __forceinline__ void pair_spill(const EdgeOut &eo, unsigned long long
   }
 }
 
-// L16 (the compact-label fill below): `lab` holds 16-bit slots (the cell's root within its 64 x 64 descent tile), a cell's
-// component is cur[tile_base[its tile] + slot] -- cur is then the node table curN --, and FIRST is not used.
-template <class T, int TOPO, bool FIRST, bool VEC, bool EMIT, bool L16 = false>
+template <class T, int TOPO, bool FIRST, bool VEC, bool EMIT>
 __global__ __launch_bounds__(NTHR) void k_scan(const T *__restrict__ z, const uint32_t *__restrict__ lab,
                                                const uint32_t *__restrict__ cur, unsigned long long *best,
                                                int w, int h, uint32_t B, uint32_t tilesX, uint32_t ntiles,
                                                const uint32_t *__restrict__ tiles_in, uint32_t nwork,
-                                               uint8_t *alive_out, EdgeOut eo,
-                                               const uint32_t *__restrict__ tile_base = nullptr, uint32_t dtx = 0,
-                                               const uint8_t *__restrict__ skip = nullptr) {
+                                               uint8_t *alive_out, EdgeOut eo) {
   __shared__ __attribute__((aligned(8))) uint32_t sk[LH * LW];
   __shared__ uint32_t sc[LH * LW];
   // The component table: in the pair pass it is only needed AFTER the pairs are reduced, when the keys are dead, so it
@@ -587,7 +583,6 @@ __global__ __launch_bounds__(NTHR) void k_scan(const T *__restrict__ z, const ui
   if (wi >= nwork) return;
   const uint32_t t = tiles_in ? tiles_in[wi] : wi;
   const int x0 = (int)(t % tilesX) * TW, y0 = (int)(t / tilesX) * TH;
-  if (L16 && skip && skip[(uint32_t)(y0 / DH) * dtx + (uint32_t)(x0 / DW)]) return;   // nothing but outlets here, ring included
   if (!EMIT)
     for (int i = threadIdx.x; i < SC_SLOTS; i += NTHR) { tab_id[i] = 0xFFFFFFFFu; tab_val[i] = ~0ull; tab_cross[i] = 0; }
   if (EMIT)
@@ -604,23 +599,7 @@ __global__ __launch_bounds__(NTHR) void k_scan(const T *__restrict__ z, const ui
     constexpr int QPT = (NQ + NTHR - 1) / NTHR;       // per thread
     Quad<T> zq[QPT];   // four cells per load: 16 / 8 / 4 bytes for 4- / 2- / 1-byte elevations
     Quad<uint32_t> lq[QPT];
-    uint32_t tb[L16 ? QPT : 1];   // L16: node base of the descent tile the quad lies in
     bool ok[QPT];
-    const uint16_t *lab16 = reinterpret_cast<const uint16_t *>(lab);
-    uint32_t tbU = 0, tbC = 0, tbD = 0, tbL[3] = {0, 0, 0}, tbR[3] = {0, 0, 0};
-    if (L16) {
-      static_assert(TW == DW && DH % TH == 0, "a scan tile lies inside one descent tile");
-      const int dcol = x0 / DW, rU = max(y0 - 1, 0) / DH, rC = y0 / DH, rD = min(y0 + TH, h - 1) / DH;
-      const int rows3[3] = {rU, rC, rD};
-      tbU = tile_base[(uint32_t)rU * dtx + (uint32_t)dcol];
-      tbC = tile_base[(uint32_t)rC * dtx + (uint32_t)dcol];
-      tbD = tile_base[(uint32_t)rD * dtx + (uint32_t)dcol];
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        tbL[k] = tile_base[(uint32_t)rows3[k] * dtx + (uint32_t)max(dcol - 1, 0)];
-        tbR[k] = tile_base[(uint32_t)rows3[k] * dtx + min((uint32_t)dcol + 1u, dtx - 1u)];
-      }
-    }
 #pragma unroll
     for (int r = 0; r < QPT; r++) {
       const int i = threadIdx.x + r * NTHR;
@@ -629,19 +608,8 @@ __global__ __launch_bounds__(NTHR) void k_scan(const T *__restrict__ z, const ui
       ok[r] = i < NQ && gy >= 0 && gy < h && gx < w;
       if (ok[r]) {
         const size_t g = (size_t)gy * w + gx;
-        if (L16) {
-          // (the labels first, the elevations in a loop of their own below: loads return in order, and the component
-          // gathers only wait for the labels -- the elevation loads are still in flight behind them)
-          const Quad<uint16_t> sq = load_quad<uint16_t, VEC>(lab16 + (g - gx), gx, w, (uint16_t)0);
-#pragma unroll
-          for (int e = 0; e < 4; e++) lq[r].v[e] = sq.v[e];
-          // node base of the quad's descent tile: the scan tile lies inside ONE descent tile (TW == DW, TH divides DH),
-          // only its halo rows may belong to the tile above / below -- three block-uniform (scalar) loads
-          tb[r] = ly == 0 ? tbU : ly == LH - 1 ? tbD : tbC;
-        } else {
-          zq[r] = load_quad<T, VEC>(z + (g - gx), gx, w, T());
-          lq[r] = load_quad<uint32_t, VEC>(lab + (g - gx), gx, w, B);   // past the row end: the outside's label
-        }
+        zq[r] = load_quad<T, VEC>(z + (g - gx), gx, w, T());
+        lq[r] = load_quad<uint32_t, VEC>(lab + (g - gx), gx, w, B);   // past the row end: the outside's label
       }
     }
     // halo columns: one cell per thread for the first 2 * LH threads
@@ -649,28 +617,13 @@ __global__ __launch_bounds__(NTHR) void k_scan(const T *__restrict__ z, const ui
     const int hly = threadIdx.x >> 1, hlx = (threadIdx.x & 1) ? LW - 1 : 0;
     bool hok = false;
     T hz = T();
-    uint32_t hl = 0, htb = 0;
+    uint32_t hl = 0;
     if (hcell) {
       const int gx = x0 - 1 + hlx, gy = y0 - 1 + hly;
       hok = gx >= 0 && gx < w && gy >= 0 && gy < h;
       if (hok) {
-        if (L16) {
-          hl = lab16[(size_t)gy * w + gx];
-          const int k = hly == 0 ? 0 : hly == LH - 1 ? 2 : 1;
-          htb = (threadIdx.x & 1) ? (k == 0 ? tbR[0] : k == 1 ? tbR[1] : tbR[2]) : (k == 0 ? tbL[0] : k == 1 ? tbL[1] : tbL[2]);
-        } else {
-          hl = lab[(size_t)gy * w + gx];
-        }
+        hl = lab[(size_t)gy * w + gx];
         hz = z[(size_t)gy * w + gx];
-      }
-    }
-    if (L16) {
-#pragma unroll
-      for (int r = 0; r < QPT; r++) {
-        const int i = threadIdx.x + r * NTHR;
-        const int ly = i / (TW / 4), q = i - ly * (TW / 4);
-        const int gx = x0 + 4 * q, gy = y0 - 1 + ly;
-        if (ok[r]) zq[r] = load_quad<T, VEC>(z + (size_t)gy * w, gx, w, T());
       }
     }
     uint32_t cq[QPT][4];
@@ -678,24 +631,12 @@ __global__ __launch_bounds__(NTHR) void k_scan(const T *__restrict__ z, const ui
     for (int r = 0; r < QPT; r++) {
       // branch-free: an absent quad reads the outside's entry (label B: cur[B] == B | CLOSED), so all gathers of
       // the thread are in flight together
-      if (L16) {
-        const int q4 = 4 * ((threadIdx.x + r * NTHR) % (TW / 4));
+      const uint32_t l[4] = {ok[r] ? lq[r].v[0] : B, ok[r] ? lq[r].v[1] : B, ok[r] ? lq[r].v[2] : B, ok[r] ? lq[r].v[3] : B};
 #pragma unroll
-        for (int e = 0; e < 4; e++) {   // (absent cells and cells past the row end: node 0 is read, the outside is taken)
-          const bool in = ok[r] && x0 + q4 + e < w;
-          const uint32_t c = cur[in ? tb[r] + lq[r].v[e] : 0u];
-          cq[r][e] = in ? c : (B | CLOSED);
-        }
-      } else {
-        const uint32_t l[4] = {ok[r] ? lq[r].v[0] : B, ok[r] ? lq[r].v[1] : B, ok[r] ? lq[r].v[2] : B, ok[r] ? lq[r].v[3] : B};
-#pragma unroll
-        for (int e = 0; e < 4; e++) cq[r][e] = RD_COMP(l[e]);
-      }
+      for (int e = 0; e < 4; e++) cq[r][e] = RD_COMP(l[e]);
     }
     const uint32_t hlsafe = hok ? hl : B;
-    uint32_t hc;
-    if (L16) { const uint32_t c = cur[hok ? htb + hl : 0u]; hc = hok ? c : (B | CLOSED); }
-    else hc = RD_COMP(hlsafe);
+    const uint32_t hc = RD_COMP(hlsafe);
 #pragma unroll
     for (int r = 0; r < QPT; r++) {
       const int i = threadIdx.x + r * NTHR;
@@ -945,17 +886,19 @@ __global__ __launch_bounds__(NTHR) void k_scan(const T *__restrict__ z, const ui
 // (current a, current b, key).  SEG: the input is the segmented list of the raster pass (one segment per block
 // range: segcap is a multiple of the 2048 records a block covers); otherwise a dense list of n records.
 constexpr int EPT = 8;
-constexpr int DT_SLOTS = 4096;   // DEDUP: pair table of a block (2048 records)
-// DEDUP (the dense rounds): the records of a block are first merged per component pair in an LDS table -- after a few
-// rounds most records of a block connect the same few large components, and without this the lists stop shrinking
-// and thousands of lanes hit the same best[] entries with atomics.
-template <bool SEG, bool DEDUP>
+constexpr int DT_SLOTS = 4096;   // the dense rounds' pair table of a block (2048 records)
+// The dense rounds (!SEG) first merge the records of a block per component pair in an LDS table -- after a few rounds
+// most records of a block connect the same few large components, and without this the lists stop shrinking and
+// thousands of lanes hit the same best[] entries with atomics.  (Merging per pair in the first list round was measured
+// slower: 2.5 vs 1.4 ms -- its records are already merged per tile.)
+template <bool SEG>
 __global__ __launch_bounds__(NTHR) void k_edge_round(const uint32_t *__restrict__ ea, const uint32_t *__restrict__ eb,
                                                      const uint32_t *__restrict__ ek, uint32_t n,
                                                      const uint32_t *__restrict__ segcount, uint32_t segcap,
                                                      const uint32_t *__restrict__ cur, unsigned long long *best, uint32_t B,
                                                      uint32_t *oa, uint32_t *ob, uint32_t *ok, uint32_t *ocount,
                                                      const uint32_t *__restrict__ dyn = nullptr) {
+  constexpr bool DEDUP = !SEG;
   __shared__ uint32_t wtot[NTHR / 64];
   __shared__ uint32_t bbase, dn;
   __shared__ unsigned long long dt_pair[DEDUP ? DT_SLOTS : 1];
@@ -1465,8 +1408,6 @@ static void fill_local_phase(const T *d_z, int w, int h, int open_top, int open_
   // (both exist for the tests of the overflow fallback and for A/B timing).
   const char *env_edges = getenv("RDGPU_FILL_EDGES"), *env_cap = getenv("RDGPU_FILL_EDGE_CAP");
   const bool edges_enabled = !(env_edges && env_edges[0] == '0');
-  const char *env_dedup = getenv("RDGPU_FILL_DEDUP");
-  const bool dedup = !(env_dedup && env_dedup[0] == '0');
   bool edge_mode = false;           // rounds 2.. run on the pair list
   EdgeOut eo{};
   uint32_t nseg = 1, nedges = 0;
@@ -1496,17 +1437,12 @@ static void fill_local_phase(const T *d_z, int w, int h, int open_top, int open_
       RD_HIP(hipMemsetAsync(dflags + 4, 0, sizeof(uint32_t), s));
       const uint32_t *ia = elist[ein], *ib = elist[ein] + ecap[ein], *ik = elist[ein] + 2 * ecap[ein];
       uint32_t *oa = elist[eout], *ob = elist[eout] + ecap[eout], *ok = elist[eout] + 2 * ecap[eout];
-      // (merging per pair in the first list round was measured slower: 2.5 vs 1.4 ms -- its records are already
-      // merged per tile)
       if (eseg)
-        RD_LAUNCH("fill.edge_round", (k_edge_round<true, false>), dim3(cdiv(ecap[ein], NTHR * EPT)), dim3(NTHR), 0, s, ia, ib, ik,
+        RD_LAUNCH("fill.edge_round", (k_edge_round<true>), dim3(cdiv(ecap[ein], NTHR * EPT)), dim3(NTHR), 0, s, ia, ib, ik,
                   (uint32_t)ecap[ein], (const uint32_t *)eo.segcount, eo.segcap, (const uint32_t *)cur, best, B, oa, ob, ok,
                   dflags + 4);
-      else if (nedges > 0 && dedup)
-        RD_LAUNCH("fill.edge_round", (k_edge_round<false, true>), dim3(cdiv(nedges, NTHR * EPT)), dim3(NTHR), 0, s, ia, ib, ik,
-                  nedges, (const uint32_t *)nullptr, 0u, (const uint32_t *)cur, best, B, oa, ob, ok, dflags + 4);
       else if (nedges > 0)
-        RD_LAUNCH("fill.edge_round", (k_edge_round<false, false>), dim3(cdiv(nedges, NTHR * EPT)), dim3(NTHR), 0, s, ia, ib, ik,
+        RD_LAUNCH("fill.edge_round", (k_edge_round<false>), dim3(cdiv(nedges, NTHR * EPT)), dim3(NTHR), 0, s, ia, ib, ik,
                   nedges, (const uint32_t *)nullptr, 0u, (const uint32_t *)cur, best, B, oa, ob, ok, dflags + 4);
       eseg = false;
       ein = eout;
@@ -1516,8 +1452,7 @@ static void fill_local_phase(const T *d_z, int w, int h, int open_top, int open_
             h, B, tilesX, ntiles, (const uint32_t *)(LIST), (uint32_t)(NWORK), alive, eo)
 #define RD_SCAN_V(FIRST_, EMIT_, LIST, NWORK)                                                                    \
   { if (vec) RD_SCAN(FIRST_, true, EMIT_, LIST, NWORK); else RD_SCAN(FIRST_, false, EMIT_, LIST, NWORK); }
-      const char *env_first = getenv("RDGPU_FILL_FIRST");   // =0: the pair pass gathers cur[label] like a shard's (A/B probe)
-      if (first && !sharded && !(env_first && env_first[0] == '0')) { if (emit) RD_SCAN_V(true, true, nullptr, ntiles) else RD_SCAN_V(true, false, nullptr, ntiles) }
+      if (first && !sharded) { if (emit) RD_SCAN_V(true, true, nullptr, ntiles) else RD_SCAN_V(true, false, nullptr, ntiles) }
       else if (first) { if (emit) RD_SCAN_V(false, true, nullptr, ntiles) else RD_SCAN_V(false, false, nullptr, ntiles) }
       else RD_SCAN_V(false, false, tlist, nlive)
 #undef RD_SCAN_V
@@ -2009,7 +1944,7 @@ static void fill_max_dep_host(T *dem, int w, int h, int topology, uint64_t max_d
 //                    the tile | OUTP.  A cell's label is the SLOT of its root: 2 bytes per cell (lab16).
 //   k_resolve_nodes  node -> basin (curN): a pending node follows lab16 / G from tile to tile.  A table pass over ~2 % of
 //                    the cell count replaces k_tile_label's raster pass (10.7 GB at S3).
-//   k_scan<L16>      the one pair pass, reading z + lab16 (6 B / cell) and gathering the components from curN.
+//   k_pairs16        the one pair pass, reading z + lab16 (6 B / cell) and taking the components from curN.
 //   rounds           unchanged (pair list).
 //   k_finalize16     z <- max(z, level of the cell's node): z + lab16 and the tile's node levels from LDS.
 // (Tried first and dropped: the pairs in the descent kernel itself, on slots, with the pairs across tile edges from edge
@@ -2545,14 +2480,14 @@ __global__ __launch_bounds__(NTHR) void k_finalize16(T *z, const uint16_t *__res
 }
 
 // ==========================================================================================================
-// The pair pass of the compact-label fill as a PERSISTENT kernel (r04).
+// The pair pass of the compact-label fill, a PERSISTENT kernel (r04).
 //
-// k_scan<L16> spends two thirds of its wave cycles parked: per 64 x 32 tile it goes through a chain of dependent global
-// round trips (tile bases -> 16-bit labels -> component gathers from the node table) before its LDS phases can start, and
-// a block does nothing else meanwhile.  Here a block stays resident and walks its share of the tiles (its XCD's band,
-// strided by the number of blocks per XCD); the NEXT tile's rows, labels, ring cells and the node table of its descent
-// tile are loaded into registers while the current tile goes through its LDS phases, so the phases of successive tiles
-// follow each other without the round trips in between.  The components of the tile's own cells come from the descent
+// It is persistent because one block per 64 x 32 tile spent two thirds of its wave cycles parked on a chain of dependent
+// global round trips (tile bases -> 16-bit labels -> component gathers from the node table) before its LDS phases could
+// start.  Here a block stays resident and walks its share of the tiles (its XCD's band, strided by the number of blocks
+// per XCD); the NEXT tile's rows, labels, ring cells and the node table of its descent tile are loaded into registers
+// while the current tile goes through its LDS phases, so the phases of successive tiles follow each other without the
+// round trips in between.  The components of the tile's own cells come from the descent
 // tile's node table staged in LDS (one coalesced read of its ~80 entries instead of 2 048 gathers); only the 196 cells
 // of the ring, which belong to the neighbouring descent tiles, are gathered one by one.  Phases, tables, records and
 // proposals are k_scan<EMIT>'s.
@@ -2587,7 +2522,7 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
                                                   EdgeOut eo,
                                                   const uint32_t *__restrict__ tile_base,
                                                   const uint32_t *__restrict__ tile_count, uint32_t dtx,
-                                                  const uint8_t *__restrict__ skip, int precheck,
+                                                  const uint8_t *__restrict__ skip,
                                                   const uint32_t *__restrict__ edgeK, const uint16_t *__restrict__ edgeS) {
   __shared__ __attribute__((aligned(8))) uint32_t sk[LH * LW];
   __shared__ uint32_t sc[LH * LW];
@@ -2600,18 +2535,14 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
   unsigned long long *const tab_val = reinterpret_cast<unsigned long long *>(sk + SC_SLOTS);
 
   // ---- this block's tiles: its XCD's band, strided over the XCD's blocks (tile j, j + blocks, ...), so that the blocks of
-  // an XCD work on neighbouring tiles at any time; RDGPU_FILL_PAIRS_STRIDED=0: a run of consecutive tiles per block
-  // (measured 0.15 ms slower; neither keeps the neighbours' rows in the 4 MB L2 for the ring columns -- hence the edge
-  // records: 22.9 GB fetched per launch without them, 12.5 with).
-  const uint32_t xcd = blockIdx.x & 7u, kb = gridDim.x >> 3, per = (nwork + 7u) / 8u;
+  // an XCD work on neighbouring tiles at any time (a run of consecutive tiles per block was measured 0.15 ms slower;
+  // neither keeps the neighbours' rows in the 4 MB L2 for the ring columns -- hence the edge records: 22.9 GB fetched per
+  // launch without them, 12.5 with).
+  const uint32_t xcd = blockIdx.x & 7u, kstep = gridDim.x >> 3, per = (nwork + 7u) / 8u;
   const uint32_t seg = blockIdx.x;   // the block's own segment of the pair list: no counter in HBM to wait for
-  const uint32_t run = (per + kb - 1u) / kb;
-  const bool strided = (precheck & 2) != 0;
-  uint32_t it = strided ? (blockIdx.x >> 3) : (blockIdx.x >> 3) * run;
-  const uint32_t it_end = strided ? per : min(it + run, per);
-  const uint32_t kstep = strided ? kb : 1u;
+  uint32_t it = blockIdx.x >> 3;
   auto next_tile = [&](uint32_t &i) -> uint32_t {
-    while (i < it_end) {
+    while (i < per) {
       const uint32_t wi = xcd * per + i;
       if (wi >= nwork) break;
       const uint32_t t = tiles_in ? tiles_in[wi] : wi;
@@ -2620,7 +2551,7 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
       if (!skip[(uint32_t)(y0 / DH) * dtx + (uint32_t)(x0 / DW)]) return t;
       i += kstep;
     }
-    i = it_end;
+    i = per;
     return NO_TILE;
   };
   if (threadIdx.x == 0) seg_fill = 0;
@@ -2806,7 +2737,7 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
       uint32_t total = 0;
 #pragma unroll
       for (int j = 0; j < ROWS; j++) total += (uint32_t)__popcll(bal[j]);
-      if (total && !(precheck & 16)) {
+      if (total) {
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(&nlist, total);
         base = __shfl(base, 0, 64);
@@ -2822,7 +2753,7 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
     __syncthreads();
     load_b(tid);
     // ---- phase 2: the pairs (k_scan<EMIT>'s) -----------------------------------------------------------------------
-    const uint32_t nl = (precheck & 4) ? 0u : nlist;
+    const uint32_t nl = nlist;
     constexpr int NF = TOPO == 8 ? 4 : 2;
     const int foff[4] = {1, TOPO == 8 ? LW + 1 : LW, LW, LW - 1};
     for (uint32_t i = tid; i < nl; i += NTHR) {
@@ -2831,13 +2762,6 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
       uint32_t nD[NF], nH[NF];
 #pragma unroll
       for (int e = 0; e < NF; e++) { nD[e] = sc[o + foff[e]]; nH[e] = sk[o + foff[e]]; }
-      if (precheck & 64) {   // (timing probe: the gathers alone)
-        uint32_t sink = C ^ kc;
-#pragma unroll
-        for (int e = 0; e < NF; e++) sink ^= nD[e] ^ nH[e];
-        if (sink == 0x12345u) nlist = 1;
-        continue;
-      }
       uint32_t pd[2] = {C, C}, pk[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
 #pragma unroll
       for (int e = 0; e < NF; e++) {
@@ -2852,10 +2776,6 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
               pair_spill_local(eo, best, seg, &seg_fill, C < D ? C : D, C < D ? D : C, hn);
           }
         }
-      }
-      if (precheck & 32) {   // (timing probe: gathers + the neighbours' sorting into two components, no table)
-        if ((pd[0] ^ pd[1] ^ pk[0] ^ pk[1]) == 0x12345u) nlist = 1;
-        continue;
       }
       uint32_t ps[2], pq[2], lo[2], hi[2];
       unsigned long long pv[2];
@@ -2889,7 +2809,7 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
       if (occ) list[base + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)tid;
     }
     __syncthreads();
-    const uint32_t tot = (precheck & 8) ? 0u : pt_n;
+    const uint32_t tot = pt_n;
     if (tid == 0) {
       uint32_t ob = seg_fill;   // (spills are over: nothing else touches the counter until the next tile's pairs)
       if (ob + tot > eo.seglimit) { *eo.overflow = 1; ob = 0xFFFFFFFFu; }
@@ -2918,8 +2838,7 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
       const uint32_t C = tab_id[tid];
       if (C != 0xFFFFFFFFu) {
         const unsigned long long cand = tab_val[tid];
-        if (precheck & 1) { if (cand < best[C]) atomicMin(&best[C], cand); }
-        else atomicMin(&best[C], cand);
+        if (cand < best[C]) atomicMin(&best[C], cand);   // cheap (possibly stale) pre-check first
       }
     }
     const uint32_t ob = pt_base;
@@ -2937,7 +2856,16 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
     if (tn == NO_TILE) break;
     t = tn;
   }
-  if (threadIdx.x == 0) eo.segcount[seg] = seg_fill;
+  // (after an overflow seg_fill can lie past seglimit: the rounds enqueued before the host sees the flag read only the
+  // records that were written)
+  if (threadIdx.x == 0) eo.segcount[seg] = min(seg_fill, eo.seglimit);
+}
+
+// f(std::true_type()) or f(std::false_type()): a runtime flag becomes a template argument of the launches in f
+template <class F>
+static void with_flag(bool b, F &&f) {
+  if (b) f(std::true_type());
+  else f(std::false_type());
 }
 
 template <class T>
@@ -2948,30 +2876,26 @@ static void fill_finalize16(T *d_z, int w, int h, const FillBuffers &fb, hipStre
   RD_LAUNCH("fill.node_levels", k_node_levels, ngrid, dim3(NTHR), 0, s, (const uint32_t *)fb.curN, (const uint32_t *)fb.acc,
             (const unsigned long long *)fb.counters, fb.rcap, fb.lvl);
   const bool vec = (w % 4) == 0 && (reinterpret_cast<uintptr_t>(d_z) % (4 * sizeof(T))) == 0;
-  if (vec)
-    RD_LAUNCH("fill.finalize", (k_finalize16<T, true>), dim3(xcd_grid(dnt)), dim3(NTHR), 0, s, d_z, (const uint16_t *)fb.lab16,
+  with_flag(vec, [&](auto V) {
+    RD_LAUNCH("fill.finalize", (k_finalize16<T, V>), dim3(xcd_grid(dnt)), dim3(NTHR), 0, s, d_z, (const uint16_t *)fb.lab16,
               (const uint32_t *)fb.lvl, (const uint32_t *)fb.tile_base, (const uint32_t *)fb.tile_count, w, h, dtx, dnt,
               (const uint8_t *)nullptr, (const uint32_t *)nullptr);
-  else
-    RD_LAUNCH("fill.finalize", (k_finalize16<T, false>), dim3(xcd_grid(dnt)), dim3(NTHR), 0, s, d_z, (const uint16_t *)fb.lab16,
-              (const uint32_t *)fb.lvl, (const uint32_t *)fb.tile_base, (const uint32_t *)fb.tile_count, w, h, dtx, dnt,
-              (const uint8_t *)nullptr, (const uint32_t *)nullptr);
+  });
 }
 
 // The compact-label fill's host side.  false: the DEM does not fit the scheme's buffers (more nodes or pair records than
-// provided for: e.g. white noise) or it was switched off -- the DEM has not been changed, the classic path runs.
+// provided for: e.g. white noise), a hook chain was left unfinished, or RDGPU_FILL_EDGES=0 asks for the raster rounds --
+// the DEM has not been changed, the classic path runs.
 // lists (optional, with skip): device arrays [descent tiles to visit | scan tiles to visit | tiles to finalize], each of
 // `stride` entries, and their lengths on the host
-// resident blocks of the persistent pair pass: what the kernel's registers and LDS let a CU hold (asked of the runtime;
-// RDGPU_FILL_PAIRS_BPC overrides), times the CUs, rounded to a multiple of 8 so that every XCD gets the same number
+// resident blocks of the persistent pair pass: what the kernel's registers and LDS let a CU hold (asked of the runtime),
+// times the CUs, rounded to a multiple of 8 so that every XCD gets the same number
 template <class K>
 static int pairs_blocks(K kernel) {
   int dev = 0, cus = 0, bpc = 0;
   RD_HIP(hipGetDevice(&dev));
   RD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const char *e = getenv("RDGPU_FILL_PAIRS_BPC");
-  if (e) bpc = atoi(e);
-  else RD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kernel, NTHR, 0));
+  RD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kernel, NTHR, 0));
   return std::max(8, (cus * std::max(bpc, 1)) / 8 * 8);
 }
 
@@ -2987,8 +2911,6 @@ template <class T, int TOPO>
 static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outlet = nullptr, const uint8_t *skip = nullptr,
                        const SparseLists *lists = nullptr, FillBuffers *keep = nullptr, BufAlloc *alloc = nullptr,
                        int open_top = 0, int open_bottom = 0) {
-  const char *fe = getenv("RDGPU_FILL_FUSED");   // =0: the classic four-pass fill (A/B and tests)
-  if (fe && fe[0] == '0') return false;
   const char *env_edges = getenv("RDGPU_FILL_EDGES");
   if (env_edges && env_edges[0] == '0') return false;   // (the raster-round fallback lives in the classic path)
   const uint64_t n64 = (uint64_t)w * (uint64_t)h;
@@ -3023,8 +2945,7 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   uint32_t *pitoff = ws.buf<uint32_t>("fused.pitoff", FSTRIPES);
   fo.overflow = dflags + 5;
   uint32_t *curN = (uint32_t *)persistent("fused.curN", (size_t)fo.gcap * 4);
-  const char *env_edge = getenv("RDGPU_FILL_EDGECOLS");   // =0: ring columns from the raster (A/B)
-  if (!outlet && !(env_edge && env_edge[0] == '0')) {   // (with outlets, tiles are skipped: their records would be stale)
+  if (!outlet) {   // (with outlets, tiles are skipped: their records would be stale)
     fo.edgeK = ws.buf<uint32_t>("fused.edgeK", (size_t)dnt * 2 * DH);
     fo.edgeS = ws.buf<uint16_t>("fused.edgeS", (size_t)dnt * 2 * DH);
   }
@@ -3039,24 +2960,16 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   const uint32_t *dl = listed ? lists->d : nullptr, *sl_ = listed ? lists->d + lists->stride : nullptr,
                  *fl = listed ? lists->d + 2 * (size_t)lists->stride : nullptr;
   if (listed && lists->n[0] == 0) return true;   // nothing but walls anywhere: nothing to raise
-  if (outlet && vec)
-    RD_LAUNCH("fill.descent", (k_descent16<T, TOPO, true, true>), dim3(listed ? lists->n[0] : xcd_grid(dnt)), dim3(NTHR), 0, s,
-              (const T *)d_z, fo, w, h, dtx, dnt, outlet, skip, dl, 0, 0);
-  else if (outlet)
-    RD_LAUNCH("fill.descent", (k_descent16<T, TOPO, false, true>), dim3(listed ? lists->n[0] : xcd_grid(dnt)), dim3(NTHR), 0, s,
-              (const T *)d_z, fo, w, h, dtx, dnt, outlet, skip, dl, 0, 0);
-  else if (sharded && vec)
-    RD_LAUNCH("fill.descent", (k_descent16<T, TOPO, true, false, true>), dim3(xcd_grid(dnt)), dim3(NTHR), 0, s, (const T *)d_z, fo, w, h, dtx,
-              dnt, (const uint8_t *)nullptr, (const uint8_t *)nullptr, (const uint32_t *)nullptr, open_top, open_bottom);
-  else if (sharded)
-    RD_LAUNCH("fill.descent", (k_descent16<T, TOPO, false, false, true>), dim3(xcd_grid(dnt)), dim3(NTHR), 0, s, (const T *)d_z, fo, w, h, dtx,
-              dnt, (const uint8_t *)nullptr, (const uint8_t *)nullptr, (const uint32_t *)nullptr, open_top, open_bottom);
-  else if (vec)
-    RD_LAUNCH("fill.descent", (k_descent16<T, TOPO, true>), dim3(xcd_grid(dnt)), dim3(NTHR), 0, s, (const T *)d_z, fo, w, h, dtx, dnt,
-              (const uint8_t *)nullptr, (const uint8_t *)nullptr, (const uint32_t *)nullptr, 0, 0);
-  else
-    RD_LAUNCH("fill.descent", (k_descent16<T, TOPO, false>), dim3(xcd_grid(dnt)), dim3(NTHR), 0, s, (const T *)d_z, fo, w, h, dtx, dnt,
-              (const uint8_t *)nullptr, (const uint8_t *)nullptr, (const uint32_t *)nullptr, 0, 0);
+  // (outlets never come with a cut; the kernel reads outlet, skip and dl only with OUTLETS, the cut rows only with CUT)
+  with_flag(vec, [&](auto V) {
+    auto descent = [&](auto OUTLETS, auto CUT) {
+      RD_LAUNCH("fill.descent", (k_descent16<T, TOPO, V, OUTLETS, CUT>), dim3(listed ? lists->n[0] : xcd_grid(dnt)), dim3(NTHR), 0, s,
+                (const T *)d_z, fo, w, h, dtx, dnt, outlet, skip, dl, open_top, open_bottom);
+    };
+    if (outlet) descent(std::true_type(), std::false_type());
+    else if (sharded) descent(std::false_type(), std::true_type());
+    else descent(std::false_type(), std::false_type());
+  });
   RD_LAUNCH("fill.stripe_offsets", k_stripe_offsets, dim3(1), dim3(64), 0, s, (const unsigned long long *)fo.counters, nstripes, pitoff,
             dflags + 8);
   RD_HIP(hipMemcpyAsync(hw, dflags + 4, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -3100,20 +3013,13 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
     g_stats.host_syncs++;
     nroots0 = hw[0];
   }
-  const char *env_pp = getenv("RDGPU_FILL_PAIRS");   // =0: k_scan<L16>, one block per tile (A/B and tests)
-  const bool persistent_pairs = !(env_pp && env_pp[0] == '0');
   const uint32_t nwork1 = listed ? lists->n[1] : ntiles;   // scan tiles the pair pass visits
-  uint32_t pgrid = 0;
-  if (persistent_pairs) {
-    static thread_local int pb_cache[2] = {0, 0};   // (per element type and topology: this function is a template)
-    int &pb = pb_cache[vec ? 1 : 0];
-    if (!pb || getenv("RDGPU_FILL_PAIRS_BPC")) pb = vec ? pairs_blocks(k_pairs16<T, TOPO, true>) : pairs_blocks(k_pairs16<T, TOPO, false>);
-    pgrid = std::max(8u, std::min<uint32_t>(xcd_grid(std::max(nwork1, 1u)), (uint32_t)pb));
-  }
-  // the pair list of the one raster pass: capacity as in the classic path; the persistent pass has one segment per block
-  uint32_t nseg = 1;
-  while (nseg < ESEG && (uint64_t)nseg * 128 <= ntiles) nseg *= 2;
-  if (persistent_pairs) nseg = pgrid;
+  static thread_local int pb_cache[2] = {0, 0};   // (per element type and topology: this function is a template)
+  int &pb = pb_cache[vec ? 1 : 0];
+  if (!pb) pb = vec ? pairs_blocks(k_pairs16<T, TOPO, true>) : pairs_blocks(k_pairs16<T, TOPO, false>);
+  const uint32_t pgrid = std::max(8u, std::min<uint32_t>(xcd_grid(std::max(nwork1, 1u)), (uint32_t)pb));
+  // the pair list of the one raster pass: capacity as in the classic path, one segment per block of the pair pass
+  const uint32_t nseg = pgrid;
   const char *env_cap = getenv("RDGPU_FILL_EDGE_CAP");
   const uint64_t cap = env_cap ? strtoull(env_cap, nullptr, 10) : std::min<uint64_t>(12ull * B, n / 2) + 2048;
   const uint32_t segcap = cdiv(cdiv(cap, nseg), NTHR * EPT) * (NTHR * EPT);
@@ -3124,26 +3030,13 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   RD_HIP(hipMemsetAsync(segcount, 0, nseg * sizeof(uint32_t), s));
   EdgeOut eo{elist[0], elist[0] + ecap, elist[0] + 2 * ecap, segcount, segcap, nseg - 1, dflags + 5};
   eo.seglimit = env_cap ? (uint32_t)std::min<uint64_t>(segcap, std::max<uint64_t>(1, cdiv(cap, nseg))) : segcap;   // (the cap given on purpose is enforced to the record: the overflow tests)
-  uint8_t *alive = ws.buf<uint8_t>("fill.alive", ntiles);
   int ein = 0;
   bool eseg = true;
-  const char *env_dedup = getenv("RDGPU_FILL_DEDUP");
-  const bool dedup = !(env_dedup && env_dedup[0] == '0');
-  const char *env_pc = getenv("RDGPU_FILL_PRECHECK");
-  const char *env_st = getenv("RDGPU_FILL_PAIRS_STRIDED");
-  // RDGPU_FILL_PAIRS_ABLATE (timing probes only, compiled in with -DRDGPU_PROBES -- the fill's RESULT IS WRONG with any bit set): 4 = no pair loop (phase 2),
-  // 8 = no proposals and no records (phase 3), 16 = no boundary list (phase 1), 32 = the pair loop without its table trips,
-  // 64 = the pair loop's gathers alone: what each part costs, tools/probes/pairs_ablate.sh.  r05 at S3 (profiles/r05e_*):
-  // staging + detection 2.5 ms, list 0.4, gathers 0.45, sorting the neighbours 1.0, table 1.8, proposals + records 0.5 = 6.1.
+  // What the parts of the pair pass cost, r05 at S3 (profiles/r05e_*, measured by switching its phases off): staging +
+  // detection 2.5 ms, list 0.4, gathers 0.45, sorting the neighbours 1.0, table 1.8, proposals + records 0.5 = 6.1.
   // Built on that and measured SLOWER or equal, not kept: the pair pass on local component ids with a direct triangular pair
   // table (9.5 ms: its LDS atomics and the id lookups cost more than the hash they replace), one table trip per cell with
   // the cells of a second component on a wavefront's own list (6.1-6.2), a two-slot fast path (6.2).
-#ifdef RDGPU_PROBES   // (a stray environment variable must not be able to corrupt a production fill)
-  const char *env_ab = getenv("RDGPU_FILL_PAIRS_ABLATE");
-#else
-  const char *env_ab = nullptr;
-#endif
-  const int precheck = (!(env_pc && env_pc[0] == '0') ? 1 : 0) | (!(env_st && env_st[0] == '0') ? 2 : 0) | (env_ab ? (atoi(env_ab) & 124) : 0);
   // r06: the rounds are enqueued WITHOUT a host read-back between them.  Every round kernel takes its counts from the device
   // (rc[4 r] = live roots entering round r, rc[4 r + 1] = records of the list it contracts) and runs a grid-stride loop over
   // a grid the host sizes from upper bounds: live roots at least halve per round (every one hooks into another component or
@@ -3170,25 +3063,12 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
     RD_LAUNCH("fill.best_reset", k_best_reset, dim3(rgrid), dim3(NTHR), 0, s, rootsA, 0u, best, nr);
     if (r == 1) {   // round 1: the one raster pass (components gathered from the node table)
       const uint32_t nwork = listed ? lists->n[1] : ntiles;
-      if (nwork == 0) {
-        // (no tile holds a wet cell although basins exist: cannot happen -- a pit is a wet cell; kept safe)
-      } else if (persistent_pairs) {
-        if (vec)
-          RD_LAUNCH("fill.scan", (k_pairs16<T, TOPO, true>), dim3(pgrid), dim3(NTHR), 0, s, (const T *)d_z, (const uint16_t *)fo.lab16,
+      if (nwork > 0)   // (none although basins exist cannot happen -- a pit is a wet cell; kept safe)
+        with_flag(vec, [&](auto V) {
+          RD_LAUNCH("fill.scan", (k_pairs16<T, TOPO, V>), dim3(pgrid), dim3(NTHR), 0, s, (const T *)d_z, (const uint16_t *)fo.lab16,
                     (const uint32_t *)curN, best, w, h, B, tilesX, sl_, nwork, eo, (const uint32_t *)fo.tile_base,
-                    (const uint32_t *)fo.tile_count, dtx, skip, precheck, (const uint32_t *)fo.edgeK, (const uint16_t *)fo.edgeS);
-        else
-          RD_LAUNCH("fill.scan", (k_pairs16<T, TOPO, false>), dim3(pgrid), dim3(NTHR), 0, s, (const T *)d_z, (const uint16_t *)fo.lab16,
-                    (const uint32_t *)curN, best, w, h, B, tilesX, sl_, nwork, eo, (const uint32_t *)fo.tile_base,
-                    (const uint32_t *)fo.tile_count, dtx, skip, precheck, (const uint32_t *)fo.edgeK, (const uint16_t *)fo.edgeS);
-      } else if (vec)
-        RD_LAUNCH("fill.scan", (k_scan<T, TOPO, false, true, true, true>), dim3(xcd_grid(nwork)), dim3(NTHR), 0, s, (const T *)d_z,
-                  reinterpret_cast<const uint32_t *>(fo.lab16), (const uint32_t *)curN, best, w, h, B, tilesX, ntiles,
-                  sl_, nwork, alive, eo, (const uint32_t *)fo.tile_base, dtx, skip);
-      else
-        RD_LAUNCH("fill.scan", (k_scan<T, TOPO, false, false, true, true>), dim3(xcd_grid(nwork)), dim3(NTHR), 0, s, (const T *)d_z,
-                  reinterpret_cast<const uint32_t *>(fo.lab16), (const uint32_t *)curN, best, w, h, B, tilesX, ntiles,
-                  sl_, nwork, alive, eo, (const uint32_t *)fo.tile_base, dtx, skip);
+                    (const uint32_t *)fo.tile_count, dtx, skip, (const uint32_t *)fo.edgeK, (const uint16_t *)fo.edgeS);
+        });
       RD_LAUNCH("fill.sum_segments", k_sum_segments, dim3(1), dim3(NTHR), 0, s, (const uint32_t *)eo.segcount, nseg, rc + 4 * 1 + 1);
       g_stats.scan_tiles += ntiles;
     } else {
@@ -3196,13 +3076,10 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
       const uint32_t *ia = elist[ein], *ib = elist[ein] + pcap[ein], *ik = elist[ein] + 2 * pcap[ein];
       uint32_t *oa = elist[eout], *ob = elist[eout] + pcap[eout], *ok = elist[eout] + 2 * pcap[eout];
       if (eseg)   // round 2 reads the segmented list of the raster pass: the segments' fill counts are on the device
-        RD_LAUNCH("fill.edge_round", (k_edge_round<true, false>), dim3(std::min<uint32_t>(4 * gcap, cdiv(ecap, NTHR * EPT))), dim3(NTHR), 0,
+        RD_LAUNCH("fill.edge_round", (k_edge_round<true>), dim3(std::min<uint32_t>(4 * gcap, cdiv(ecap, NTHR * EPT))), dim3(NTHR), 0,
                   s, ia, ib, ik, (uint32_t)ecap, (const uint32_t *)segcount, segcap, (const uint32_t *)cur, best, B, oa, ob, ok, ne_next);
-      else if (dedup)
-        RD_LAUNCH("fill.edge_round", (k_edge_round<false, true>), dim3(gcap), dim3(NTHR), 0, s, ia, ib, ik, 0u,
-                  (const uint32_t *)nullptr, 0u, (const uint32_t *)cur, best, B, oa, ob, ok, ne_next, ne);
       else
-        RD_LAUNCH("fill.edge_round", (k_edge_round<false, false>), dim3(gcap), dim3(NTHR), 0, s, ia, ib, ik, 0u,
+        RD_LAUNCH("fill.edge_round", (k_edge_round<false>), dim3(gcap), dim3(NTHR), 0, s, ia, ib, ik, 0u,
                   (const uint32_t *)nullptr, 0u, (const uint32_t *)cur, best, B, oa, ob, ok, ne_next, ne);
       eseg = false;
       ein = eout;
@@ -3223,7 +3100,7 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   {
     uint32_t lg = 0;
     while ((1ull << lg) < (unsigned long long)nroots0 + 1ull) lg++;
-    int batch = (precheck & 124) ? 1 : std::min(MAXR, std::max(4, (int)(2 * lg + 4) / 5 + 1));   // ~log5.7(roots) + 1: S3 enqueues 11, runs 9
+    int batch = std::min(MAXR, std::max(4, (int)(2 * lg + 4) / 5 + 1));   // ~log5.7(roots) + 1: S3 enqueues 11, runs 9
     const char *env_batch = getenv("RDGPU_FILL_ROUND_BATCH");
     if (env_batch) batch = std::min(MAXR, std::max(1, atoi(env_batch)));   // (tests: several batches)
     uint32_t last_live = 0xFFFFFFFFu;
@@ -3235,7 +3112,6 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
       g_stats.host_syncs++;
       if (getenv("RDGPU_FILL_DEBUG")) fprintf(stderr, "fill_fused: pair pass: %u records, overflow %u, %u tiles on the slow road; %d rounds enqueued\n", hrc[4 + 1], hw[5], hw[12], rdone);
       if (hw[0] != 0) { if (getenv("RDGPU_FILL_DEBUG")) fprintf(stderr, "fill_fused: hook chain unfinished\n"); return false; }
-      if (precheck & 124) break;   // RDGPU_FILL_PAIRS_ABLATE (timing probes): the pair pass ran, its output is not used
       if (hw[5] != 0) { if (getenv("RDGPU_FILL_DEBUG")) fprintf(stderr, "fill_fused: pair list overflow (B %u cap %llu nseg %u segcap %u nwork %u)\n", B, (unsigned long long)cap, nseg, segcap, nwork1); return false; }   // the pair list overflowed: the DEM is untouched, the classic path takes over
       rounds_run = 0;
       for (int r = 1; r <= rdone; r++) rounds_run += hrc[4 * r] != 0;
@@ -3263,14 +3139,11 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
     return true;
   }
   if (listed && lists->n[2] == 0) return true;
-  if (vec)
-    RD_LAUNCH("fill.finalize", (k_finalize16<T, true>), dim3(listed ? lists->n[2] : xcd_grid(dnt)), dim3(NTHR), 0, s, d_z,
+  with_flag(vec, [&](auto V) {
+    RD_LAUNCH("fill.finalize", (k_finalize16<T, V>), dim3(listed ? lists->n[2] : xcd_grid(dnt)), dim3(NTHR), 0, s, d_z,
               (const uint16_t *)fo.lab16, (const uint32_t *)lvl, (const uint32_t *)fo.tile_base, (const uint32_t *)fo.tile_count, w, h, dtx,
               dnt, skip, fl);
-  else
-    RD_LAUNCH("fill.finalize", (k_finalize16<T, false>), dim3(listed ? lists->n[2] : xcd_grid(dnt)), dim3(NTHR), 0, s, d_z,
-              (const uint16_t *)fo.lab16, (const uint32_t *)lvl, (const uint32_t *)fo.tile_base, (const uint32_t *)fo.tile_count, w, h, dtx,
-              dnt, skip, fl);
+  });
   return true;
 }
 
@@ -3293,7 +3166,7 @@ static void fill_outlets_device(T *d_z, const uint8_t *d_outlet, const uint8_t *
   if (!d_outlet) throw Error(RDGPU_ERR_ARG, "rdgpu_fill_outlets: null outlet mask");
   if (w <= 2 || h <= 2) return;   // every cell is a border cell
   if (fill_fused<T, 8>(d_z, w, h, s, d_outlet, d_skip, lists)) return;
-  FillBuffers fb;   // (the compact labels ran out of table space, or are switched off: the classic path)
+  FillBuffers fb;   // (the compact labels ran out of table space: the classic path)
   BufAlloc ws_alloc{false, nullptr};
   fill_local_phase<T, 8>(d_z, w, h, 0, 0, ws_alloc, fb, s, d_outlet);
   fill_finalize<T>(d_z, w, h, fb, s);

@@ -711,6 +711,65 @@ int rdgpu_flow_accumulation_f64(const float *props9, int width, int height, doub
 int rdgpu_flow_accumulation_dev_f64(const float *d_props9, int width, int height, double *d_accum, void *hip_stream);
 int rdgpu_flow_accumulation_rounds(uint32_t *rounds); /* work-list rounds of the last generic accumulation */
 
+/* ---- TerrainAttribute: slope, aspect, curvature, SPI, CTI ------------------------------------
+ * Replaces richdem::TA_slope_riserun / _percentage / _degrees / _radians, TA_aspect, TA_curvature,
+ * TA_planform_curvature, TA_profile_curvature and TA_SPI / TA_CTI (include/richdem/methods/terrain_attributes.hpp).
+ * One pass of a 3 x 3 stencil in double, the reference's operations in the reference's order: rise/run, percentage and
+ * the three curvatures are bit-equal to the reference's, the atan / atan2 / log attributes within 1 float32 ULP.
+ * A neighbour that is off the grid or == nodata (compared in T) takes the centre's value; every value is multiplied by
+ * zscale; cell_x / cell_y are the cell lengths |geotransform[1]| / |geotransform[5]| (their sign is ignored; zero or
+ * non-finite is an error); a NoData cell gives out_nodata.  A flat window has aspect 270, as in the reference.
+ *   rdgpu_terrain_attribute[_dev]_<T>    one attribute (an RDGPU_TA_* id) into one float plane
+ *   rdgpu_terrain_attributes[_dev]_<T>   every attribute of `mask` (bit k = id k) in ONE launch / one read of the DEM:
+ *                                        outs[k] is the plane of attribute k, for every bit k of mask (other entries of
+ *                                        the RDGPU_TA_COUNT-entry array are not read)
+ *   rdgpu_ta_spi[_dev] / rdgpu_ta_cti[_dev]   log((fa / (cell_x * cell_y)) * (slope + 0.001)), CTI with / for *; where
+ *                                        fa == fa_nodata or slope == slope_nodata the result is -1, the NoData the
+ *                                        reference sets on its output.
+ * An unknown id / mask, a non-positive size, a null pointer or a bad cell length returns RDGPU_ERR_ARG before any
+ * device work. */
+enum {
+  RDGPU_TA_SLOPE_RISERUN = 0,
+  RDGPU_TA_SLOPE_PERCENTAGE = 1,
+  RDGPU_TA_SLOPE_DEGREES = 2,
+  RDGPU_TA_SLOPE_RADIANS = 3,
+  RDGPU_TA_ASPECT = 4,
+  RDGPU_TA_CURVATURE = 5,
+  RDGPU_TA_PLANFORM_CURVATURE = 6,
+  RDGPU_TA_PROFILE_CURVATURE = 7,
+  RDGPU_TA_COUNT = 8
+};
+#define RDGPU_DECL_TERRAIN(SUF, T)                                                                                   \
+  int rdgpu_terrain_attribute_##SUF(const T *dem, T nodata, int width, int height, double cell_x, double cell_y,     \
+                                    float zscale, int attribute, float *out, float out_nodata);                      \
+  int rdgpu_terrain_attribute_dev_##SUF(const T *d_dem, T nodata, int width, int height, double cell_x,              \
+                                        double cell_y, float zscale, int attribute, float *d_out, float out_nodata,  \
+                                        void *hip_stream);                                                           \
+  int rdgpu_terrain_attributes_##SUF(const T *dem, T nodata, int width, int height, double cell_x, double cell_y,    \
+                                     float zscale, unsigned mask, float *const *outs, float out_nodata);             \
+  int rdgpu_terrain_attributes_dev_##SUF(const T *d_dem, T nodata, int width, int height, double cell_x,             \
+                                         double cell_y, float zscale, unsigned mask, float *const *d_outs,           \
+                                         float out_nodata, void *hip_stream);
+RDGPU_DECL_TERRAIN(u8, uint8_t)
+RDGPU_DECL_TERRAIN(i16, int16_t)
+RDGPU_DECL_TERRAIN(u16, uint16_t)
+RDGPU_DECL_TERRAIN(i32, int32_t)
+RDGPU_DECL_TERRAIN(u32, uint32_t)
+RDGPU_DECL_TERRAIN(f32, float)
+RDGPU_DECL_TERRAIN(f64, double)
+RDGPU_DECL_TERRAIN(i8, int8_t)
+RDGPU_DECL_TERRAIN(i64, int64_t)
+RDGPU_DECL_TERRAIN(u64, uint64_t)
+#undef RDGPU_DECL_TERRAIN
+int rdgpu_ta_spi(const double *fa, double fa_nodata, const float *slope, float slope_nodata, int width, int height,
+                 double cell_x, double cell_y, float *out);
+int rdgpu_ta_spi_dev(const double *d_fa, double fa_nodata, const float *d_slope, float slope_nodata, int width,
+                     int height, double cell_x, double cell_y, float *d_out, void *hip_stream);
+int rdgpu_ta_cti(const double *fa, double fa_nodata, const float *slope, float slope_nodata, int width, int height,
+                 double cell_x, double cell_y, float *out);
+int rdgpu_ta_cti_dev(const double *d_fa, double fa_nodata, const float *d_slope, float slope_nodata, int width,
+                     int height, double cell_x, double cell_y, float *d_out, void *hip_stream);
+
 /* ---- synthetic input (test/bench input generator) ----------- */
 int rdgpu_synth_dem_dev_f32(float *d_dem, int width, int height, int seed, int x0, int y0,
                             float tilt, void *hip_stream);

@@ -586,4 +586,93 @@ void dinf_flow_directions(const E &elevations, F &flowdirs) {
                 "dinf_flow_directions");
 }
 
+// ---- TerrainAttribute (methods/terrain_attributes.hpp) ------------------------------------------------------------------
+namespace detail {
+#define RDGPU_SHIM_TERRAIN(SUF, T)                                                                                   \
+  inline int c_terrain(const T *p, T nd, int w, int h, double cx, double cy, float zs, int a, float *o, float ond) { \
+    return rdgpu_terrain_attribute_##SUF(p, nd, w, h, cx, cy, zs, a, o, ond);                                        \
+  }
+RDGPU_SHIM_TERRAIN(u8, uint8_t) RDGPU_SHIM_TERRAIN(i8, int8_t) RDGPU_SHIM_TERRAIN(u16, uint16_t)
+RDGPU_SHIM_TERRAIN(i16, int16_t) RDGPU_SHIM_TERRAIN(u32, uint32_t) RDGPU_SHIM_TERRAIN(i32, int32_t)
+RDGPU_SHIM_TERRAIN(u64, uint64_t) RDGPU_SHIM_TERRAIN(i64, int64_t) RDGPU_SHIM_TERRAIN(f32, float)
+RDGPU_SHIM_TERRAIN(f64, double)
+#undef RDGPU_SHIM_TERRAIN
+template <class T>
+int c_terrain(const T *, T, int, int, double, double, float, int, float *, float) { unsupported("TerrainAttribute"); }
+
+// the cell lengths |geotransform[1]|, |geotransform[5]| (Array2D.hpp:1387-1399).  The reference asserts that there is a
+// geotransform and, under NDEBUG, reads past the empty vector: here that is an exception.
+template <class A>
+void cell_lengths(const A &a, const char *fn, double &cx, double &cy) {
+  if (a.geotransform.size() < 6)
+    throw std::runtime_error(std::string(fn) + ": the raster has no geotransform, so its cell lengths are unknown");
+  cx = a.geotransform[1] < 0 ? -a.geotransform[1] : a.geotransform[1];
+  cy = a.geotransform[5] < 0 ? -a.geotransform[5] : a.geotransform[5];
+}
+
+// TerrainProcessor (terrain_attributes.hpp:329-348): output.resize(elevations) takes the size, geotransform and projection
+// and KEEPS the output's own NoData value, which NoData cells of the input receive.
+template <class E, class F>
+void terrain(const E &elevations, F &output, float zscale, int attribute, const char *fn) {
+  using T = elem_t<E>;
+  static_assert(std::is_same<elem_t<F>, float>::value, "TerrainAttribute: the output must be Array2D<float>");
+  double cx, cy;
+  cell_lengths(elevations, fn, cx, cy);
+  output.resize(elevations);
+  if (elevations.width() == 0 || elevations.height() == 0) return;
+  check(c_terrain((const T *)elevations.data(), elevations.noData(), elevations.width(), elevations.height(), cx, cy,
+                  zscale, attribute, output.data(), output.noData()),
+        fn);
+}
+
+template <class A, class S, class R>
+void spi_cti(const A &flow_accumulation, const S &riserun_slope, R &result, bool cti) {
+  static_assert(std::is_same<elem_t<A>, double>::value && std::is_same<elem_t<S>, float>::value &&
+                    std::is_same<elem_t<R>, float>::value,
+                "TA_SPI / TA_CTI: Array2D<double> accumulation, Array2D<float> slope, Array2D<float> result");
+  if (flow_accumulation.width() != riserun_slope.width() || flow_accumulation.height() != riserun_slope.height())
+    throw std::runtime_error(cti ? "Couldn't calculate CTI! The input matricies were of unequal dimensions!"
+                                 : "Couldn't calculate SPI! The input matricies were of unequal dimensions!");
+  double cx, cy;
+  cell_lengths(flow_accumulation, cti ? "TA_CTI" : "TA_SPI", cx, cy);
+  result.resize(flow_accumulation);
+  result.setNoData(-1);
+  if (flow_accumulation.width() == 0 || flow_accumulation.height() == 0) return;
+  const int w = flow_accumulation.width(), h = flow_accumulation.height();
+  check(cti ? rdgpu_ta_cti((const double *)flow_accumulation.data(), flow_accumulation.noData(),
+                           (const float *)riserun_slope.data(), riserun_slope.noData(), w, h, cx, cy, result.data())
+            : rdgpu_ta_spi((const double *)flow_accumulation.data(), flow_accumulation.noData(),
+                           (const float *)riserun_slope.data(), riserun_slope.noData(), w, h, cx, cy, result.data()),
+        cti ? "TA_CTI" : "TA_SPI");
+}
+}  // namespace detail
+
+// richdem::TA_slope_riserun / _percentage / _degrees / _radians, TA_aspect, TA_curvature, TA_planform_curvature,
+// TA_profile_curvature (const Array2D<T>&, Array2D<float>&, float zscale = 1)   terrain_attributes.hpp:362-562
+#define RDGPU_SHIM_TA(NAME, ID)                                            \
+  template <class E, class F>                                              \
+  void NAME(const E &elevations, F &output, float zscale = 1.0f) {         \
+    detail::terrain(elevations, output, zscale, ID, #NAME);                \
+  }
+RDGPU_SHIM_TA(TA_slope_riserun, RDGPU_TA_SLOPE_RISERUN)
+RDGPU_SHIM_TA(TA_slope_percentage, RDGPU_TA_SLOPE_PERCENTAGE)
+RDGPU_SHIM_TA(TA_slope_degrees, RDGPU_TA_SLOPE_DEGREES)
+RDGPU_SHIM_TA(TA_slope_radians, RDGPU_TA_SLOPE_RADIANS)
+RDGPU_SHIM_TA(TA_aspect, RDGPU_TA_ASPECT)
+RDGPU_SHIM_TA(TA_curvature, RDGPU_TA_CURVATURE)
+RDGPU_SHIM_TA(TA_planform_curvature, RDGPU_TA_PLANFORM_CURVATURE)
+RDGPU_SHIM_TA(TA_profile_curvature, RDGPU_TA_PROFILE_CURVATURE)
+#undef RDGPU_SHIM_TA
+
+// richdem::TA_SPI / TA_CTI(const Array2D<T>&, const Array2D<U>&, Array2D<V>&)   terrain_attributes.hpp:30-112:
+// the result takes the accumulation's size and geotransform, NoData -1
+template <class A, class S, class R>
+void TA_SPI(const A &flow_accumulation, const S &riserun_slope, R &result) {
+  detail::spi_cti(flow_accumulation, riserun_slope, result, false);
+}
+template <class A, class S, class R>
+void TA_CTI(const A &flow_accumulation, const S &riserun_slope, R &result) {
+  detail::spi_cti(flow_accumulation, riserun_slope, result, true);
+}
+
 }  // namespace rdgpu

@@ -694,3 +694,182 @@ def epsilon_stats() -> dict:
     st = _EpsStats()
     check(lib().rdgpu_fill_epsilon_get_stats(ctypes.byref(st)), "rdgpu_fill_epsilon_get_stats")
     return {k: getattr(st, k) for k, _ in _EpsStats._fields_}
+
+
+# ---- TerrainAttribute: slope, aspect, curvature, SPI, CTI (reference methods/terrain_attributes.hpp) ---------------------
+#: the reference's attribute names (wrappers/pyrichdem/richdem/__init__.py TerrainAttribute), in RDGPU_TA_* id order
+TERRAIN_ATTRIBUTES = ("slope_riserun", "slope_percentage", "slope_degrees", "slope_radians", "aspect", "curvature",
+                      "planform_curvature", "profile_curvature")
+
+
+def _ta_id(attrib) -> int:
+    if attrib not in TERRAIN_ATTRIBUTES:
+        raise RdgpuError("Invalid TerrainAttributes attribute. Valid attributes are: " + ", ".join(TERRAIN_ATTRIBUTES))
+    return TERRAIN_ATTRIBUTES.index(attrib)
+
+
+def _ta_meta(dem, nodata, cell):
+    """an rdarray supplies no_data and, through its geotransform, the cell lengths |gt[1]|, |gt[5]|"""
+    if nodata is None:
+        nodata = getattr(dem, "no_data", None)
+    if nodata is None:
+        raise RdgpuError("terrain attributes: a no_data value is required (nodata=, or an rdarray input)")
+    if cell is None:
+        gt = getattr(dem, "geotransform", None)
+        cell = (abs(float(gt[1])), abs(float(gt[5]))) if gt is not None and len(gt) == 6 else (1.0, 1.0)
+    return nodata, (float(cell[0]), float(cell[1]))
+
+
+def _ta_scalar(s: str, nodata):
+    """_scalar, except that an integer no_data of an integer DEM is taken exactly (64-bit values above 2**53 do not survive
+    the trip through a double that _scalar makes)"""
+    if s not in ("f32", "f64") and isinstance(nodata, (int, np.integer)) and not isinstance(nodata, bool):
+        bits = 8 * np.dtype(_NP[s]).itemsize
+        v = int(nodata) & ((1 << bits) - 1)
+        if np.issubdtype(_NP[s], np.signedinteger) and v >= 1 << (bits - 1):
+            v -= 1 << bits
+        return _CT[s](v)
+    return _scalar(s, nodata)
+
+
+def _ta_ids(attribs):
+    ids = [_ta_id(a) for a in attribs]
+    if not ids or len(set(ids)) != len(ids):
+        raise RdgpuError("terrain_attributes: expected a non-empty list of distinct attribute names")
+    return ids
+
+
+def terrain_attributes(dem: np.ndarray, attribs, nodata=None, zscale: float = 1.0, cell=None, out_nodata=-9999) -> dict:
+    """{name: float32 array} of several terrain attributes from ONE launch, one read of the DEM (reference TA_* of
+    methods/terrain_attributes.hpp, each bit for bit what the single calls give)."""
+    ids = _ta_ids(list(attribs))
+    nodata, cell = _ta_meta(dem, nodata, cell)
+    dem, s = _elev(np.asarray(dem), "terrain_attribute")
+    h, w = dem.shape
+    outs = {k: np.empty((h, w), np.float32) for k in ids}
+    ptrs = (ctypes.c_void_p * len(TERRAIN_ATTRIBUTES))()
+    for k, a in outs.items():
+        ptrs[k] = a.ctypes.data
+    mask = sum(1 << k for k in ids)
+    check(getattr(lib(), f"rdgpu_terrain_attributes_{s}")(dem.ctypes.data_as(ctypes.c_void_p), _ta_scalar(s, nodata), w, h,
+                                                          ctypes.c_double(cell[0]), ctypes.c_double(cell[1]),
+                                                          ctypes.c_float(zscale), ctypes.c_uint(mask), ptrs,
+                                                          ctypes.c_float(out_nodata)), "rdgpu_terrain_attributes")
+    return {TERRAIN_ATTRIBUTES[k]: outs[k] for k in ids}
+
+
+def terrain_attribute(dem: np.ndarray, attrib: str, nodata=None, zscale: float = 1.0, cell=None, out_nodata=-9999) -> np.ndarray:
+    """float32 terrain attribute of ``dem`` (reference TerrainAttribute(dem, attrib, zscale)): ``attrib`` is one of
+    TERRAIN_ATTRIBUTES; ``cell`` = (cellX, cellY), (1, 1) unless an rdarray's geotransform says otherwise; NoData cells get
+    ``out_nodata`` (the reference's Python wrapper passes -9999)."""
+    k = _ta_id(attrib)
+    nodata, cell = _ta_meta(dem, nodata, cell)
+    dem, s = _elev(np.asarray(dem), "terrain_attribute")
+    h, w = dem.shape
+    out = np.empty((h, w), np.float32)
+    check(getattr(lib(), f"rdgpu_terrain_attribute_{s}")(dem.ctypes.data_as(ctypes.c_void_p), _ta_scalar(s, nodata), w, h,
+                                                         ctypes.c_double(cell[0]), ctypes.c_double(cell[1]),
+                                                         ctypes.c_float(zscale), k, out.ctypes.data_as(ctypes.c_void_p),
+                                                         ctypes.c_float(out_nodata)), "rdgpu_terrain_attribute")
+    return out
+
+
+def _spi_cti(which, accum, slope, accum_nodata, slope_nodata, cell):
+    if accum_nodata is None:
+        accum_nodata = getattr(accum, "no_data", None)
+    if slope_nodata is None:
+        slope_nodata = getattr(slope, "no_data", None)
+    if accum_nodata is None or slope_nodata is None:
+        raise RdgpuError(f"terrain_{which}: the no_data values of the accumulation and of the slope are required")
+    _, cell = _ta_meta(accum, accum_nodata, cell)
+    accum, slope = np.asarray(accum), np.asarray(slope)
+    if accum.ndim != 2 or slope.ndim != 2 or accum.shape != slope.shape:   # the reference's message
+        raise RdgpuError(f"Couldn't calculate {which.upper()}! The input matricies were of unequal dimensions!")
+    accum = np.ascontiguousarray(accum, np.float64)
+    slope = np.ascontiguousarray(slope, np.float32)
+    h, w = accum.shape
+    out = np.empty((h, w), np.float32)
+    check(getattr(lib(), f"rdgpu_ta_{which}")(accum.ctypes.data_as(ctypes.c_void_p), ctypes.c_double(accum_nodata),
+                                              slope.ctypes.data_as(ctypes.c_void_p), ctypes.c_float(slope_nodata), w, h,
+                                              ctypes.c_double(cell[0]), ctypes.c_double(cell[1]),
+                                              out.ctypes.data_as(ctypes.c_void_p)), f"rdgpu_ta_{which}")
+    return out
+
+
+def terrain_spi(accum, slope, accum_nodata=None, slope_nodata=None, cell=None) -> np.ndarray:
+    """log((accum / cellArea) * (slope + 0.001)) as float32 (reference TA_SPI); NoData in either input gives -1."""
+    return _spi_cti("spi", accum, slope, accum_nodata, slope_nodata, cell)
+
+
+def terrain_cti(accum, slope, accum_nodata=None, slope_nodata=None, cell=None) -> np.ndarray:
+    """log((accum / cellArea) / (slope + 0.001)) as float32 (reference TA_CTI); NoData in either input gives -1."""
+    return _spi_cti("cti", accum, slope, accum_nodata, slope_nodata, cell)
+
+
+def _torch_ta_suffix(t) -> str:
+    import torch
+
+    m = {getattr(torch, n): s for n, s in (("uint16", "u16"), ("uint32", "u32"), ("uint64", "u64")) if hasattr(torch, n)}
+    return m[t.dtype] if t.dtype in m else _torch_elev_suffix(t)
+
+
+def terrain_attributes_dev(dem, attribs, nodata, outs, zscale: float = 1.0, cell=(1.0, 1.0), out_nodata=-9999) -> None:
+    """outs[name] (float32 CUDA tensors of the DEM's shape) <- the attributes ``attribs`` of the CUDA tensor ``dem``, all
+    from one launch on torch's current stream."""
+    import torch
+
+    ids = _ta_ids(list(attribs))
+    h, w = _dev2d(dem, "terrain_attributes_dev")
+    ptrs = (ctypes.c_void_p * len(TERRAIN_ATTRIBUTES))()
+    for k in ids:
+        o = outs[TERRAIN_ATTRIBUTES[k]]
+        if _dev2d(o, "terrain_attributes_dev", torch.float32) != (h, w):
+            raise RdgpuError("terrain_attributes_dev: shape mismatch")
+        ptrs[k] = o.data_ptr()
+    s = _torch_ta_suffix(dem)
+    check(getattr(lib(), f"rdgpu_terrain_attributes_dev_{s}")(ctypes.c_void_p(dem.data_ptr()), _ta_scalar(s, nodata), w, h,
+                                                              ctypes.c_double(cell[0]), ctypes.c_double(cell[1]),
+                                                              ctypes.c_float(zscale), ctypes.c_uint(sum(1 << k for k in ids)),
+                                                              ptrs, ctypes.c_float(out_nodata), _stream_ptr()),
+          "rdgpu_terrain_attributes_dev")
+
+
+def terrain_attribute_dev(dem, attrib: str, nodata, out, zscale: float = 1.0, cell=(1.0, 1.0), out_nodata=-9999) -> None:
+    """out (float32 CUDA tensor) <- one terrain attribute of the CUDA tensor ``dem``, on torch's current stream."""
+    import torch
+
+    k = _ta_id(attrib)
+    h, w = _dev2d(dem, "terrain_attribute_dev")
+    if _dev2d(out, "terrain_attribute_dev", torch.float32) != (h, w):
+        raise RdgpuError("terrain_attribute_dev: shape mismatch")
+    s = _torch_ta_suffix(dem)
+    check(getattr(lib(), f"rdgpu_terrain_attribute_dev_{s}")(ctypes.c_void_p(dem.data_ptr()), _ta_scalar(s, nodata), w, h,
+                                                             ctypes.c_double(cell[0]), ctypes.c_double(cell[1]),
+                                                             ctypes.c_float(zscale), k, ctypes.c_void_p(out.data_ptr()),
+                                                             ctypes.c_float(out_nodata), _stream_ptr()),
+          "rdgpu_terrain_attribute_dev")
+
+
+def _spi_cti_dev(which, accum, slope, out, accum_nodata, slope_nodata, cell):
+    import torch
+
+    if accum.dim() != 2 or slope.dim() != 2 or tuple(accum.shape) != tuple(slope.shape):
+        raise RdgpuError(f"Couldn't calculate {which.upper()}! The input matricies were of unequal dimensions!")
+    h, w = _dev2d(accum, f"terrain_{which}_dev", torch.float64)
+    _dev2d(slope, f"terrain_{which}_dev", torch.float32)
+    if _dev2d(out, f"terrain_{which}_dev", torch.float32) != (h, w):
+        raise RdgpuError(f"terrain_{which}_dev: shape mismatch")
+    check(getattr(lib(), f"rdgpu_ta_{which}_dev")(ctypes.c_void_p(accum.data_ptr()), ctypes.c_double(accum_nodata),
+                                                  ctypes.c_void_p(slope.data_ptr()), ctypes.c_float(slope_nodata), w, h,
+                                                  ctypes.c_double(cell[0]), ctypes.c_double(cell[1]),
+                                                  ctypes.c_void_p(out.data_ptr()), _stream_ptr()), f"rdgpu_ta_{which}_dev")
+
+
+def terrain_spi_dev(accum, slope, out, accum_nodata=-1.0, slope_nodata=-9999.0, cell=(1.0, 1.0)) -> None:
+    """out (float32) <- TA_SPI of a float64 accumulation and a float32 rise/run slope, CUDA tensors, current stream."""
+    _spi_cti_dev("spi", accum, slope, out, accum_nodata, slope_nodata, cell)
+
+
+def terrain_cti_dev(accum, slope, out, accum_nodata=-1.0, slope_nodata=-9999.0, cell=(1.0, 1.0)) -> None:
+    """out (float32) <- TA_CTI of a float64 accumulation and a float32 rise/run slope, CUDA tensors, current stream."""
+    _spi_cti_dev("cti", accum, slope, out, accum_nodata, slope_nodata, cell)

@@ -770,6 +770,46 @@ int rdgpu_ta_cti(const double *fa, double fa_nodata, const float *slope, float s
 int rdgpu_ta_cti_dev(const double *d_fa, double fa_nodata, const float *d_slope, float slope_nodata, int width,
                      int height, double cell_x, double cell_y, float *d_out, void *hip_stream);
 
+/* ---- upslope cells, catchments and outlets on the D8 direction forest -------------------------
+ * Replaces richdem::d8_upslope_cells (include/richdem/methods/d8_methods.hpp:144-236) and answers the two questions
+ * next to it.  Directions are uint8 D8 codes (0 NO_FLOW, 1..8, dir_nodata).  "The path of cell c" is c, the cell c's
+ * direction points to, and so on; it ends at a cell without a direction 1..8 (NO_FLOW, NoData, any other code) or
+ * whose target is off the raster.  A path that runs into a direction loop never ends.  Exact; one read of the
+ * directions per tile pass, two tile passes, 8 bytes of scratch per 16 cells.
+ *   rdgpu_d8_catchments     every cell gets the label of the FIRST seed on its path, itself included; a cell whose path
+ *                           meets no seed (or never ends without meeting one) gets `unreached`.  seed_cells are flat
+ *                           indices y * width + x.  A seed labels itself whatever its own direction is (NoData, NO_FLOW,
+ *                           a cell of a loop).  Of two entries for one cell the first of the list wins.  A seed
+ *                           outside the raster returns RDGPU_ERR_ARG before anything is written.  n_seeds may be 0.
+ *   rdgpu_d8_outlets        every cell whose direction is not NoData gets the flat index of the last cell of its path
+ *                           that is not NoData: one id per drainage basin, and the id says where the basin drains.
+ *                           NoData cells and cells whose path never ends get 0xFFFFFFFF.
+ *   rdgpu_d8_upslope_cells  the reference's function: 2 on the cells of the line (x0,y0)-(x1,y1) as
+ *                           rdgpu_d8_upslope_line rasterises it, 1 on every cell whose path meets one, 255
+ *                           (FLOWDIR_NO_DATA) elsewhere.  x0 == x1 and y0 == y1: a pour point.
+ *   rdgpu_d8_upslope_line   host code only (no GPU needed): the cells the reference's "modified Bresenham" marks, in its
+ *                           order.  End points are swapped when x0 > x1; the error term and slope are float; per column
+ *                           the cell (x, y) is marked, and when the error reaches 0.5 also (x + 1, y) before y moves by
+ *                           one row -- a steep line stops short of (x1, y1); x0 == x1 with y0 != y1 marks (x0, y0) and
+ *                           (x0 + 1, y0) only.  Where that procedure would mark a cell outside the raster (undefined
+ *                           behaviour in the reference) RDGPU_ERR_ARG is returned and nothing is written.  *n receives
+ *                           the number of cells (at most 2 * width); with cells == NULL and capacity == 0 only the
+ *                           count is returned; a capacity below the count is RDGPU_ERR_ARG.
+ * The _dev forms take device pointers (the seed arrays too) and are ordered on hip_stream; rdgpu_d8_catchments_dev
+ * synchronises that stream once, to verify the seeds before it writes. */
+int rdgpu_d8_catchments(const uint8_t *dirs, uint8_t dir_nodata, int width, int height, const uint32_t *seed_cells,
+                        const int32_t *seed_labels, uint32_t n_seeds, int32_t unreached, int32_t *labels);
+int rdgpu_d8_catchments_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int width, int height, const uint32_t *d_seed_cells,
+                            const int32_t *d_seed_labels, uint32_t n_seeds, int32_t unreached, int32_t *d_labels,
+                            void *hip_stream);
+int rdgpu_d8_outlets(const uint8_t *dirs, uint8_t dir_nodata, int width, int height, uint32_t *outlet);
+int rdgpu_d8_outlets_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int width, int height, uint32_t *d_outlet, void *hip_stream);
+int rdgpu_d8_upslope_cells(const uint8_t *dirs, uint8_t dir_nodata, int width, int height, int x0, int y0, int x1, int y1,
+                           uint8_t *out);
+int rdgpu_d8_upslope_cells_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int width, int height, int x0, int y0, int x1, int y1,
+                               uint8_t *d_out, void *hip_stream);
+int rdgpu_d8_upslope_line(int width, int height, int x0, int y0, int x1, int y1, uint32_t *cells, uint32_t capacity, uint32_t *n);
+
 /* ---- synthetic input (test/bench input generator) ----------- */
 int rdgpu_synth_dem_dev_f32(float *d_dem, int width, int height, int seed, int x0, int y0,
                             float tilt, void *hip_stream);

@@ -404,6 +404,59 @@ void d8_flow_accum(const F &flowdirs, G &area) {
                 "d8_flow_accum");
 }
 
+// ---- upslope cells, catchments, outlets --------------------------------------------------------
+// richdem::d8_upslope_cells(int x0, int y0, int x1, int y1, const Array2D<T>& flowdirs, Array2D<U>& upslope_cells)
+// methods/d8_methods.hpp:144-236: 2 on the cells of the reference's line, 1 on every cell that drains through one,
+// FLOWDIR_NO_DATA (255, converted to U) elsewhere; the output is resized to the directions and NoData-tagged with it.
+// A line that would leave the raster (undefined behaviour in the reference) throws.
+template <class F, class G>
+void d8_upslope_cells(int x0, int y0, int x1, int y1, const F &flowdirs, G &upslope_cells) {
+  static_assert(std::is_same<detail::elem_t<const F>, uint8_t>::value || std::is_same<detail::elem_t<F>, uint8_t>::value,
+                "d8_upslope_cells: flow directions must be uint8_t (d8_flowdir_t)");
+  using U = detail::elem_t<G>;
+  upslope_cells.resize(flowdirs);
+  upslope_cells.setAll((U)255);          // FLOWDIR_NO_DATA, d8_methods.hpp:179
+  upslope_cells.setNoData((U)255);       // d8_methods.hpp:180
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  const size_t n = (size_t)flowdirs.width() * (size_t)flowdirs.height();
+  if constexpr (std::is_same<U, uint8_t>::value) {
+    detail::check(rdgpu_d8_upslope_cells(flowdirs.data(), flowdirs.noData(), flowdirs.width(), flowdirs.height(), x0, y0, x1, y1,
+                                         upslope_cells.data()), "d8_upslope_cells");
+  } else {
+    std::vector<uint8_t> tmp(n);
+    detail::check(rdgpu_d8_upslope_cells(flowdirs.data(), flowdirs.noData(), flowdirs.width(), flowdirs.height(), x0, y0, x1, y1,
+                                         tmp.data()), "d8_upslope_cells");
+    for (size_t i = 0; i < n; i++) upslope_cells.data()[i] = (U)tmp[i];
+  }
+}
+
+// every cell <- the label of the first seed on its flow path (cells: flat indices y * width + x), `unreached` without one
+template <class F, class G>
+void d8_catchments(const F &flowdirs, const std::vector<uint32_t> &cells, const std::vector<int32_t> &labels, G &out,
+                   int32_t unreached = 0) {
+  static_assert(std::is_same<detail::elem_t<const F>, uint8_t>::value || std::is_same<detail::elem_t<F>, uint8_t>::value,
+                "d8_catchments: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<detail::elem_t<G>, int32_t>::value, "d8_catchments: the label raster must be int32_t");
+  if (cells.size() != labels.size()) throw std::runtime_error("d8_catchments: one label per seed cell");
+  out.resize(flowdirs);
+  out.setNoData(unreached);
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  detail::check(rdgpu_d8_catchments(flowdirs.data(), flowdirs.noData(), flowdirs.width(), flowdirs.height(), cells.data(),
+                                    labels.data(), (uint32_t)cells.size(), unreached, out.data()), "d8_catchments");
+}
+
+// every cell <- the flat index of the cell it finally drains to; 0xFFFFFFFF (the output's NoData) on NoData cells and loops
+template <class F, class G>
+void d8_outlets(const F &flowdirs, G &out) {
+  static_assert(std::is_same<detail::elem_t<const F>, uint8_t>::value || std::is_same<detail::elem_t<F>, uint8_t>::value,
+                "d8_outlets: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<detail::elem_t<G>, uint32_t>::value, "d8_outlets: the outlet raster must be uint32_t");
+  out.resize(flowdirs);
+  out.setNoData(0xFFFFFFFFu);
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  detail::check(rdgpu_d8_outlets(flowdirs.data(), flowdirs.noData(), flowdirs.width(), flowdirs.height(), out.data()), "d8_outlets");
+}
+
 // richdem::FA_D8(const Array2D<elev_t>&, Array2D<accum_t>&)   methods/flow_accumulation.hpp:27
 // accum is in/out: pre-loaded with the flow each cell generates.
 template <class E, class G>

@@ -873,3 +873,124 @@ def terrain_spi_dev(accum, slope, out, accum_nodata=-1.0, slope_nodata=-9999.0, 
 def terrain_cti_dev(accum, slope, out, accum_nodata=-1.0, slope_nodata=-9999.0, cell=(1.0, 1.0)) -> None:
     """out (float32) <- TA_CTI of a float64 accumulation and a float32 rise/run slope, CUDA tensors, current stream."""
     _spi_cti_dev("cti", accum, slope, out, accum_nodata, slope_nodata, cell)
+
+
+# ---- upslope cells, catchments, outlets (csrc/upslope.hip) -----------------------------------
+def _dirs2d(dirs, who):
+    if not isinstance(dirs, np.ndarray) or dirs.ndim != 2 or dirs.dtype != np.uint8:
+        raise RdgpuError(f"{who}: expected a 2-D uint8 array of D8 directions")
+    return np.ascontiguousarray(dirs)
+
+
+def _seed_cells(seed_cells, w, h, who) -> np.ndarray:
+    """flat indices, or an (n, 2) array of (x, y); a cell outside the raster is an error"""
+    c = np.asarray(seed_cells)
+    if c.size == 0:
+        return np.zeros(0, np.uint32)
+    if c.dtype.kind not in "iu":
+        raise RdgpuError(f"{who}: seed cells must be integers")
+    c = c.astype(np.int64)
+    if c.ndim == 2 and c.shape[1] == 2:
+        if ((c[:, 0] < 0) | (c[:, 0] >= w) | (c[:, 1] < 0) | (c[:, 1] >= h)).any():
+            raise RdgpuError(f"{who}: a seed cell lies outside the raster")
+        c = c[:, 1] * w + c[:, 0]
+    elif c.ndim != 1:
+        raise RdgpuError(f"{who}: seed cells are flat indices or an (n, 2) array of (x, y)")
+    if ((c < 0) | (c >= w * h)).any():
+        raise RdgpuError(f"{who}: a seed cell lies outside the raster")
+    return np.ascontiguousarray(c, np.uint32)
+
+
+def d8_upslope_line(shape, x0: int, y0: int, x1: int, y1: int) -> np.ndarray:
+    """Flat indices of the cells the reference's d8_upslope_cells marks for the line (x0,y0)-(x1,y1) on a raster of
+    shape (height, width), in its order (rdgpu_d8_upslope_line: host code, no GPU).  Raises where the line would leave
+    the raster."""
+    h, w = int(shape[0]), int(shape[1])
+    n = ctypes.c_uint32(0)
+    fn = lib().rdgpu_d8_upslope_line
+    check(fn(w, h, int(x0), int(y0), int(x1), int(y1), None, ctypes.c_uint32(0), ctypes.byref(n)), "rdgpu_d8_upslope_line")
+    cells = np.empty(n.value, np.uint32)
+    check(fn(w, h, int(x0), int(y0), int(x1), int(y1), cells.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint32(n.value),
+             ctypes.byref(n)), "rdgpu_d8_upslope_line")
+    return cells
+
+
+def d8_upslope_cells(dirs: np.ndarray, x0: int, y0: int, x1: int, y1: int, nodata: int = 255) -> np.ndarray:
+    """uint8 raster: 2 on the line's cells, 1 on every cell that drains through one, 255 elsewhere (reference
+    d8_upslope_cells, methods/d8_methods.hpp:144-236)."""
+    dirs = _dirs2d(dirs, "d8_upslope_cells")
+    h, w = dirs.shape
+    out = np.empty((h, w), np.uint8)
+    check(lib().rdgpu_d8_upslope_cells(dirs.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint8(nodata), w, h, int(x0), int(y0),
+                                       int(x1), int(y1), out.ctypes.data_as(ctypes.c_void_p)), "rdgpu_d8_upslope_cells")
+    return out
+
+
+def d8_catchments(dirs: np.ndarray, seed_cells, seed_labels, unreached: int = 0, nodata: int = 255) -> np.ndarray:
+    """int32 raster: the label of the first seed on every cell's flow path, `unreached` where there is none.  seed_cells:
+    flat indices or an (n, 2) array of (x, y); of two entries for one cell the first wins."""
+    dirs = _dirs2d(dirs, "d8_catchments")
+    h, w = dirs.shape
+    cells = _seed_cells(seed_cells, w, h, "d8_catchments")
+    labels = np.ascontiguousarray(np.asarray(seed_labels).reshape(-1), np.int32)
+    if labels.size != cells.size:
+        raise RdgpuError("d8_catchments: one label per seed cell")
+    out = np.empty((h, w), np.int32)
+    check(lib().rdgpu_d8_catchments(dirs.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint8(nodata), w, h,
+                                    cells.ctypes.data_as(ctypes.c_void_p), labels.ctypes.data_as(ctypes.c_void_p),
+                                    ctypes.c_uint32(cells.size), ctypes.c_int32(unreached),
+                                    out.ctypes.data_as(ctypes.c_void_p)), "rdgpu_d8_catchments")
+    return out
+
+
+def d8_outlets(dirs: np.ndarray, nodata: int = 255) -> np.ndarray:
+    """uint32 raster: the flat index of the cell every cell finally drains to (one id per drainage basin); 0xFFFFFFFF on
+    NoData cells and on cells that drain into a direction loop."""
+    dirs = _dirs2d(dirs, "d8_outlets")
+    h, w = dirs.shape
+    out = np.empty((h, w), np.uint32)
+    check(lib().rdgpu_d8_outlets(dirs.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint8(nodata), w, h,
+                                 out.ctypes.data_as(ctypes.c_void_p)), "rdgpu_d8_outlets")
+    return out
+
+
+def d8_upslope_cells_dev(dirs, x0: int, y0: int, x1: int, y1: int, out, nodata: int = 255) -> None:
+    """out (uint8 CUDA tensor) <- d8_upslope_cells of dirs (uint8 CUDA tensor), on torch's current stream."""
+    import torch
+
+    h, w = _dev2d(dirs, "d8_upslope_cells_dev", torch.uint8)
+    if _dev2d(out, "d8_upslope_cells_dev", torch.uint8) != (h, w):
+        raise RdgpuError("d8_upslope_cells_dev: shape mismatch")
+    check(lib().rdgpu_d8_upslope_cells_dev(ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(nodata), w, h, int(x0), int(y0),
+                                           int(x1), int(y1), ctypes.c_void_p(out.data_ptr()), _stream_ptr()),
+          "rdgpu_d8_upslope_cells_dev")
+
+
+def d8_catchments_dev(dirs, seed_cells, seed_labels, out, unreached: int = 0, nodata: int = 255) -> None:
+    """out (int32 CUDA tensor) <- catchments; seed_cells (int32 CUDA tensor of flat indices, read as unsigned) and
+    seed_labels (int32 CUDA tensor) stay on the device."""
+    import torch
+
+    h, w = _dev2d(dirs, "d8_catchments_dev", torch.uint8)
+    if _dev2d(out, "d8_catchments_dev", torch.int32) != (h, w):
+        raise RdgpuError("d8_catchments_dev: shape mismatch")
+    for t in (seed_cells, seed_labels):
+        if not (t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.dtype == torch.int32):
+            raise RdgpuError("d8_catchments_dev: seeds are contiguous 1-D int32 tensors on the GPU")
+    if seed_cells.numel() != seed_labels.numel():
+        raise RdgpuError("d8_catchments_dev: one label per seed cell")
+    check(lib().rdgpu_d8_catchments_dev(ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(nodata), w, h,
+                                        ctypes.c_void_p(seed_cells.data_ptr()), ctypes.c_void_p(seed_labels.data_ptr()),
+                                        ctypes.c_uint32(seed_cells.numel()), ctypes.c_int32(unreached),
+                                        ctypes.c_void_p(out.data_ptr()), _stream_ptr()), "rdgpu_d8_catchments_dev")
+
+
+def d8_outlets_dev(dirs, out, nodata: int = 255) -> None:
+    """out (int32 CUDA tensor, holding the uint32 flat indices bit for bit: -1 is "none") <- outlets of dirs."""
+    import torch
+
+    h, w = _dev2d(dirs, "d8_outlets_dev", torch.uint8)
+    if _dev2d(out, "d8_outlets_dev", torch.int32) != (h, w):
+        raise RdgpuError("d8_outlets_dev: shape mismatch")
+    check(lib().rdgpu_d8_outlets_dev(ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(nodata), w, h,
+                                     ctypes.c_void_p(out.data_ptr()), _stream_ptr()), "rdgpu_d8_outlets_dev")

@@ -15,6 +15,7 @@
 //      one atomicAdd(word, area - (1<<56)) per step; integer, exact, order independent.
 //  f64 weights (FA_D8): f64 atomicAdd on the total + release/acquire decrement of a separate counter.
 #include "common.hpp"
+#include "tile_front.hpp"
 
 #include <string>
 #include <type_traits>
@@ -26,7 +27,6 @@
 
 namespace rdgpu {
 
-constexpr int NTHR = 256;
 constexpr unsigned long long CNT1 = 1ull << 56;
 constexpr unsigned long long LOWMASK = CNT1 - 1ull;
 constexpr unsigned long long SRC = 0xFFull;        // count-field marker of a source cell (unit path)
@@ -38,10 +38,6 @@ constexpr unsigned long long AREAMASK = (1ull << DIRSHIFT) - 1ull;
 // source, 0xF0 a NoData cell (at most 8 arrivals ever decrement it: it never reads as 1 or as a source)
 constexpr uint32_t SRC32 = 0xFEu;
 constexpr uint32_t NODATA32 = 0xF0u;
-
-// D8 neighbour offsets, numbering 234/105/876 (reference common/constants.hpp:44-45)
-__device__ __forceinline__ int d8dx(int n) { return (n == 1 || n == 2 || n == 8) ? -1 : (n >= 4 && n <= 6) ? 1 : 0; }
-__device__ __forceinline__ int d8dy(int n) { return (n >= 2 && n <= 4) ? -1 : (n >= 6 && n <= 8) ? 1 : 0; }
 
 // target cell of c under direction n, or -1 when there is none / it is off the grid
 __device__ __forceinline__ int64_t flow_target(uint32_t c, int n, int w, int h) {
@@ -260,7 +256,7 @@ __global__ __launch_bounds__(NTHR) void k_acc_out_unit(const uint8_t *__restrict
 // Direction loops keep the reference's semantics (d8_methods.hpp:104-131: a cell that never becomes free of
 // dependencies never passes anything on and keeps the inflow that did arrive, without its own 1): an exit that is not
 // complete inside its tile is blocked for good, and a border cell with an unfinished outside donor stays pending.
-constexpr int LT = 64, LLW = LT + 2;
+constexpr int LLW = LT + 2;
 constexpr uint32_t NO_NODE = 0xFFFFFFFFu;
 // The words of the link forest's nodes (exits): pending in-links in bits 40..63, total in bits 0..39.  The per-cell words
 // of the raster-wide walk keep their count in 8 bits (a cell has at most 8 donors), but an EXIT can be handed flow by
@@ -272,61 +268,7 @@ constexpr unsigned long long LK_CNT1 = 1ull << LK_SHIFT, LK_LOW = LK_CNT1 - 1ull
 constexpr unsigned long long LK_SRC = 0xFFFFFFull;      // count-field marker: an exit nobody hands anything to
 constexpr unsigned long long NOT_A_NODE = 0xFFFFFEull;  // count field of a slot that is not an exit
 
-__device__ __forceinline__ int border_slot(int lx, int ly) {
-  if (ly == 0) return lx;
-  if (ly == LT - 1) return LT + lx;
-  if (lx == 0) return 2 * LT + (ly - 1);
-  if (lx == LT - 1) return 2 * LT + (LT - 2) + (ly - 1);
-  return -1;
-}
-
-// The pointer tables of the tile passes are gathered at random by all 64 lanes; with rows of 64 two-byte entries every row
-// starts on the same LDS bank, so lanes that point at neighbouring columns of DIFFERENT rows -- the usual case: flow
-// converges -- collide.  Rows of LPS = 66 entries shift the banks by one per row (r03e: SQ_LDS_BANK_CONFLICT was 57 % of
-// k_acc_link_tile's LDS cycles, 44 % of k_acc_link_final_sums').  A cell's table index is ly * LPS + lx.
-constexpr int LPS = LT + 2;
-// ---- the tile passes' common front end (r04d) ---------------------------------------------------------------------
-// The staged directions: rows of SDW = 72 bytes with the tile's first column at byte SDO = 4, so that an interior tile is
-// staged with aligned 32-bit LDS stores from 32-bit global loads (one byte per load and a division per byte made the
-// staging a fifth of k_acc_link_tile's instructions).  Cells outside the raster read as `fill`.
-constexpr int SDW = 72, SDO = 4, SDH = LT + 2;
-__device__ __forceinline__ void stage_dirs_rows(const uint8_t *__restrict__ dirs, int w, int h, int x0, int y0, uint8_t fill,
-                                                uint8_t *sd) {
-  if (y0 >= 1 && y0 + LT < h && x0 + LT <= w) {   // (block-uniform) every row of the window lies in the raster
-    constexpr int NQ = SDH * (LT / 4), QPT = (NQ + NTHR - 1) / NTHR;
-    uint32_t v[QPT];
-#pragma unroll
-    for (int r = 0; r < QPT; r++) {
-      const int i = (int)threadIdx.x + r * NTHR;
-      if (i < NQ) __builtin_memcpy(&v[r], dirs + (size_t)(y0 - 1 + (i >> 4)) * w + (x0 + 4 * (i & 15)), 4);   // (any alignment)
-    }
-#pragma unroll
-    for (int r = 0; r < QPT; r++) {
-      const int i = (int)threadIdx.x + r * NTHR;
-      if (i < NQ) *reinterpret_cast<uint32_t *>(sd + (i >> 4) * SDW + SDO + 4 * (i & 15)) = v[r];
-    }
-    if (threadIdx.x < 2 * SDH) {   // the two ring columns
-      const int ly = (int)threadIdx.x >> 1, side = (int)threadIdx.x & 1;
-      const int gx = side ? x0 + LT : x0 - 1;
-      sd[ly * SDW + (side ? SDO + LT : SDO - 1)] = (gx >= 0 && gx < w) ? dirs[(size_t)(y0 - 1 + ly) * w + gx] : fill;
-    }
-  } else {
-    for (int i = (int)threadIdx.x; i < SDH * SDH; i += NTHR) {
-      const int ly = i / SDH, lx = i - ly * SDH;
-      const int gx = x0 - 1 + lx, gy = y0 - 1 + ly;
-      sd[ly * SDW + SDO - 1 + lx] = (gx >= 0 && gx < w && gy >= 0 && gy < h) ? dirs[(size_t)gy * w + gx] : fill;
-    }
-  }
-}
-// Per direction 1..8 (index e = d - 1), one byte each, looked up with v_perm_b32 (selector bytes 0..3 pick from the second
-// operand, 4..7 from the first, 0x0c gives 0): the target's offset in the staged rows (+73), in the pointer table (+67), and
-// which side of the tile it can leave through (1: left, 2: right, 4: top, 8: bottom).
-__device__ __forceinline__ uint32_t d8_byte(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
-constexpr uint32_t D8_SD_LO = 0x02010048u, D8_SD_HI = 0x9091924Au;   // (dy * SDW + dx) + SDW + 1
-constexpr uint32_t D8_LP_LO = 0x02010042u, D8_LP_HI = 0x84858644u;   // (dy * LPS + dx) + LPS + 1
-constexpr uint32_t D8_FL_LO = 0x06040501u, D8_FL_HI = 0x09080A02u;
-static_assert(SDW == 72 && LPS == 66, "the byte tables above");
-
+// (border_slot, LPS, stage_dirs_rows and the byte tables of the tile passes' front end: tile_front.hpp)
 __global__ __launch_bounds__(NTHR, 6) void k_acc_link_tile(const uint8_t *__restrict__ dirs, uint8_t nodata, int w, int h,
                                                         uint32_t tilesX, uint32_t ntiles, unsigned long long *nw,
                                                         uint32_t *next, uint8_t *rootslot) {

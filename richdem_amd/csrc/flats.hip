@@ -4,7 +4,7 @@
 // (reference include/richdem/flats/flat_resolution.hpp:587-605) =
 //   d8_flow_directions                       (flowmet/d8_flowdirs.hpp:96-123)       -> flowdirs.hip
 //   resolve_flats_barnes                     (flat_resolution.hpp:447-517)
-//      find_flat_edges :381-418              -> k_flat_classify   (3x3 stencil -> flag byte, compacted lists)
+//      find_flat_edges :381-418              -> k_flat_classify   (3x3 stencil -> flag byte)
 //      label_this :331-355                   -> k_ccl_*           (components of the equal-elevation 8-graph:
 //                                                in LDS per tile, lock-free union-find across tile borders;
 //                                                root = lowest cell index)
@@ -41,9 +41,9 @@ __device__ __forceinline__ int fdx(int n) { return (n == 1 || n == 2 || n == 8) 
 __device__ __forceinline__ int fdy(int n) { return (n >= 2 && n <= 4) ? -1 : (n >= 6 && n <= 8) ? 1 : 0; }
 
 // NOTE on atomics: same-address device atomics serialise at ~12 ns each on MI355X, so nothing in
-// this file funnels per-cell or per-wave work through one counter: lists are built with
-// count / scan / fill compaction, BFS appends use ONE atomic per block, flat heights are reduced in
-// reverse level order behind a pre-check.
+// this file funnels per-cell or per-wave work through one counter: counts are reduced per block
+// first, tile-list appends use ONE atomic per block, flat heights are reduced in reverse level order
+// behind a pre-check.
 
 constexpr uint8_t F_LOW = 1, F_HIGH = 2, F_NOFLOW = 4;
 constexpr uint8_t F_NEAR = 8;       // NO_FLOW cell next to an equal-elevation cell WITH a direction (a low edge): towards level 2
@@ -385,73 +385,6 @@ __global__ __launch_bounds__(NTHR) void k_dirs_classify(const T *__restrict__ z,
       for (int o = 32; o >= 1; o >>= 1) lo += __shfl_xor(lo, o, 64);
       if (lx == 0) atomicAdd(bm.counts + 3 * ((t * 4 + (threadIdx.x >> 6)) & 255u), lo);
     }
-  }
-}
-
-constexpr int CPB = 4096;   // cells per block
-__global__ __launch_bounds__(NTHR) void k_flag_count(const uint8_t *__restrict__ flags, uint8_t mask, uint64_t n,
-                                                     uint32_t *__restrict__ counts) {
-  __shared__ uint32_t ws[NTHR / 64];
-  const uint64_t base = (uint64_t)blockIdx.x * CPB;
-  uint32_t cnt = 0;
-#pragma unroll 4
-  for (int j = 0; j < CPB / NTHR; j++) {
-    const uint64_t c = base + (uint64_t)j * NTHR + threadIdx.x;
-    if (c < n && (flags[c] & mask)) cnt++;
-  }
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) counts[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-// single workgroup: exclusive scan of counts[0..m) in place; total -> *total
-__global__ __launch_bounds__(1024) void k_flag_scan(uint32_t *counts, uint32_t m, uint32_t *total) {
-  __shared__ uint32_t part[1024];
-  const uint32_t chunk = (m + 1023u) / 1024u;
-  const uint32_t lo = threadIdx.x * chunk, hi = min(lo + chunk, m);
-  uint32_t s = 0;
-  for (uint32_t i = lo; i < hi; i++) s += counts[i];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    uint32_t v = (threadIdx.x >= (uint32_t)o) ? part[threadIdx.x - o] : 0;
-    __syncthreads();
-    part[threadIdx.x] += v;
-    __syncthreads();
-  }
-  uint32_t run = threadIdx.x ? part[threadIdx.x - 1] : 0;
-  for (uint32_t i = lo; i < hi; i++) {
-    const uint32_t v = counts[i];
-    counts[i] = run;
-    run += v;
-  }
-  if (threadIdx.x == 1023) *total = part[1023];
-}
-
-__global__ __launch_bounds__(NTHR) void k_flag_fill(const uint8_t *__restrict__ flags, uint8_t mask, uint64_t n,
-                                                    const uint32_t *__restrict__ offsets, uint32_t *__restrict__ out) {
-  __shared__ uint32_t ws[NTHR / 64];
-  const uint64_t base = (uint64_t)blockIdx.x * CPB;
-  uint32_t run = offsets[blockIdx.x];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int j = 0; j < CPB / NTHR; j++) {
-    const uint64_t c = base + (uint64_t)j * NTHR + threadIdx.x;
-    const bool hit = c < n && (flags[c] & mask);
-    const unsigned long long bal = __ballot(hit);
-    const uint32_t rank = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) ws[wv] = __popcll(bal);
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < NTHR / 64; k++) {
-      const uint32_t v = ws[k];
-      if (k < wv) woff += v;
-      tot += v;
-    }
-    if (hit) out[run + woff + rank] = (uint32_t)c;
-    run += tot;
-    __syncthreads();
   }
 }
 
@@ -818,7 +751,7 @@ __global__ __launch_bounds__(NTHR) void k_ccl_flatten(uint32_t *L, uint64_t n) {
 }
 
 // fh[root] = -1: flat without a low edge (label 0 in the reference, :483-487); >= 0: labelled.
-// the same from the flag bytes (no edge list): every low edge marks its flat as having an outlet
+// every low edge marks its flat as having an outlet
 __global__ __launch_bounds__(NTHR) void k_flat_mark_low_flags(const uint8_t *__restrict__ flags, const uint32_t *__restrict__ L,
                                                               int32_t *fh, uint64_t n) {
   const uint64_t stride = (uint64_t)gridDim.x * NTHR;
@@ -826,29 +759,20 @@ __global__ __launch_bounds__(NTHR) void k_flat_mark_low_flags(const uint8_t *__r
     if (flags[c] & F_LOW) fh[L[c]] = 0;
 }
 
-__global__ __launch_bounds__(NTHR) void k_flat_mark_low(const uint32_t *__restrict__ low, uint32_t nlow,
-                                                        const uint32_t *__restrict__ L, int32_t *fh) {
-  const uint32_t i = blockIdx.x * NTHR + threadIdx.x;
-  if (i < nlow) fh[L[low[i]]] = 0;
-}
-
 // ------------------------------------------------------------------------------------------
 // BuildAwayGradient (:152-198) / BuildTowardsCombinedGradient (:241-298): the reference's levels are
 // BFS distances (8-connected, through NO_FLOW cells of the same flat) from the high / low edges.  A
 // level-synchronous BFS needs one global step per level -- 20 000+ steps on a 40k x 40k filled DEM whose
-// lakes are long and thin -- so distances are computed by tile-local relaxation instead: an active
-// 64x32 tile is staged in LDS (elevation, eligibility, distance, 1-cell halo), relaxed to its local fixed
-// point d(c) = min(d(c), min over equal-elevation neighbours d(n) + 1), written back, and the tiles
-// across a changed edge are activated for the next round.  Distances only ever decrease and stay upper
-// bounds, so the fixed point is the exact BFS level; the number of global rounds is the geodesic length in
-// TILES, not in cells.
+// lakes are long and thin -- so distances are computed tile by tile instead: an active tile is searched to its
+// local fixed point d(c) = min(d(c), min over equal-elevation neighbours d(n) + 1) from its seeds and the ring
+// of cells around it, written back, and the tiles across a changed edge are activated for the next round.
+// Distances only ever decrease and stay upper bounds, so the fixed point is the exact BFS level; the number of
+// global rounds is the geodesic length in TILES, not in cells.
+// (The first engine did this with a stencil relaxation over one int per cell in LDS; its record is in
+// docs/HISTORY.md and profiles/.)
 // ------------------------------------------------------------------------------------------
 constexpr int32_t DINF = 0x7F7F7F7F;   // memset-able "not reached"
-constexpr int RCH = 32;                // relaxation tiles are CW x RCH (the labelling tiles CW x CH)
-constexpr int HSTEPS = 8;              // stencil steps per barrier inside a relaxation tile (a step without a move ends them early)
-constexpr int RNT = 256, RBANDS = RNT / 64;   // one wavefront per band of RCH / RBANDS rows
-constexpr int RELAX_BATCH = 8;         // relaxation rounds enqueued per host read-back (stencil engine)
-constexpr int BITS_BATCH = 24;         // ... of the bitmap search: its rounds are short, the read-back's bubble is not
+constexpr int BITS_BATCH = 24;         // search rounds enqueued per host read-back: the rounds are short, the read-back's bubble is not
 
 __device__ __forceinline__ uint32_t block_append(bool pred, uint32_t *counter) {
   __shared__ uint32_t wcnt[NTHR / 64];
@@ -865,26 +789,6 @@ __device__ __forceinline__ uint32_t block_append(bool pred, uint32_t *counter) {
   uint32_t off = bbase;
   for (int k = 0; k < wv; k++) off += wcnt[k];
   return off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-}
-
-// sources get distance 1 and activate their tile.  fh != nullptr: only cells of labelled flats (:491-500)
-__global__ __launch_bounds__(NTHR) void k_flat_seed(const uint32_t *__restrict__ src, uint32_t nsrc,
-                                                    const uint32_t *__restrict__ L, const int32_t *__restrict__ fh,
-                                                    int32_t *D, uint8_t *tile_active, int w, uint32_t tilesX,
-                                                    uint32_t tilesY, const int32_t *__restrict__ reach) {
-  const uint32_t i = blockIdx.x * NTHR + threadIdx.x;
-  if (i >= nsrc) return;
-  const uint32_t c = src[i];
-  if (fh && fh[L[c]] < 0) return;   // its flat has no outlet: not a source
-  if (reach && reach[c] >= DINF) return;   // same test through the towards distances (row-block shards)
-  D[c] = 1;
-  // wake the source's tile and the tiles of its 8 neighbours (a source on a tile edge feeds the next tile)
-  const int x = (int)(c % (uint32_t)w), y = (int)(c / (uint32_t)w);
-  const int tx0 = max(x - 1, 0) / CW, tx1 = min(x + 1, w - 1) / CW;
-  const int ty0 = max(y - 1, 0) / RCH, ty1 = (y + 1) / RCH;
-  for (int ty = ty0; ty <= ty1; ty++)
-    for (int tx = tx0; tx <= tx1; tx++)
-      if ((uint32_t)ty < tilesY) tile_active[(uint32_t)ty * tilesX + (uint32_t)tx] = 1;
 }
 
 // active-tile flags -> list (flags are cleared for the next round)
@@ -906,197 +810,14 @@ __device__ __forceinline__ int32_t from_right(int32_t v, int32_t fill) {
 }
 __device__ __forceinline__ int32_t imin(int32_t a, int32_t b) { return a < b ? a : b; }
 
-// Start of the towards field, one 64 x RCH tile per block: low edges hold level 1 (they are not relaxed: they have a
-// direction), the NO_FLOW cells next to a low edge of their own flat level 2 (:262-275: the low edges are the first
-// BFS level), everything else "not reached".  Rows outside [row_lo, row_hi) -- a shard's ghost rows -- are not
-// seeded: their levels arrive from their owners.  A tile with a seed wakes itself and its 8 neighbours.
-__global__ __launch_bounds__(NTHR) void k_flat_init_towards(const uint8_t *__restrict__ flags, int32_t *__restrict__ D,
-                                                            uint8_t *tile_active, int w, int h, int row_lo, int row_hi,
-                                                            uint32_t tilesX, uint32_t tilesY) {
-  const uint32_t t = blockIdx.x;
-  const int tx = (int)(t % tilesX), ty = (int)(t / tilesX);
-  const int x0 = tx * CW, y0 = ty * RCH;
-  const int lx = threadIdx.x & (CW - 1), r0 = threadIdx.x >> 6;
-  int seed = 0;
-#pragma unroll
-  for (int j = 0; j < RCH / 4; j++) {
-    const int gx = x0 + lx, gy = y0 + r0 + 4 * j;
-    if (gx >= w || gy >= h) continue;
-    const size_t g = (size_t)gy * w + gx;
-    int32_t v = DINF;
-    if (gy >= row_lo && gy < row_hi) {
-      const uint8_t f = flags[g];
-      if (f & F_LOW) v = 1;
-      else if (f & F_NEAR) { v = 2; seed = 1; }
-    }
-    D[g] = v;
-  }
-  if (__syncthreads_or(seed) && threadIdx.x < 9) {
-    const int ntx = tx + (int)threadIdx.x % 3 - 1, nty = ty + (int)threadIdx.x / 3 - 1;
-    if (ntx >= 0 && nty >= 0 && ntx < (int)tilesX && nty < (int)tilesY) tile_active[nty * tilesX + ntx] = 1;
-  }
-}
-
-// One active tile to its local fixed point d(c) = min(d(c), min over the 8 neighbours d(n) + 1) over its NO_FLOW
-// cells.  Two adjacent NO_FLOW cells always have the same elevation (neither has a lower neighbour), so among the cells
-// that take part the flat graph is the plain 8-grid with the other cells as walls: no elevations are read here at all
-// (the low edges enter through the start values, k_flat_init_towards).  Per cell the kernel reads its level and its
-// direction byte.
-// A wavefront is one 64-column band of ROWS rows: a lane keeps its column strip in registers, sweeps it down and up
-// (Gauss-Seidel), takes the two side columns' vertical 3-minima from the neighbouring lanes with DPP wave shifts, and
-// only the bands' first/last rows go through LDS (double buffered: one barrier per iteration, shared with the "anything
-// changed" vote).  Levels only decrease and stay upper bounds, so the fixed point is the exact BFS level.
-// (Measured and dropped, r02, all correct: min-plus scans along the rows inside this kernel -- a front then crosses the
-// tile width in one trip -- with ds_bpermute shuffles or with DPP row shifts + v_readlane: 2.5-3x SLOWER at S3, because
-// with one stencil step per trip the diagonal fronts of open lakes take 32 trips instead of 8; and one wavefront per
-// tile running chamfer sweeps over rows kept in LDS, no barriers at all: 1.4x slower, 89 + 46 ms against 60 + 33 ms; a
-// block that follows the front -- goes on with the tile across a changed edge, up to four tiles per launch, minimum
-// writes -- saved 7 % of the rounds and doubled the relaxations of the full rounds: 76 + 48 ms against 54 + 26 ms.)
-constexpr int32_t DWALL = DINF + 1;   // LDS only: a cell that does not take part
-__device__ __forceinline__ void relax_tile(const uint8_t *__restrict__ dirs, int32_t *D, const uint32_t t,
-                                           uint8_t *next_active, int w, int h, uint32_t tilesX, uint32_t tilesY, int row_lo,
-                                           int row_hi) {
-  constexpr int RW = CW + 2, RH = RCH + 2, ROWS = RCH / RBANDS;
-  __shared__ int32_t sd[RH * RW];
-  __shared__ int32_t xrow[2][RBANDS][2][CW];
-  const int tx = (int)(t % tilesX), ty = (int)(t / tilesX);
-  const int x0 = tx * CW, y0 = ty * RCH;
-  {
-    // all loads of the thread are issued before the first one is consumed (clamped addresses, branch-free)
-    constexpr int IPT = (RH * RW + RNT - 1) / RNT;
-    int32_t dv[IPT];
-    uint8_t ev[IPT];
-#pragma unroll
-    for (int r = 0; r < IPT; r++) {
-      const int i = min((int)threadIdx.x + r * RNT, RH * RW - 1);
-      const int ly = i / RW, lxx = i - ly * RW;
-      const int gx = min(max(x0 - 1 + lxx, 0), w - 1), gy = min(max(y0 - 1 + ly, 0), h - 1);
-      const size_t g = (size_t)gy * w + gx;
-      dv[r] = __hip_atomic_load(&D[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // neighbours' tiles write it
-      ev[r] = dirs[g];
-    }
-#pragma unroll
-    for (int r = 0; r < IPT; r++) {
-      const int i = (int)threadIdx.x + r * RNT;
-      if (i >= RH * RW) continue;
-      const int ly = i / RW, lxx = i - ly * RW;
-      const int gx = x0 - 1 + lxx, gy = y0 - 1 + ly;
-      const bool in = gx >= 0 && gx < w && gy >= 0 && gy < h;
-      sd[i] = (in && (ev[r] == 0 || ev[r] == DIR_GHOST_NOFLOW)) ? dv[r] : DWALL;   // only NO_FLOW cells take part (:190-191)
-    }
-  }
-  __syncthreads();
-  const int lx = threadIdx.x & (CW - 1), band = threadIdx.x >> 6;
-  int32_t d[ROWS], d0[ROWS];
-  uint32_t elig = 0;   // bit j: the cell is relaxed here (NO_FLOW, inside the raster, in the own rows)
-#pragma unroll
-  for (int j = 0; j < ROWS; j++) {
-    const int ly = band * ROWS + j, gy = y0 + ly;
-    d[j] = sd[(ly + 1) * RW + lx + 1];
-    if (d[j] <= DINF && gy >= row_lo && gy < row_hi) elig |= 1u << j;
-    d0[j] = d[j];
-  }
-  if (!__syncthreads_or(elig != 0)) return;
-  auto ring = [&](int ly /* -1..RCH */, int cx /* -1..CW */) -> int32_t { return sd[(ly + 1) * RW + cx + 1]; };
-  int32_t sideL[ROWS], sideR[ROWS];   // vertical 3-minima of the halo columns (lanes 0 and 63 use them)
-#pragma unroll
-  for (int j = 0; j < ROWS; j++) {
-    const int ly = band * ROWS + j;
-    sideL[j] = lx == 0 ? imin(ring(ly - 1, -1), imin(ring(ly, -1), ring(ly + 1, -1))) : DWALL;
-    sideR[j] = lx == CW - 1 ? imin(ring(ly - 1, CW), imin(ring(ly, CW), ring(ly + 1, CW))) : DWALL;
-  }
-  const int32_t halo_up = band == 0 ? ring(-1, lx) : DWALL, halo_dn = band == RBANDS - 1 ? ring(RCH, lx) : DWALL;
-  int changed = 1, it = 0;
-  for (; it < 256; it++) {
-    // Gauss-Seidel along the strip
-#pragma unroll
-    for (int j = 1; j < ROWS; j++)
-      if (elig & (1u << j)) d[j] = imin(d[j], d[j - 1] + 1);
-#pragma unroll
-    for (int j = ROWS - 2; j >= 0; j--)
-      if (elig & (1u << j)) d[j] = imin(d[j], d[j + 1] + 1);
-    xrow[it & 1][band][0][lx] = d[0];
-    xrow[it & 1][band][1][lx] = d[ROWS - 1];
-    if (!__syncthreads_or(changed)) break;
-    const int32_t up = band == 0 ? halo_up : xrow[it & 1][band - 1][1][lx];
-    const int32_t dn = band == RBANDS - 1 ? halo_dn : xrow[it & 1][band + 1][0][lx];
-    // HSTEPS stencil steps per barrier: the sideways exchange is all DPP (registers), so a front crosses HSTEPS
-    // columns per trip; the rows above / below the band are one trip stale, which only delays, never breaks,
-    // convergence (levels are upper bounds and only decrease).  A step in which no lane of the wavefront moved ends
-    // the trip's steps (the next ones would compute the same values).  (Measured and dropped: skipping single rows
-    // whose neighbourhood did not move -- the per-row scalar branches cost the tail rounds more, 60 -> 72 ms, than
-    // they saved the full rounds, 33 -> 30 ms.)
-    changed = 0;
-#pragma unroll
-    for (int sub = 0; sub < HSTEPS; sub++) {
-      int32_t m[ROWS];
-      int moved = 0;
-#pragma unroll
-      for (int j = 0; j < ROWS; j++) m[j] = imin(j ? d[j - 1] : up, imin(d[j], j + 1 < ROWS ? d[j + 1] : dn));
-#pragma unroll
-      for (int j = 0; j < ROWS; j++) {
-        const int32_t side = imin(from_left(m[j], sideL[j]), from_right(m[j], sideR[j]));
-        const int32_t best = imin(m[j], side) + 1;
-        if ((elig & (1u << j)) && best < d[j]) { d[j] = best; moved = 1; }
-      }
-      changed |= moved;
-      if (!__any(moved)) break;
-    }
-  }
-  if (it == 256 && threadIdx.x == 0) next_active[t] = 1;   // iteration cap hit: finish this tile next round
-  // Write back, and wake a neighbouring tile only if a cell that moved here can still lower one of ITS cells: the ring
-  // staged at the start holds that tile's edge levels, and a ring cell at most one above the new level has nothing to
-  // gain (levels only decrease, so a stale ring value can only wake a tile needlessly, never miss one).  Waking on
-  // every changed edge made two tiles that merely agree on their common edge wake each other for another round.
-  __shared__ uint32_t wake;
-  if (threadIdx.x == 0) wake = 0;
-  __syncthreads();
-  uint32_t mine = 0;   // bit (dy + 1) * 3 + (dx + 1): the tile at (tx + dx, ty + dy)
-#pragma unroll
-  for (int j = 0; j < ROWS; j++) {
-    if (!(elig & (1u << j)) || d[j] >= d0[j]) continue;
-    const int ly = band * ROWS + j;
-    const int gx = x0 + lx, gy = y0 + ly;
-    __hip_atomic_store(&D[(size_t)gy * w + gx], d[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (ly != 0 && ly != RCH - 1 && lx != 0 && lx != CW - 1) continue;
-    for (int dy = -1; dy <= 1; dy++)
-      for (int dx = -1; dx <= 1; dx++) {
-        const int ny = ly + dy, nx = lx + dx;
-        const int sy = ny < 0 ? -1 : ny >= RCH ? 1 : 0, sx = nx < 0 ? -1 : nx >= CW ? 1 : 0;
-        if (!sy && !sx) continue;
-        const int32_t r = ring(ny, nx);
-        if (r <= DINF && r > d[j] + 1) mine |= 1u << ((sy + 1) * 3 + sx + 1);
-      }
-  }
-  if (mine) atomicOr(&wake, mine);
-  __syncthreads();
-  if (threadIdx.x < 9 && threadIdx.x != 4 && (wake >> threadIdx.x & 1u)) {
-    const int ntx = tx + (int)threadIdx.x % 3 - 1, nty = ty + (int)threadIdx.x / 3 - 1;
-    if (ntx >= 0 && nty >= 0 && ntx < (int)tilesX && nty < (int)tilesY) next_active[nty * tilesX + ntx] = 1;
-  }
-}
-
-// One block per listed tile.  The count lives on the device (rounds are enqueued in batches, the host sizes the
-// grid from the previous batch): blocks past the count leave at once, and tiles past the grid -- the list grew
-// faster than expected -- simply stay active for the next round (relaxation is monotone, order is irrelevant).
-__global__ __launch_bounds__(RNT) void k_flat_relax(const uint8_t *__restrict__ dirs, int32_t *D,
-                                                    const uint32_t *__restrict__ tiles, const uint32_t *__restrict__ count,
-                                                    uint8_t *next_active, int w, int h, uint32_t tilesX, uint32_t tilesY,
-                                                    int row_lo, int row_hi) {
-  const uint32_t n = *count;
-  for (uint32_t i = gridDim.x + blockIdx.x * RNT + threadIdx.x; i < n; i += gridDim.x * RNT) next_active[tiles[i]] = 1;
-  if (blockIdx.x >= n) return;
-  relax_tile(dirs, D, tiles[blockIdx.x], next_active, w, h, tilesX, tilesY, row_lo, row_hi);
-}
-
 // ------------------------------------------------------------------------------------------
-// The same fixed point by breadth-first search on BITMAPS, one wavefront per 64 x 64 tile (single device and row-block
-// shards alike: see RowWin; k_flat_relax above stays selectable with RDGPU_FLAT_BITS=0).
+// That fixed point by breadth-first search on BITMAPS, one wavefront per 64 x 64 tile (single device and row-block
+// shards alike: see RowWin).
 // Lane r holds row r of the tile as 64-bit masks: the cells that take part (M), those not yet reached (A), the current
 // front (F).  One BFS level is   N = dilate8(F) & A   =   two DPP row shifts, two bit shifts and a few ORs for the whole
-// tile -- against ~100 VALU instructions per wavefront and stencil step in k_flat_relax, which r02's traces showed to be
-// what bounds the stage (instruction issue in the full rounds, a lone wavefront's dependent chain in the ~500 tail
-// rounds).  Levels are recorded bit-sliced (plane j collects the cells whose level has bit j set) relative to a base,
+// tile -- against ~100 VALU instructions per wavefront and step of the stencil relaxation it replaced, which r02's
+// traces showed to be what bounded the stage (instruction issue in the full rounds, a lone wavefront's dependent chain
+// in the ~500 tail rounds).  Levels are recorded bit-sliced (plane j collects the cells whose level has bit j set) relative to a base,
 // and turned back into one int per cell when the tile is stored.
 // Sources of a visit: the tile's seeds (a bitmap, from the flags) and the ring of cells around the tile with the levels
 // they hold now -- each is injected at its own level, so the search also runs from several fronts at different depths,
@@ -1573,7 +1294,8 @@ __device__ __forceinline__ uint32_t relax_visit(const unsigned long long *__rest
   }
   unsigned long long tk4 = 0;
   if (STATS) tk4 = wall_clock64();
-  // Wake a neighbouring tile only if an edge cell that moved here can still lower one of ITS cells (see k_flat_relax).
+  // Wake a neighbouring tile only if an edge cell that moved here can still lower one of ITS cells (a ring cell at most
+  // one above the new level has nothing to gain; a stale ring value can only wake a tile needlessly, never miss one).
   // Edge cell (r, c) with new level v against the ring cells next to it, whose levels were read at the start.
   uint32_t wake = 0;   // bit (dy + 1) * 3 + dx + 1
   {
@@ -1692,6 +1414,7 @@ struct AsyncQ {
 
 __device__ __forceinline__ uint32_t aq_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
+constexpr int AQ_NAP = 1;   // k_relax_bits_async's `nap`: the sleep multiplier of wavefronts that find their queues empty
 constexpr uint32_t AQ_SPIN_CAP = 1u << 22;   // polls of one slot before the launch is given up (never reached unless the protocol is broken)
 __device__ __forceinline__ void aq_push(const AsyncQ &Q, uint32_t tile) {
   const uint32_t qi = tile % AQ_NQ;
@@ -2184,6 +1907,11 @@ __global__ __launch_bounds__(NTHR) void k_flat_labels_out(const uint32_t *__rest
 // driver
 // ------------------------------------------------------------------------------------------
 static thread_local rdgpu_flat_stats g_fstats;
+// environment switches (A/B runs and tests): NAME is set and starts with c
+static bool env_is(const char *name, char c) {
+  const char *e = getenv(name);
+  return e && e[0] == c;
+}
 static inline uint32_t sgrid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + NTHR - 1) / NTHR, 256u * 32u); }
 
 template <class T>
@@ -2205,7 +1933,8 @@ static void launch_ccl_border(const T *d_z, uint32_t *L, int w, int h, hipStream
             tilesX, ntiles);
 }
 
-// ---- the two edge lists (and the NO_FLOW count) in ONE count pass and ONE fill pass over the flag raster ----
+// ---- the edge counts (low edges, NO_FLOW cells, high edges) in ONE pass over the flag raster ----
+constexpr int CPB = 4096;   // cells per block
 __global__ __launch_bounds__(NTHR) void k_flag_count3(const uint8_t *__restrict__ flags, uint64_t n, uint32_t *__restrict__ cl,
                                                       uint32_t *__restrict__ cn, uint32_t *__restrict__ ch) {
   __shared__ uint32_t ws[3][NTHR / 64];
@@ -2227,35 +1956,7 @@ __global__ __launch_bounds__(NTHR) void k_flag_count3(const uint8_t *__restrict_
   }
 }
 
-__global__ __launch_bounds__(NTHR) void k_flag_fill2(const uint8_t *__restrict__ flags, uint64_t n,
-                                                     const uint32_t *__restrict__ offl, const uint32_t *__restrict__ offh,
-                                                     uint32_t *__restrict__ outl, uint32_t *__restrict__ outh) {
-  __shared__ uint32_t ws[2][NTHR / 64];
-  const uint64_t base = (uint64_t)blockIdx.x * CPB;
-  uint32_t runl = offl[blockIdx.x], runh = offh[blockIdx.x];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int j = 0; j < CPB / NTHR; j++) {
-    const uint64_t c = base + (uint64_t)j * NTHR + threadIdx.x;
-    const uint8_t f = c < n ? flags[c] : 0;
-    const bool hl = (f & F_LOW) != 0, hh = (f & F_HIGH) != 0;
-    const unsigned long long bl = __ballot(hl), bh = __ballot(hh);
-    if (lane == 0) { ws[0][wv] = __popcll(bl); ws[1][wv] = __popcll(bh); }
-    __syncthreads();
-    uint32_t wl = 0, tl = 0, wh = 0, th = 0;
-#pragma unroll
-    for (int k = 0; k < NTHR / 64; k++) {
-      if (k < wv) { wl += ws[0][k]; wh += ws[1][k]; }
-      tl += ws[0][k]; th += ws[1][k];
-    }
-    const unsigned long long below = (1ull << lane) - 1ull;
-    if (hl) outl[runl + wl + __popcll(bl & below)] = (uint32_t)c;
-    if (hh) outh[runh + wh + __popcll(bh & below)] = (uint32_t)c;
-    runl += tl; runh += th;
-    __syncthreads();
-  }
-}
-
-// totals of the three per-block count arrays (the counts-only case needs no offsets: one launch instead of three scans)
+// totals of the three per-block count arrays
 __global__ __launch_bounds__(NTHR) void k_flag_totals(const uint32_t *__restrict__ cl, const uint32_t *__restrict__ cn,
                                                       const uint32_t *__restrict__ ch, uint32_t nblk, uint32_t *tot) {
   uint32_t a = 0, b = 0, c = 0;
@@ -2264,128 +1965,23 @@ __global__ __launch_bounds__(NTHR) void k_flag_totals(const uint32_t *__restrict
   if ((threadIdx.x & 63) == 0) { atomicAdd(tot, a); atomicAdd(tot + 1, b); atomicAdd(tot + 2, c); }
 }
 
-static void compact_edges(const uint8_t *flags, uint64_t n, uint32_t **low, uint32_t *nlow, uint32_t **high, uint32_t *nhigh,
-                          uint32_t *nnoflow, hipStream_t s, bool lists = true) {
+// the mask path's edge counts, read back (the searches take their seeds from the flag bytes: no edge lists)
+static void count_edges(const uint8_t *flags, uint64_t n, uint32_t *nlow, uint32_t *nhigh, uint32_t *nnoflow, hipStream_t s) {
   Workspace &ws = Workspace::get();
   uint32_t *hw = ws.host_words();
   const uint32_t nblk = (uint32_t)((n + CPB - 1) / CPB);
-  uint32_t *counts = ws.buf<uint32_t>("flats.counts3", 3 * ((size_t)nblk + 1));
-  uint32_t *cl = counts, *cn = counts + (nblk + 1), *ch = counts + 2 * ((size_t)nblk + 1);
+  uint32_t *cl = ws.buf<uint32_t>("flats.counts3", 3 * (size_t)nblk), *cn = cl + nblk, *ch = cn + nblk;
   RD_LAUNCH("flats.flag_count", k_flag_count3, dim3(nblk), dim3(NTHR), 0, s, flags, n, cl, cn, ch);
-  if (!lists) {
-    uint32_t *tot = ws.buf<uint32_t>("flats.totals3", 4);
-    RD_HIP(hipMemsetAsync(tot, 0, 3 * sizeof(uint32_t), s));
-    RD_LAUNCH("flats.flag_totals", k_flag_totals, dim3(64), dim3(NTHR), 0, s, (const uint32_t *)cl, (const uint32_t *)cn,
-              (const uint32_t *)ch, nblk, tot);
-    RD_HIP(hipMemcpyAsync(hw, tot, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    RD_HIP(hipStreamSynchronize(s));
-    *nlow = hw[0]; *nnoflow = hw[1]; *nhigh = hw[2];
-    *low = *high = nullptr;
-    return;
-  }
-  RD_LAUNCH("flats.flag_scan", k_flag_scan, dim3(1), dim3(1024), 0, s, cl, nblk, cl + nblk);
-  RD_LAUNCH("flats.flag_scan", k_flag_scan, dim3(1), dim3(1024), 0, s, cn, nblk, cn + nblk);
-  RD_LAUNCH("flats.flag_scan", k_flag_scan, dim3(1), dim3(1024), 0, s, ch, nblk, ch + nblk);
-  RD_HIP(hipMemcpyAsync(hw, cl + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  RD_HIP(hipMemcpyAsync(hw + 1, cn + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  RD_HIP(hipMemcpyAsync(hw + 2, ch + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  uint32_t *tot = ws.buf<uint32_t>("flats.totals3", 4);
+  RD_HIP(hipMemsetAsync(tot, 0, 3 * sizeof(uint32_t), s));
+  RD_LAUNCH("flats.flag_totals", k_flag_totals, dim3(64), dim3(NTHR), 0, s, (const uint32_t *)cl, (const uint32_t *)cn,
+            (const uint32_t *)ch, nblk, tot);
+  RD_HIP(hipMemcpyAsync(hw, tot, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   RD_HIP(hipStreamSynchronize(s));
   *nlow = hw[0]; *nnoflow = hw[1]; *nhigh = hw[2];
-  *low = *high = nullptr;
-  if (*nlow == 0 || !lists) return;   // nothing will be resolved / the bitmap engine takes its seeds from the flags: counts only
-  *low = ws.buf<uint32_t>("flats.low", *nlow);
-  *high = ws.buf<uint32_t>("flats.highall", std::max<uint32_t>(*nhigh, 1u));
-  RD_LAUNCH("flats.flag_fill", k_flag_fill2, dim3(nblk), dim3(NTHR), 0, s, flags, n, (const uint32_t *)cl, (const uint32_t *)ch,
-            *low, *high);
 }
 
-// list of the cells with flags & mask, in index order; returns the count
-static uint32_t compact_flags(const uint8_t *flags, uint8_t mask, uint64_t n, const char *name, uint32_t **out,
-                              hipStream_t s) {
-  Workspace &ws = Workspace::get();
-  uint32_t *hw = ws.host_words();
-  const uint32_t nblk = (uint32_t)((n + CPB - 1) / CPB);
-  uint32_t *counts = ws.buf<uint32_t>("flats.counts", (size_t)nblk + 1);
-  RD_LAUNCH("flats.flag_count", k_flag_count, dim3(nblk), dim3(NTHR), 0, s, flags, mask, n, counts);
-  RD_LAUNCH("flats.flag_scan", k_flag_scan, dim3(1), dim3(1024), 0, s, counts, nblk, counts + nblk);
-  RD_HIP(hipMemcpyAsync(hw, counts + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  RD_HIP(hipStreamSynchronize(s));
-  const uint32_t total = hw[0];
-  *out = nullptr;
-  if (out && name && total) {
-    *out = ws.buf<uint32_t>(name, total);
-    RD_LAUNCH("flats.flag_fill", k_flag_fill, dim3(nblk), dim3(NTHR), 0, s, flags, mask, n, (const uint32_t *)counts, *out);
-  }
-  return total;
-}
-
-// Relaxation rounds until no tile is active.  Rounds are enqueued RELAX_BATCH at a time (compact the active
-// tile flags into a list + count on the device, relax that list); the host only reads the counts back once
-// per batch, and the rounds enqueued past the fixed point see an empty list.  Returns the rounds that had work.
-static uint32_t relax_rounds(const uint8_t *d_dirs, int32_t *D, uint8_t *tflags, uint32_t *tlist,
-                             uint32_t *ctr /* RELAX_BATCH words */, int w, int h, int row_lo, int row_hi, const char *name,
-                             hipStream_t s) {
-  uint32_t *hw = Workspace::get().host_words();
-  const uint32_t tilesX = (w + CW - 1) / CW, tilesY = (h + RCH - 1) / RCH, ntiles = tilesX * tilesY;
-  const bool trace = getenv("RDGPU_FLAT_TRACE") != nullptr;
-  uint32_t rounds = 0, grid = ntiles;   // any tile may be active in the first batch
-  for (;;) {
-    RD_HIP(hipMemsetAsync(ctr, 0, RELAX_BATCH * sizeof(uint32_t), s));
-    for (int b = 0; b < RELAX_BATCH; b++) {
-      RD_LAUNCH("flats.tiles_compact", k_tiles_compact, dim3((ntiles + NTHR - 1) / NTHR), dim3(NTHR), 0, s, tflags, ntiles,
-                tlist, ctr + b);
-      RD_LAUNCH(name, k_flat_relax, dim3(grid), dim3(RNT), 0, s, d_dirs, D, (const uint32_t *)tlist,
-                (const uint32_t *)(ctr + b), tflags, w, h, tilesX, tilesY, row_lo, row_hi);
-    }
-    RD_HIP(hipMemcpyAsync(hw, ctr, RELAX_BATCH * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    RD_HIP(hipStreamSynchronize(s));
-    uint32_t most = 0;
-    for (int b = 0; b < RELAX_BATCH; b++) {
-      if (trace) fprintf(stderr, "%s round %u nact %u (grid %u)\n", name, rounds, hw[b], grid);
-      if (hw[b] == 0) return rounds;
-      most = std::max(most, hw[b]);
-      rounds++;
-    }
-    grid = std::min<uint32_t>(ntiles, std::max<uint32_t>(1024u, 2u * most));
-    if (rounds > (1u << 26)) throw Error(RDGPU_ERR_HIP, "rdgpu flat resolution: relaxation did not terminate");
-  }
-}
-
-struct RelaxScratch {
-  uint8_t *tflags;
-  uint32_t *tlist, *ctr;
-  uint32_t tilesX, tilesY, ntiles;
-};
-static RelaxScratch relax_scratch(int w, int h) {
-  Workspace &ws = Workspace::get();
-  RelaxScratch r;
-  r.tilesX = (w + CW - 1) / CW; r.tilesY = (h + RCH - 1) / RCH; r.ntiles = r.tilesX * r.tilesY;
-  r.tflags = ws.buf<uint8_t>("flats.tflags", r.ntiles);
-  r.tlist = ws.buf<uint32_t>("flats.tlist", r.ntiles);
-  r.ctr = ws.buf<uint32_t>("flats.tctr", BITS_BATCH);
-  return r;
-}
-
-// Away levels from the high edges listed in src (level 1) by tile relaxation.  Returns the number of rounds.
-static uint32_t run_relax_away(const uint8_t *d_dirs, int32_t *D, const uint32_t *src, uint32_t nsrc, const uint32_t *L,
-                               const int32_t *fh_filter, int w, int h, hipStream_t s) {
-  const RelaxScratch r = relax_scratch(w, h);
-  RD_HIP(hipMemsetAsync(r.tflags, 0, r.ntiles, s));
-  RD_LAUNCH("flats.seed", k_flat_seed, dim3((nsrc + NTHR - 1) / NTHR), dim3(NTHR), 0, s, src, nsrc, L, fh_filter, D,
-            r.tflags, w, r.tilesX, r.tilesY, (const int32_t *)nullptr);
-  return relax_rounds(d_dirs, D, r.tflags, r.tlist, r.ctr, w, h, 0, h, "flats.relax_away", s);
-}
-
-// Towards levels from the low edges (flags: F_LOW level 1, F_NEAR level 2).  D is written in full.
-static uint32_t run_relax_towards(const uint8_t *d_dirs, const uint8_t *flags, int32_t *D, int w, int h, hipStream_t s) {
-  const RelaxScratch r = relax_scratch(w, h);
-  RD_HIP(hipMemsetAsync(r.tflags, 0, r.ntiles, s));
-  RD_LAUNCH("flats.init_towards", k_flat_init_towards, dim3(r.ntiles), dim3(NTHR), 0, s, flags, D, r.tflags, w, h, 0, h, r.tilesX,
-            r.tilesY);
-  return relax_rounds(d_dirs, D, r.tflags, r.tlist, r.ctr, w, h, 0, h, "flats.relax_towards", s);
-}
-
-// ---- the bitmap engine's rounds (same protocol as relax_rounds: batches of rounds, counts read back per batch) ----
+// ---- the bitmap engine's rounds (batches of rounds, the active-tile counts read back per batch) ----
 // second = true: the tile flags, lists and counters of a search that runs BESIDE another one (the bitmaps are shared)
 static BitsScratch bits_scratch(int w, int h, bool second = false, bool planes = false) {
   Workspace &ws = Workspace::get();
@@ -2469,16 +2065,14 @@ static AsyncRun async_enqueue(const BitsScratch &b, int32_t *D, int w, int h, co
   // 256 / 320 / 384 / 448 / 512 / 640 blocks 33.8 / 33.9 / 34.4 / 35.5 / 36.6 / 38.7 ms for the stage, 53.8 ms (320) against
   // 56.4 (512) for ResolveFlatsEpsilon.
   r.blocks = (uint32_t)r.cus * 5u / 4u;
-  int nap = 1;
   if (const char *e = getenv("RDGPU_FLAT_ASYNC_BLOCKS")) r.blocks = std::max(1, atoi(e));
-  if (const char *e = getenv("RDGPU_FLAT_ASYNC_NAP")) nap = std::min(255, std::max(1, atoi(e)));
   if (beside && beside->mark) beside->mark();
   if (b.pf.P)
     RD_LAUNCH(name, (k_relax_bits_async<SEED_LEVEL, true>), dim3(r.blocks), dim3(NTHR), 0, s, (const unsigned long long *)b.mbits, D, Q,
-              w, h, win, b.tilesX, b.tilesY, budget, nap, b.pf);
+              w, h, win, b.tilesX, b.tilesY, budget, AQ_NAP, b.pf);
   else
     RD_LAUNCH(name, (k_relax_bits_async<SEED_LEVEL>), dim3(r.blocks), dim3(NTHR), 0, s, (const unsigned long long *)b.mbits, D, Q, w,
-              h, win, b.tilesX, b.tilesY, budget, nap, PlaneField{});
+              h, win, b.tilesX, b.tilesY, budget, AQ_NAP, PlaneField{});
   if (beside && beside->go) beside->go();
   return r;
 }
@@ -2486,7 +2080,7 @@ static AsyncRun async_enqueue(const BitsScratch &b, int32_t *D, int w, int h, co
 // the end state, checked on the host (s is synchronised here): no abort, every counter pair equal, every queue drained
 // Returns false (and says so on stderr) when the launch gave up: the levels are valid upper bounds then, and the caller
 // finishes the search in rounds from "every tile active" (the fixed point does not depend on the schedule).
-static bool async_check(const AsyncRun &r, const char *name, hipStream_t s) {
+static bool async_check(const AsyncRun &r, const char *name, hipStream_t s, bool stats) {
   std::vector<uint32_t> all(AQ_WORDS);
   uint32_t live = 0;
   RD_HIP(hipMemcpyAsync(all.data(), r.Q.ctl, AQ_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -2507,7 +2101,7 @@ static bool async_check(const AsyncRun &r, const char *name, hipStream_t s) {
   g_async_info.visits += all[AQ_G_VISITS];
   g_async_info.live_tiles += live;
   g_async_info.launches++;
-  if (getenv("RDGPU_FLAT_TRACE") || getenv("RDGPU_FLAT_ASYNC_STATS"))
+  if (stats)
     fprintf(stderr, "%s asynchronous tail: %u visits, %llu pushes, %u wavefronts on %d CUs, ticks (%d kHz): in visits %llu, longest wavefront %u\n",
             name, all[AQ_G_VISITS], (unsigned long long)pushes, r.blocks * 4u, r.cus, r.rate_khz,
             (unsigned long long)all[AQ_G_BUSY] | ((unsigned long long)all[AQ_G_BUSY + 1] << 32), all[AQ_G_SPAN]);
@@ -2520,9 +2114,10 @@ static uint32_t relax_rounds_bits(const BitsScratch &b, int32_t *D, int w, int h
                                   bool allow_async = true) {
   if (win.hi < 0) win.hi = h;   // single device: all rows, no ghost rows
   uint32_t *hw = Workspace::get().host_words();
-  const bool trace = getenv("RDGPU_FLAT_TRACE") != nullptr;
+  const bool trace = getenv("RDGPU_FLAT_TRACE") != nullptr, stats = trace || getenv("RDGPU_FLAT_ASYNC_STATS");
+  const bool fail = getenv("RDGPU_FLAT_ASYNC_FAIL") != nullptr;   // (tests: the recovery path below)
   uint32_t async_below = allow_async ? async_threshold() : 0u;
-  if (allow_async && getenv("RDGPU_FLAT_ASYNC_FAIL")) async_below = std::max(async_below, 1u);   // (tests: the recovery path below)
+  if (allow_async && fail) async_below = std::max(async_below, 1u);
   uint32_t rounds = 0, grid = (b.ntiles + 3) / 4;   // any tile may be active in the first batch
   for (;;) {
     // with the asynchronous tail ahead the batches are short (the switch is decided on the host, from the counts)
@@ -2568,7 +2163,7 @@ static uint32_t relax_rounds_bits(const BitsScratch &b, int32_t *D, int w, int h
     if (async_below && hw[batch - 1] < async_below) {
       const AsyncRun run = async_enqueue<SEED_LEVEL>(b, D, w, h, name, s, win, false, beside);
       beside = nullptr;   // (its callbacks have run)
-      if (async_check(run, name, s) && !getenv("RDGPU_FLAT_ASYNC_FAIL")) return rounds + 1;
+      if (async_check(run, name, s, stats) && !fail) return rounds + 1;
       // the tail gave up (or the test switch says so): rounds to the end, from every tile
       RD_HIP(hipMemsetAsync(b.tflags, 1, b.ntiles, s));
       async_below = 0;
@@ -2580,6 +2175,35 @@ static uint32_t relax_rounds_bits(const BitsScratch &b, int32_t *D, int w, int h
   }
 }
 
+// The start of a field's search: the bitmap of the cells that take part, the seeds at their level, the tiles to visit first
+// (towards: with the edge counts in cnt, if given).  On planes (b.pf.P) from the bitmaps the classification made (no flags) or
+// from the flag bytes; else on ints (write_m: this field makes the bitmap; L / fh: only the high edges of flats with an outlet).
+template <bool TOWARDS>
+static void launch_prepare(const BitsScratch &b, const uint8_t *flags, const uint32_t *L, const int32_t *fh, int32_t *D, bool write_m,
+                           uint32_t *cnt, int w, int h, hipStream_t s) {
+  // (b.pf.P is set exactly when bits_scratch was asked for planes: it stands for the callers' `planes`)
+  const dim3 per_tile(b.ntiles), per_wave((b.ntiles + 3) / 4), blk(NTHR);
+  const RowWin win{0, h, nullptr, nullptr};
+  if (b.pf.P && !flags && TOWARDS) {
+    // (it also counts the NO_FLOW cells and the high edges from their bitmaps: the away search may start later, the counts
+    // are read with this search's)
+    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare_b<true>), per_wave, blk, 0, s, (const unsigned long long *)b.near, b.pf, b.tflags, h,
+              b.tilesX, b.tilesY, (const unsigned long long *)b.mbits, cnt, 2);
+    if (cnt) RD_LAUNCH("flats.bits_counts_high", k_rows_count, per_wave, blk, 0, s, (const unsigned long long *)b.high, b.ntiles, cnt, 1);
+  } else if (b.pf.P && !flags)
+    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare_b<false>), per_wave, blk, 0, s, (const unsigned long long *)b.high, b.pf, b.tflags, h,
+              b.tilesX, b.tilesY);
+  else if (b.pf.P)
+    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare<TOWARDS, TOWARDS>), per_tile, blk, 0, s, flags, b.pf, b.mbits,
+              TOWARDS ? b.near : (unsigned long long *)nullptr, b.tflags, cnt, w, h, b.tilesX, b.tilesY);
+  else if (write_m)
+    RD_LAUNCH("flats.bits_prepare", (k_bits_prepare<TOWARDS, true>), per_tile, blk, 0, s, flags, L, fh, D, b.mbits, b.tflags, cnt, w, win,
+              (const int32_t *)nullptr, b.tilesX, b.tilesY);
+  else
+    RD_LAUNCH("flats.bits_prepare", (k_bits_prepare<TOWARDS, false>), per_tile, blk, 0, s, flags, L, fh, D, b.mbits, b.tflags, cnt, w, win,
+              (const int32_t *)nullptr, b.tilesX, b.tilesY);
+}
+
 // Towards levels from the low edges, D written in full; write_m: also the bitmap of the cells that take part (shared
 // with the away field); counts3 (optional, host): low edges, high edges, NO_FLOW cells.
 static uint32_t run_bits_towards(const uint8_t *flags, int32_t *D, bool write_m, unsigned long long *counts3, int w, int h,
@@ -2588,27 +2212,9 @@ static uint32_t run_bits_towards(const uint8_t *flags, int32_t *D, bool write_m,
   RD_HIP(hipMemsetAsync(b.tflags, 0, b.ntiles, s));
   RD_HIP(hipMemsetAsync(b.expanded, 0, b.ntiles, s));
   uint32_t *cnt = counts3 ? b.counts : nullptr;
-  if (cnt && flags) RD_HIP(hipMemsetAsync(cnt, 0, (3 * 256 + 8) * sizeof(uint32_t), s));
-  if (planes && !flags) {   // the classification made the bitmaps (mbits, near) and the counts: k_dirs_classify<BITMAPS>
-    RD_HIP(hipMemsetAsync(b.pf.overflow, 0, 2 * sizeof(uint32_t), s));
-    // (it also counts the NO_FLOW cells and the high edges from their bitmaps: the away search may start later, the counts
-    // are read with this search's)
-    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare_b<true>), dim3((b.ntiles + 3) / 4), dim3(NTHR), 0, s,
-              (const unsigned long long *)b.near, b.pf, b.tflags, h, b.tilesX, b.tilesY, (const unsigned long long *)b.mbits, cnt, 2);
-    if (cnt) RD_LAUNCH("flats.bits_counts_high", k_rows_count, dim3((b.ntiles + 3) / 4), dim3(NTHR), 0, s,
-                       (const unsigned long long *)b.high, b.ntiles, cnt, 1);
-  } else if (planes) {
-    RD_HIP(hipMemsetAsync(b.pf.overflow, 0, 2 * sizeof(uint32_t), s));   // (both fields' words)
-    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare<true, true>), dim3(b.ntiles), dim3(NTHR), 0, s, flags, b.pf, b.mbits, b.near,
-              b.tflags, cnt, w, h, b.tilesX, b.tilesY);
-  } else if (write_m)
-    RD_LAUNCH("flats.bits_prepare", (k_bits_prepare<true, true>), dim3(b.ntiles), dim3(NTHR), 0, s, flags, (const uint32_t *)nullptr,
-              (const int32_t *)nullptr, D, b.mbits, b.tflags, cnt, w, RowWin{0, h, nullptr, nullptr}, (const int32_t *)nullptr,
-              b.tilesX, b.tilesY);
-  else
-    RD_LAUNCH("flats.bits_prepare", (k_bits_prepare<true, false>), dim3(b.ntiles), dim3(NTHR), 0, s, flags, (const uint32_t *)nullptr,
-              (const int32_t *)nullptr, D, b.mbits, b.tflags, cnt, w, RowWin{0, h, nullptr, nullptr}, (const int32_t *)nullptr,
-              b.tilesX, b.tilesY);
+  if (cnt && flags) RD_HIP(hipMemsetAsync(cnt, 0, (3 * 256 + 8) * sizeof(uint32_t), s));   // (no flags: the classification counted)
+  if (planes) RD_HIP(hipMemsetAsync(b.pf.overflow, 0, 2 * sizeof(uint32_t), s));   // (both fields' words)
+  launch_prepare<true>(b, flags, nullptr, nullptr, D, write_m, cnt, w, h, s);
   if (cnt) {
     unsigned long long *out = reinterpret_cast<unsigned long long *>(cnt + 3 * 256 + 2);
     RD_LAUNCH("flats.bits_counts", k_bits_counts, dim3(1), dim3(NTHR), 0, s, (const uint32_t *)cnt, out);
@@ -2623,19 +2229,7 @@ static uint32_t run_bits_away(const uint8_t *flags, const uint32_t *L, const int
   const BitsScratch b = bits_scratch(w, h, planes, planes);   // (planes: the field's own planes, beside the towards field's)
   RD_HIP(hipMemsetAsync(b.tflags, 0, b.ntiles, s));
   RD_HIP(hipMemsetAsync(b.expanded, 0, b.ntiles, s));
-  if (planes && !flags)
-    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare_b<false>), dim3((b.ntiles + 3) / 4), dim3(NTHR), 0, s,
-              (const unsigned long long *)b.high, b.pf, b.tflags, h,
-              b.tilesX, b.tilesY);
-  else if (planes)
-    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare<false, false>), dim3(b.ntiles), dim3(NTHR), 0, s, flags, b.pf, b.mbits,
-              (unsigned long long *)nullptr, b.tflags, (uint32_t *)nullptr, w, h, b.tilesX, b.tilesY);
-  else if (write_m)
-    RD_LAUNCH("flats.bits_prepare", (k_bits_prepare<false, true>), dim3(b.ntiles), dim3(NTHR), 0, s, flags, L, fh, D, b.mbits,
-              b.tflags, (uint32_t *)nullptr, w, RowWin{0, h, nullptr, nullptr}, (const int32_t *)nullptr, b.tilesX, b.tilesY);
-  else
-    RD_LAUNCH("flats.bits_prepare", (k_bits_prepare<false, false>), dim3(b.ntiles), dim3(NTHR), 0, s, flags, L, fh, D, b.mbits,
-              b.tflags, (uint32_t *)nullptr, w, RowWin{0, h, nullptr, nullptr}, (const int32_t *)nullptr, b.tilesX, b.tilesY);
+  launch_prepare<false>(b, flags, L, fh, D, write_m, nullptr, w, h, s);
   return relax_rounds_bits<1>(b, D, w, h, "flats.relax_away", s);
 }
 
@@ -2649,8 +2243,7 @@ struct StaticAway {
   AsyncRun run;
 };
 static bool away_beside() {
-  const char *env = getenv("RDGPU_FLAT_AWAY_BESIDE");
-  return !(env && env[0] == '0') && async_threshold() > 0 && getenv("RDGPU_FLAT_TRACE") == nullptr;
+  return !env_is("RDGPU_FLAT_AWAY_BESIDE", '0') && async_threshold() > 0 && getenv("RDGPU_FLAT_TRACE") == nullptr;
 }
 // r06 (plane engine): the TOWARDS search as one enqueue as well -- start levels (with the edge counts), TOWARDS_STATIC_ROUNDS
 // rounds over grids that follow the front's usual shrink (S3: 0.82, 0.44, 0.13, 0.05, 0.03, 0.02 of the tiles), the
@@ -2658,36 +2251,41 @@ static bool away_beside() {
 // synchronisation per call instead of one per batch of rounds, per tail and per check (on a busy host each is a scheduling
 // quantum: profiles/README.md r05u).
 constexpr int TOWARDS_STATIC_ROUNDS = 6;
+// the part the two static searches share: `rounds` rounds over grids that follow the front's usual shrink (towards, S3: 0.82,
+// 0.44, 0.13, 0.05, 0.03, 0.02 of the tiles; away: 0.86, 0.78, 0.37, 0.17, 0.09, 0.04, 0.02, 0.01 -- a grid that is too small
+// for a round is not an error: the tiles past it stay active for the next one), then the asynchronous tail
+template <int SEED_LEVEL>
+static AsyncRun enqueue_static_rounds(const BitsScratch &b, int32_t *D, int rounds, int w, int h, const char *name, hipStream_t s,
+                                      bool second, const Beside *beside) {
+  const RowWin win{0, h, nullptr, nullptr};
+  RD_HIP(hipMemsetAsync(b.ctr, 0, BITS_BATCH * sizeof(uint32_t), s));
+  for (int k = 0; k < rounds; k++) {
+    RD_LAUNCH("flats.tiles_compact", k_tiles_compact, dim3((b.ntiles + NTHR - 1) / NTHR), dim3(NTHR), 0, s, b.tflags, b.ntiles, b.tlist,
+              b.ctr + k);
+    const uint32_t full = (b.ntiles + 3) / 4, grid = k < 2 ? full : std::max<uint32_t>(256u, full >> (k - 1));
+    if (b.pf.P)
+      RD_LAUNCH(name, (k_relax_planes<SEED_LEVEL>), dim3(grid), dim3(NTHR), 0, s, (const unsigned long long *)b.mbits, b.expanded, b.pf,
+                (const uint32_t *)b.tlist, (const uint32_t *)(b.ctr + k), b.tflags, w, h, b.tilesX, b.tilesY);
+    else
+      RD_LAUNCH(name, (k_relax_bits<SEED_LEVEL>), dim3(grid), dim3(NTHR), 0, s, (const unsigned long long *)b.mbits, b.expanded, D,
+                (const uint32_t *)b.tlist, (const uint32_t *)(b.ctr + k), b.tflags, w, h, win, b.tilesX, b.tilesY);
+  }
+  return async_enqueue<SEED_LEVEL>(b, D, w, h, name, s, win, second, beside);   // (mark() before the tail's launch, go() after)
+}
+
 static StaticAway enqueue_towards_static(const uint8_t *flags, unsigned long long *d_counts3, int w, int h, hipStream_t s,
                                          const Beside *beside) {
   static_assert(TOWARDS_STATIC_ROUNDS < BITS_BATCH - 1, "the tail's own counter word is the last one");
   StaticAway st;
   st.b = bits_scratch(w, h, false, true);
   const BitsScratch &b = st.b;
-  const RowWin win{0, h, nullptr, nullptr};
   RD_HIP(hipMemsetAsync(b.tflags, 0, b.ntiles, s));
   RD_HIP(hipMemsetAsync(b.expanded, 0, b.ntiles, s));
   RD_HIP(hipMemsetAsync(b.pf.overflow, 0, 2 * sizeof(uint32_t), s));   // (both fields' words)
-  if (!flags) {   // the classification made the bitmaps and counted the low edges
-    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare_b<true>), dim3((b.ntiles + 3) / 4), dim3(NTHR), 0, s,
-              (const unsigned long long *)b.near, b.pf, b.tflags, h, b.tilesX, b.tilesY, (const unsigned long long *)b.mbits, b.counts, 2);
-    RD_LAUNCH("flats.bits_counts_high", k_rows_count, dim3((b.ntiles + 3) / 4), dim3(NTHR), 0, s, (const unsigned long long *)b.high,
-              b.ntiles, b.counts, 1);
-  } else {
-    RD_HIP(hipMemsetAsync(b.counts, 0, (3 * 256 + 8) * sizeof(uint32_t), s));
-    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare<true, true>), dim3(b.ntiles), dim3(NTHR), 0, s, flags, b.pf, b.mbits, b.near,
-              b.tflags, b.counts, w, h, b.tilesX, b.tilesY);
-  }
+  if (flags) RD_HIP(hipMemsetAsync(b.counts, 0, (3 * 256 + 8) * sizeof(uint32_t), s));   // (no flags: the classification counted the low edges)
+  launch_prepare<true>(b, flags, nullptr, nullptr, nullptr, true, b.counts, w, h, s);
   RD_LAUNCH("flats.bits_counts", k_bits_counts, dim3(1), dim3(NTHR), 0, s, (const uint32_t *)b.counts, d_counts3);
-  RD_HIP(hipMemsetAsync(b.ctr, 0, BITS_BATCH * sizeof(uint32_t), s));
-  for (int k = 0; k < TOWARDS_STATIC_ROUNDS; k++) {
-    RD_LAUNCH("flats.tiles_compact", k_tiles_compact, dim3((b.ntiles + NTHR - 1) / NTHR), dim3(NTHR), 0, s, b.tflags, b.ntiles, b.tlist,
-              b.ctr + k);
-    const uint32_t full = (b.ntiles + 3) / 4, grid = k < 2 ? full : std::max<uint32_t>(256u, full >> (k - 1));
-    RD_LAUNCH("flats.relax_towards", (k_relax_planes<2>), dim3(grid), dim3(NTHR), 0, s, (const unsigned long long *)b.mbits, b.expanded,
-              b.pf, (const uint32_t *)b.tlist, (const uint32_t *)(b.ctr + k), b.tflags, w, h, b.tilesX, b.tilesY);
-  }
-  st.run = async_enqueue<2>(b, nullptr, w, h, "flats.relax_towards", s, win, false, beside);   // (mark() before the tail's launch, go() after)
+  st.run = enqueue_static_rounds<2>(b, nullptr, TOWARDS_STATIC_ROUNDS, w, h, "flats.relax_towards", s, false, beside);
   return st;
 }
 
@@ -2696,76 +2294,35 @@ static StaticAway enqueue_away_static(const uint8_t *flags, int32_t *A, int w, i
   StaticAway sa;
   sa.b = bits_scratch(w, h, true, planes);
   const BitsScratch &b = sa.b;
-  const RowWin win{0, h, nullptr, nullptr};
   RD_HIP(hipMemsetAsync(b.tflags, 0, b.ntiles, s));
   RD_HIP(hipMemsetAsync(b.expanded, 0, b.ntiles, s));
-  if (planes && !flags)
-    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare_b<false>), dim3((b.ntiles + 3) / 4), dim3(NTHR), 0, s,
-              (const unsigned long long *)b.high, b.pf, b.tflags, h,
-              b.tilesX, b.tilesY);
-  else if (planes)
-    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare<false, false>), dim3(b.ntiles), dim3(NTHR), 0, s, flags, b.pf, b.mbits,
-              (unsigned long long *)nullptr, b.tflags, (uint32_t *)nullptr, w, h, b.tilesX, b.tilesY);
-  else
-  RD_LAUNCH("flats.bits_prepare", (k_bits_prepare<false, false>), dim3(b.ntiles), dim3(NTHR), 0, s, flags, (const uint32_t *)nullptr,
-            (const int32_t *)nullptr, A, b.mbits, b.tflags, (uint32_t *)nullptr, w, win, (const int32_t *)nullptr, b.tilesX, b.tilesY);
-  RD_HIP(hipMemsetAsync(b.ctr, 0, BITS_BATCH * sizeof(uint32_t), s));
-  for (int k = 0; k < AWAY_STATIC_ROUNDS; k++) {
-    RD_LAUNCH("flats.tiles_compact", k_tiles_compact, dim3((b.ntiles + NTHR - 1) / NTHR), dim3(NTHR), 0, s, b.tflags, b.ntiles, b.tlist,
-              b.ctr + k);
-    // (the front of this search shrinks fast -- S3: 0.86, 0.78, 0.37, 0.17, 0.09, 0.04, 0.02, 0.01 of the tiles -- and a grid
-    // that is too small for a round is not an error: the tiles past it stay active for the next one)
-    const uint32_t full = (b.ntiles + 3) / 4, grid = k < 2 ? full : std::max<uint32_t>(256u, full >> (k - 1));
-    if (planes)
-      RD_LAUNCH("flats.relax_away", (k_relax_planes<1>), dim3(grid), dim3(NTHR), 0, s, (const unsigned long long *)b.mbits, b.expanded,
-                b.pf, (const uint32_t *)b.tlist, (const uint32_t *)(b.ctr + k), b.tflags, w, h, b.tilesX, b.tilesY);
-    else
-    RD_LAUNCH("flats.relax_away", (k_relax_bits<1>), dim3(grid), dim3(NTHR), 0, s, (const unsigned long long *)b.mbits,
-              b.expanded, A, (const uint32_t *)b.tlist, (const uint32_t *)(b.ctr + k), b.tflags, w, h, win, b.tilesX, b.tilesY);
-  }
-  sa.run = async_enqueue<1>(b, A, w, h, "flats.relax_away", s, win, true, nullptr);
+  launch_prepare<false>(b, flags, nullptr, nullptr, A, false, nullptr, w, h, s);
+  sa.run = enqueue_static_rounds<1>(b, A, AWAY_STATIC_ROUNDS, w, h, "flats.relax_away", s, true, nullptr);
   return sa;
 }
-// on a stream that has waited for the side stream: the end state of the tail, and the number of rounds that had work
-// (the towards field of the static plane search: the same end-of-search check; *recovered: the tail had given up)
-static uint32_t finish_towards_static(const StaticAway &st, int w, int h, hipStream_t s, bool *recovered) {
-  uint32_t counts[TOWARDS_STATIC_ROUNDS];
-  RD_HIP(hipMemcpyAsync(counts, st.b.ctr, sizeof counts, hipMemcpyDeviceToHost, s));
-  const bool ok = async_check(st.run, "flats.relax_towards", s);   // (synchronises s)
+
+// On a stream that has waited for the search's stream: the end state of the tail, and the number of rounds that had work.
+// *recovered (optional): the tail had given up (or the test switch says so) and the search was finished in rounds, from every
+// tile, on this stream.
+template <int SEED_LEVEL>
+static uint32_t finish_static(const StaticAway &st, int32_t *D, int nrounds, int w, int h, const char *name, hipStream_t s,
+                              bool *recovered = nullptr) {
+  uint32_t counts[BITS_BATCH];
+  RD_HIP(hipMemcpyAsync(counts, st.b.ctr, nrounds * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  const bool ok = async_check(st.run, name, s, getenv("RDGPU_FLAT_TRACE") || getenv("RDGPU_FLAT_ASYNC_STATS"));   // (synchronises s)
   uint32_t rounds = 1;
-  for (int k = 0; k < TOWARDS_STATIC_ROUNDS; k++) rounds += counts[k] != 0;
-  *recovered = false;
-  if (!ok || getenv("RDGPU_FLAT_ASYNC_FAIL")) {
+  for (int k = 0; k < nrounds; k++) rounds += counts[k] != 0;
+  const bool redo = !ok || getenv("RDGPU_FLAT_ASYNC_FAIL");
+  if (redo) {
     RD_HIP(hipMemsetAsync(st.b.tflags, 1, st.b.ntiles, s));
-    rounds += relax_rounds_bits<2>(st.b, nullptr, w, h, "flats.relax_towards", s, RowWin{0, -1, nullptr, nullptr}, nullptr, false);
-    *recovered = true;
+    rounds += relax_rounds_bits<SEED_LEVEL>(st.b, D, w, h, name, s, RowWin{0, -1, nullptr, nullptr}, nullptr, false);
   }
-  return rounds;
-}
-static uint32_t finish_away_static(const StaticAway &sa, int32_t *A, int w, int h, hipStream_t s, bool *recovered = nullptr) {
-  uint32_t counts[AWAY_STATIC_ROUNDS];
-  RD_HIP(hipMemcpyAsync(counts, sa.b.ctr, sizeof counts, hipMemcpyDeviceToHost, s));
-  const bool ok = async_check(sa.run, "flats.relax_away", s);   // (synchronises s)
-  uint32_t rounds = 1;
-  for (int k = 0; k < AWAY_STATIC_ROUNDS; k++) rounds += counts[k] != 0;
-  if (recovered) *recovered = false;
-  if (!ok || getenv("RDGPU_FLAT_ASYNC_FAIL")) {   // the tail gave up: rounds to the end, from every tile, on this stream
-    RD_HIP(hipMemsetAsync(sa.b.tflags, 1, sa.b.ntiles, s));
-    rounds += relax_rounds_bits<1>(sa.b, A, w, h, "flats.relax_away", s, RowWin{0, -1, nullptr, nullptr}, nullptr, false);
-    if (recovered) *recovered = true;
-  }
+  if (recovered) *recovered = redo;
   return rounds;
 }
 
-static bool lean_labels() {
-  const char *env = getenv("RDGPU_RFE_LEAN");   // =0: labels, outlet marks and flat heights as the flat_mask path makes them: A/B and tests
-  return !(env && env[0] == '0');
-}
-
-static bool use_bits_engine() {
-  const char *env = getenv("RDGPU_FLAT_BITS");   // =0: the stencil relaxation: A/B and tests
-  return !(env && env[0] == '0');
-}
+// RDGPU_RFE_LEAN=0: labels, outlet marks and flat heights as the flat_mask path makes them: A/B and tests
+static bool lean_labels() { return !env_is("RDGPU_RFE_LEAN", '0'); }
 
 // Computes flat_mask (M) for the DEM; d_dirs must hold d8_flow_directions output.
 // Returns device pointers (workspace) to M, L, fh through the out parameters.
@@ -2778,7 +2335,7 @@ static void resolve_flats_device(const T *d_z, const uint8_t *d_dirs, int w, int
   *outM = M;
   *outL = nullptr;
   *outFh = nullptr;
-  const bool lean = outA && use_bits_engine() && lean_labels();
+  const bool lean = outA && lean_labels();
   if (!lean) RD_HIP(hipMemsetAsync(M, 0, n * sizeof(int32_t), s));  // flat_mask.setAll(0), :469 (lean: the towards search writes every cell)
   g_fstats = rdgpu_flat_stats{0, 0, 0, 0, 0};
   g_async_info = AsyncInfo{0, 0, 0, 0};
@@ -2792,10 +2349,9 @@ static void resolve_flats_device(const T *d_z, const uint8_t *d_dirs, int w, int
     RD_LAUNCH("flats.findflats_classify", (k_dirs_classify<T, false, true>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, ff_nodata,
               (uint8_t *)nullptr, flags, w, h, tilesX, ntiles);
   }
-  uint32_t *low = nullptr, *highall = nullptr;
   uint32_t nlow = 0, nhigh_all = 0, nnoflow = 0;
   if (!lean) {
-    compact_edges(flags, n, &low, &nlow, &highall, &nhigh_all, &nnoflow, s, !use_bits_engine());
+    count_edges(flags, n, &nlow, &nhigh_all, &nnoflow, s);
     g_fstats.low_edges = nlow;
     g_fstats.noflow_cells = nnoflow;
     g_fstats.high_edges = nhigh_all;
@@ -2812,7 +2368,7 @@ static void resolve_flats_device(const T *d_z, const uint8_t *d_dirs, int w, int
     // The caller wants the levels, the labels and the flat heights (ResolveFlatsEpsilon), nothing per flat beyond that: the
     // labels do not depend on the searches here.  "The flat has an outlet" (:491-500) is what the towards levels say anyway
     // (a flat without a low edge is never reached: its cells keep DINF and k_flat_epsilon4 skips them), so the away field
-    // starts from EVERY high edge and fh needs no "-1 = no outlet" marks: no k_flat_mark_low pass, no fill of fh.
+    // starts from EVERY high edge and fh needs no "-1 = no outlet" marks: no k_flat_mark_low_flags pass, no fill of fh.
     const uint32_t tilesX = (w + CW - 1) / CW, ntiles = tilesX * ((h + CH - 1) / CH);
     T *colZ = ws.buf<T>("flats.colz", (size_t)ntiles * 2 * CH);
     uint32_t *colL = ws.buf<uint32_t>("flats.coll", (size_t)ntiles * 2 * CH);
@@ -2820,8 +2376,7 @@ static void resolve_flats_device(const T *d_z, const uint8_t *d_dirs, int w, int
     // stream: the tail keeps two resident blocks per CU busy with dependent visits and leaves the memory system idle, the
     // labelling is three streaming passes.  (Started with the search's first rounds, which are throughput-bound
     // themselves, the labels only took their turn: 64.4 -> 63.0 ms at S3.)  RDGPU_RFE_OVERLAP=0: one stream.
-    const char *env = getenv("RDGPU_RFE_OVERLAP");
-    const bool beside = !(env && env[0] == '0');
+    const bool beside = !env_is("RDGPU_RFE_OVERLAP", '0');
     hipStream_t ls = s;
     Workspace::SideLane *lane = nullptr;   // (lane 0: the labels; lane 1: the away search)
     if (beside) {
@@ -2841,10 +2396,9 @@ static void resolve_flats_device(const T *d_z, const uint8_t *d_dirs, int w, int
     if (!beside) labels();
     // ... the away search too, on a second side stream (see enqueue_away_static), only on request: with the labels already
     // beside the tail a third stream gains nothing (S3: 58.7 ms without, 59.5 with; RDGPU_RFE_AWAY_BESIDE=1)
-    const char *env3 = getenv("RDGPU_RFE_AWAY_BESIDE");
     // (the edge counts come with the towards search's start levels, as on the directions path: no counting pass)
     unsigned long long c3[3] = {0, 0, 0};
-    const bool away_too = beside && env3 && env3[0] == '1' && away_beside();
+    const bool away_too = beside && env_is("RDGPU_RFE_AWAY_BESIDE", '1') && away_beside();
     Workspace::SideLane *alane = away_too ? &ws.side_lane(1) : nullptr;
     StaticAway sa;
     int32_t *A = nullptr;
@@ -2869,7 +2423,7 @@ static void resolve_flats_device(const T *d_z, const uint8_t *d_dirs, int w, int
     g_fstats.noflow_cells = c3[2];
     if (away_started) {
       RD_HIP(hipStreamWaitEvent(s, alane->join, 0));
-      g_fstats.away_levels = finish_away_static(sa, A, w, h, s);
+      g_fstats.away_levels = finish_static<1>(sa, A, AWAY_STATIC_ROUNDS, w, h, "flats.relax_away", s);
     } else if (c3[0] > 0 && c3[1] > 0) {
       A = ws.buf<int32_t>("flats.away", n);
       g_fstats.away_levels = run_bits_away(flags, nullptr, nullptr, A, false, w, h, s);
@@ -2890,29 +2444,19 @@ static void resolve_flats_device(const T *d_z, const uint8_t *d_dirs, int w, int
   launch_ccl_border<T>(d_z, L, w, h, s);
   RD_LAUNCH("flats.ccl_flatten", k_ccl_flatten, dim3(sgrid(n)), dim3(NTHR), 0, s, L, n);
   RD_HIP(hipMemsetAsync(fh, 0xFF, n * sizeof(int32_t), s));        // -1 everywhere
-  if (low)
-    RD_LAUNCH("flats.mark_low", k_flat_mark_low, dim3((nlow + NTHR - 1) / NTHR), dim3(NTHR), 0, s, (const uint32_t *)low,
-              nlow, (const uint32_t *)L, fh);
-  else
-    RD_LAUNCH("flats.mark_low", k_flat_mark_low_flags, dim3(sgrid(n)), dim3(NTHR), 0, s, (const uint8_t *)flags, (const uint32_t *)L,
-              fh, n);
+  RD_LAUNCH("flats.mark_low", k_flat_mark_low_flags, dim3(sgrid(n)), dim3(NTHR), 0, s, (const uint8_t *)flags, (const uint32_t *)L,
+            fh, n);
 
   // away gradient: sources = high edges whose flat has a low edge
   int32_t *A = nullptr;
   if (nhigh_all > 0) {
     A = ws.buf<int32_t>("flats.away", n);
-    if (use_bits_engine()) {
-      g_fstats.away_levels = run_bits_away(flags, L, fh, A, true, w, h, s);
-    } else {
-      RD_HIP(hipMemsetAsync(A, 0x7F, n * sizeof(int32_t), s));
-      g_fstats.away_levels = run_relax_away(d_dirs, A, highall, nhigh_all, L, fh, w, h, s);
-    }
+    g_fstats.away_levels = run_bits_away(flags, L, fh, A, true, w, h, s);
     RD_LAUNCH("flats.height", k_flat_height, dim3(sgrid(n)), dim3(NTHR), 0, s, (const int32_t *)A, (const uint32_t *)L, fh,
               n);
   }
   // towards gradient from every low edge, then the combined mask in place
-  g_fstats.towards_levels = use_bits_engine() ? run_bits_towards(flags, M, nhigh_all == 0, nullptr, w, h, s)
-                                              : run_relax_towards(d_dirs, flags, M, w, h, s);
+  g_fstats.towards_levels = run_bits_towards(flags, M, nhigh_all == 0, nullptr, w, h, s);
   if (outA) {   // the caller combines on the fly (k_flat_epsilon): M holds the towards levels
     *outA = A;
     return;
@@ -2922,41 +2466,45 @@ static void resolve_flats_device(const T *d_z, const uint8_t *d_dirs, int w, int
 }
 
 static thread_local bool g_planes_overflowed = false;   // (flat_resolution_device: this call repeats a plane search that overflowed)
+// A level beyond 16 bits: once more, on ints (the last pass has not run, or left dirs alone: it holds what the classification
+// wrote, nothing is lost).
+template <class T>
+void flat_resolution_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, hipStream_t s);
+template <class T>
+static void repeat_on_ints(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, hipStream_t s) {
+  g_planes_overflowed = true;
+  struct Reset { ~Reset() { g_planes_overflowed = false; } } reset;
+  flat_resolution_device<T>(d_z, nodata, w, h, d_dirs, s);
+}
+// The last pass from the two fields' planes.  over / abort_t / abort_a (device words, optional): the pass looks at them itself
+// and leaves dirs alone when one is set.
+static void launch_dirs_qp(const BitsScratch &bt, const BitsScratch &ba, int have_away, uint8_t *d_dirs, int w, int h, hipStream_t s,
+                           const uint32_t *over = nullptr, const uint32_t *abort_t = nullptr, const uint32_t *abort_a = nullptr) {
+  RD_LAUNCH("flats.dirs_q", k_flat_dirs_qp, dim3(xcd_grid((bt.ntiles + 3) / 4)), dim3(NTHR), 0, s, bt.pf, ba.pf,
+            (const unsigned long long *)bt.near, have_away, d_dirs, w, h, bt.tilesX, bt.tilesY, over, abort_t, abort_a);
+}
 template <class T>
 void flat_resolution_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, hipStream_t s) {
   if (!d_z || !d_dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8: null pointer");
   if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8: width and height must be positive");
   if ((uint64_t)w * (uint64_t)h > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8: raster too large");
-  const char *env = getenv("RDGPU_FLAT_FULLMASK");
-  const char *envf = getenv("RDGPU_FLAT_FUSED_CLASSIFY");   // =0: d8_flow_directions and the classification as two kernels: A/B and tests
-  const bool fused_classify = use_bits_engine() && !(env && env[0] == '1') && !(envf && envf[0] == '0');
-  if (!fused_classify) flowdirs_device<T>(d_z, nodata, w, h, d_dirs, MODE_D8, s);   // =1: through the full flat_mask (labels, flat heights): A/B and tests
-  if (env && env[0] == '1') {
-    int32_t *M, *fh;
-    uint32_t *L;
-    resolve_flats_device<T>(d_z, d_dirs, w, h, &M, &L, &fh, s);
-    if (L)   // there is at least one low edge
-      launch_masked_dirs<T>(d_z, M, d_dirs, w, h, s);
-    return;
-  }
-  // directions only: the two level fields suffice (k_flat_dirs_levels)
+  // directions only: the two level fields suffice, no labels and no flat heights; d8_flow_directions is part of the
+  // classification pass (k_dirs_classify)
   const uint64_t n = (uint64_t)w * h;
   Workspace &ws = Workspace::get();
   g_fstats = rdgpu_flat_stats{0, 0, 0, 0, 0};
   g_async_info = AsyncInfo{0, 0, 0, 0};
   // r05: the last pass from 4 bits per cell, without the DEM (k_flat_dirs_q; the cells next to a low edge get their direction
   // in the classification); RDGPU_FLAT_Q=0: k_flat_dirs_levels over the level planes and the DEM (r02-r04): A/B and tests
-  const char *envq = getenv("RDGPU_FLAT_Q");
-  const bool qpass = fused_classify && !(envq && envq[0] == '0');
+  const bool qpass = !env_is("RDGPU_FLAT_Q", '0');
   // r06: the level fields as bit planes per tile (flat_planes.inc); RDGPU_FLAT_PLANES=0, a level beyond 16 bits (an open flat
-  // wider than 65 000 cells), or any of the A/B switches above: one int per cell (r02-r05).  The plane engine takes its
+  // wider than 65 000 cells), RDGPU_FLAT_Q=0 or RDGPU_FLAT_TRACE: one int per cell (r02-r05).  The plane engine takes its
   // bitmaps and counts from the flag bytes, or straight from the classification (RDGPU_FLAT_CLASS_BITMAPS=1).
-  const char *envp = getenv("RDGPU_FLAT_PLANES"), *envb = getenv("RDGPU_FLAT_CLASS_BITMAPS");
-  const bool planes = qpass && use_bits_engine() && !(envp && envp[0] == '0') && !g_planes_overflowed && !getenv("RDGPU_FLAT_TRACE");
+  const bool planes = qpass && !env_is("RDGPU_FLAT_PLANES", '0') && !g_planes_overflowed && !getenv("RDGPU_FLAT_TRACE");
   // (measured r06: the start kernels drop from 2.9 to 0.4 ms and 4.8 GB of flag traffic go away, but the classification itself
   // goes from 4.9 to 6.6 ms with the ballots and row words in it -- 22.7 ms either way at S3; so the flags stay the default and
   // RDGPU_FLAT_CLASS_BITMAPS=1 selects the bitmaps: profiles/r06f_flats_class_bitmaps_ab.json)
-  const bool class_bitmaps = planes && envb && envb[0] == '1';
+  const bool class_bitmaps = planes && env_is("RDGPU_FLAT_CLASS_BITMAPS", '1');
   uint8_t *flags = class_bitmaps ? nullptr : ws.buf<uint8_t>("flats.flags", n);
   if (class_bitmaps) {
     const BitsScratch bt = bits_scratch(w, h, false, true);
@@ -2967,7 +2515,7 @@ void flat_resolution_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dir
     const uint32_t tilesX = (w + SW - 1) / SW, ntiles = tilesX * 2u * (uint32_t)((h + BT - 1) / BT);   // whole search tiles: their rows past the raster read as empty
     RD_LAUNCH("flats.dirs_classify", (k_dirs_classify<T, true, false, true>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, nodata,
               d_dirs, (uint8_t *)nullptr, w, h, tilesX, ntiles, bm);
-  } else if (fused_classify) {
+  } else {
     const uint32_t tilesX = (w + SW - 1) / SW, ntiles = tilesX * ((h + KLH - 1) / KLH);
     if (qpass)
       RD_LAUNCH("flats.dirs_classify", (k_dirs_classify<T, true>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, nodata, d_dirs, flags,
@@ -2975,12 +2523,10 @@ void flat_resolution_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dir
     else
       RD_LAUNCH("flats.dirs_classify", (k_dirs_classify<T>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, nodata, d_dirs, flags, w, h,
                 tilesX, ntiles);
-  } else {
-    launch_classify<T>(d_z, d_dirs, w, h, flags, s);
   }
   int32_t *TWd = planes ? nullptr : ws.buf<int32_t>("flats.mask", n), *A = nullptr;
-  const char *envs = getenv("RDGPU_FLAT_STATIC");   // =0: the towards search in batches of rounds decided on the host (r02-r05): A/B and tests
-  if (planes && away_beside() && !(envs && envs[0] == '0')) {
+  // RDGPU_FLAT_STATIC=0: the towards search in batches of rounds decided on the host (r02-r05): A/B and tests
+  if (planes && away_beside() && !env_is("RDGPU_FLAT_STATIC", '0')) {
     // Everything enqueued, nothing read back: towards search (start, rounds, tail), the away search beside its tail on a side
     // stream, the last pass -- which looks at the overflow and abort words itself and leaves `dirs` alone when one is set.
     // Then ONE synchronisation: the tails' end states, the overflow words, the counts.
@@ -2996,16 +2542,14 @@ void flat_resolution_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dir
     };
     const StaticAway st = enqueue_towards_static(flags, d_c3, w, h, s, &bs);
     RD_HIP(hipStreamWaitEvent(s, lane.join, 0));
-    const uint32_t *abT = st.run.Q.ctl + AQ_G_ABORT, *abA = sa.run.Q.ctl + AQ_G_ABORT;
-    RD_LAUNCH("flats.dirs_q", k_flat_dirs_qp, dim3(xcd_grid((st.b.ntiles + 3) / 4)), dim3(NTHR), 0, s, st.b.pf, sa.b.pf,
-              (const unsigned long long *)st.b.near, 1, d_dirs, w, h, st.b.tilesX, st.b.tilesY, (const uint32_t *)st.b.pf.overflow, abT, abA);
+    launch_dirs_qp(st.b, sa.b, 1, d_dirs, w, h, s, st.b.pf.overflow, st.run.Q.ctl + AQ_G_ABORT, sa.run.Q.ctl + AQ_G_ABORT);
     unsigned long long c3[3] = {0, 0, 0};
     uint32_t over[2] = {0, 0};
     RD_HIP(hipMemcpyAsync(c3, d_c3, sizeof c3, hipMemcpyDeviceToHost, s));
     RD_HIP(hipMemcpyAsync(over, st.b.pf.overflow, sizeof over, hipMemcpyDeviceToHost, s));
     bool recT = false, recA = false;
-    g_fstats.towards_levels = finish_towards_static(st, w, h, s, &recT);   // (the synchronisation)
-    g_fstats.away_levels = finish_away_static(sa, nullptr, w, h, s, &recA);
+    g_fstats.towards_levels = finish_static<2>(st, nullptr, TOWARDS_STATIC_ROUNDS, w, h, "flats.relax_towards", s, &recT);   // (the synchronisation)
+    g_fstats.away_levels = finish_static<1>(sa, nullptr, AWAY_STATIC_ROUNDS, w, h, "flats.relax_away", s, &recA);
     g_fstats.low_edges = c3[0];
     g_fstats.high_edges = c3[1];
     g_fstats.noflow_cells = c3[2];
@@ -3013,83 +2557,50 @@ void flat_resolution_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dir
       RD_HIP(hipMemcpyAsync(over, st.b.pf.overflow, sizeof over, hipMemcpyDeviceToHost, s));
       RD_HIP(hipStreamSynchronize(s));
     }
-    if (over[0] | over[1]) {   // a level beyond 16 bits: once more, on ints (the last pass left dirs as the classification wrote it)
-      g_planes_overflowed = true;
-      struct Reset { ~Reset() { g_planes_overflowed = false; } } reset;
-      flat_resolution_device<T>(d_z, nodata, w, h, d_dirs, s);
-      return;
-    }
-    if (recT || recA)
-      RD_LAUNCH("flats.dirs_q", k_flat_dirs_qp, dim3(xcd_grid((st.b.ntiles + 3) / 4)), dim3(NTHR), 0, s, st.b.pf, sa.b.pf,
-                (const unsigned long long *)st.b.near, 1, d_dirs, w, h, st.b.tilesX, st.b.tilesY, (const uint32_t *)nullptr,
-                (const uint32_t *)nullptr, (const uint32_t *)nullptr);
+    if (over[0] | over[1]) return repeat_on_ints<T>(d_z, nodata, w, h, d_dirs, s);
+    if (recT || recA) launch_dirs_qp(st.b, sa.b, 1, d_dirs, w, h, s);
     return;
   }
-  if (use_bits_engine()) {
-    // no edge lists at all: the seeds are bitmaps made from the flags, the counts come with them
-    unsigned long long c3[3] = {0, 0, 0};
-    // the away search starts when the towards search enters its tail (the counts have arrived by then), on a side stream
-    const bool beside = away_beside();
-    Workspace::SideLane *lane = beside ? &ws.side_lane(1) : nullptr;
-    StaticAway sa;
-    bool started = false;
-    Beside bs;
-    bs.mark = [&]() {
-      if (beside) RD_HIP(hipEventRecord(lane->fork, s));   // (the bitmaps are made, the flags and the DEM as the caller left them)
-    };
-    bs.go = [&]() {
-      if (!beside || c3[0] == 0 || c3[1] == 0) return;
-      RD_HIP(hipStreamWaitEvent(lane->stream, lane->fork, 0));
-      if (!planes) A = ws.buf<int32_t>("flats.away", n);
-      sa = enqueue_away_static(flags, A, w, h, lane->stream, planes);
-      RD_HIP(hipEventRecord(lane->join, lane->stream));
-      started = true;
-    };
-    g_fstats.towards_levels = run_bits_towards(flags, TWd, true, c3, w, h, s, &bs, planes);
-    if (started) RD_HIP(hipStreamWaitEvent(s, lane->join, 0));
-    g_fstats.low_edges = c3[0];
-    g_fstats.high_edges = c3[1];
-    g_fstats.noflow_cells = c3[2];
-    if (c3[0] == 0) return;   // no flats, or none with an outlet (:475-481)
-    bool have_away = started;
-    if (c3[1] > 0 && !started) {
-      if (!planes) A = ws.buf<int32_t>("flats.away", n);
-      g_fstats.away_levels = run_bits_away(flags, nullptr, nullptr, A, false, w, h, s, planes);
-      have_away = true;
-    }
-    if (started) g_fstats.away_levels = finish_away_static(sa, A, w, h, s);
-    if (planes) {
-      const BitsScratch bt = bits_scratch(w, h, false, true), ba = bits_scratch(w, h, true, true);
-      uint32_t over[2] = {0, 0};
-      RD_HIP(hipMemcpyAsync(over, bt.pf.overflow, sizeof over, hipMemcpyDeviceToHost, s));
-      RD_HIP(hipStreamSynchronize(s));
-      if (over[0] | over[1]) {   // a level beyond 16 bits: once more, on ints (dirs holds what the classification wrote: nothing is lost)
-        g_planes_overflowed = true;
-        struct Reset { ~Reset() { g_planes_overflowed = false; } } reset;
-        flat_resolution_device<T>(d_z, nodata, w, h, d_dirs, s);
-        return;
-      }
-      RD_LAUNCH("flats.dirs_q", k_flat_dirs_qp, dim3(xcd_grid((bt.ntiles + 3) / 4)), dim3(NTHR), 0, s, bt.pf, ba.pf,
-                (const unsigned long long *)bt.near, have_away ? 1 : 0, d_dirs, w, h, bt.tilesX, bt.tilesY, (const uint32_t *)nullptr,
-                (const uint32_t *)nullptr, (const uint32_t *)nullptr);
-      return;
-    }
-  } else {
-    uint32_t *low = nullptr, *highall = nullptr;
-    uint32_t nlow = 0, nhigh_all = 0, nnoflow = 0;
-    compact_edges(flags, n, &low, &nlow, &highall, &nhigh_all, &nnoflow, s);
-    g_fstats.low_edges = nlow;
-    g_fstats.noflow_cells = nnoflow;
-    g_fstats.high_edges = nhigh_all;
-    if (nlow == 0) return;   // no flats, or none with an outlet (:475-481)
-    if (nhigh_all > 0) {
-      // every high edge seeds (the flats without an outlet are not filtered out: that would need their labels; their
-      // cells are never reached by the towards field, so they get no direction either way)
-      A = ws.buf<int32_t>("flats.away", n);
-      RD_HIP(hipMemsetAsync(A, 0x7F, n * sizeof(int32_t), s));
-      g_fstats.away_levels = run_relax_away(d_dirs, A, highall, nhigh_all, nullptr, nullptr, w, h, s);
-    }
-    g_fstats.towards_levels = run_relax_towards(d_dirs, flags, TWd, w, h, s);
+  // no edge lists at all: the seeds are bitmaps made from the flags, the counts come with them
+  unsigned long long c3[3] = {0, 0, 0};
+  // the away search starts when the towards search enters its tail (the counts have arrived by then), on a side stream
+  const bool beside = away_beside();
+  Workspace::SideLane *lane = beside ? &ws.side_lane(1) : nullptr;
+  StaticAway sa;
+  bool started = false;
+  Beside bs;
+  bs.mark = [&]() {
+    if (beside) RD_HIP(hipEventRecord(lane->fork, s));   // (the bitmaps are made, the flags and the DEM as the caller left them)
+  };
+  bs.go = [&]() {
+    if (!beside || c3[0] == 0 || c3[1] == 0) return;
+    RD_HIP(hipStreamWaitEvent(lane->stream, lane->fork, 0));
+    if (!planes) A = ws.buf<int32_t>("flats.away", n);
+    sa = enqueue_away_static(flags, A, w, h, lane->stream, planes);
+    RD_HIP(hipEventRecord(lane->join, lane->stream));
+    started = true;
+  };
+  g_fstats.towards_levels = run_bits_towards(flags, TWd, true, c3, w, h, s, &bs, planes);
+  if (started) RD_HIP(hipStreamWaitEvent(s, lane->join, 0));
+  g_fstats.low_edges = c3[0];
+  g_fstats.high_edges = c3[1];
+  g_fstats.noflow_cells = c3[2];
+  if (c3[0] == 0) return;   // no flats, or none with an outlet (:475-481)
+  bool have_away = started;
+  if (c3[1] > 0 && !started) {
+    if (!planes) A = ws.buf<int32_t>("flats.away", n);
+    g_fstats.away_levels = run_bits_away(flags, nullptr, nullptr, A, false, w, h, s, planes);
+    have_away = true;
+  }
+  if (started) g_fstats.away_levels = finish_static<1>(sa, A, AWAY_STATIC_ROUNDS, w, h, "flats.relax_away", s);
+  if (planes) {
+    const BitsScratch bt = bits_scratch(w, h, false, true), ba = bits_scratch(w, h, true, true);
+    uint32_t over[2] = {0, 0};
+    RD_HIP(hipMemcpyAsync(over, bt.pf.overflow, sizeof over, hipMemcpyDeviceToHost, s));
+    RD_HIP(hipStreamSynchronize(s));
+    if (over[0] | over[1]) return repeat_on_ints<T>(d_z, nodata, w, h, d_dirs, s);
+    launch_dirs_qp(bt, ba, have_away ? 1 : 0, d_dirs, w, h, s);
+    return;
   }
   const uint32_t tilesX = (w + SW - 1) / SW, ntiles = tilesX * ((h + KLH - 1) / KLH);
   if (qpass)
@@ -3359,13 +2870,10 @@ struct rdgpu_flat_shard {
   uint8_t *dirs = nullptr, *flags = nullptr;
   uint32_t *L = nullptr, *first = nullptr;
   int32_t *fh = nullptr, *D[2] = {nullptr, nullptr};
-  uint32_t *src[2] = {nullptr, nullptr};
-  uint32_t nsrc[2] = {0, 0};
   uint8_t *tflags[2] = {nullptr, nullptr};
   uint32_t *tlist = nullptr, *ctr = nullptr;
-  // the bitmap engine's state (RDGPU_FLAT_BITS=0: the stencil relaxation instead): cells that take part per tile row,
-  // the same for the two ghost rows next to the own rows, "tile visited" per field
-  bool bits = false;
+  // the bitmap search's state: cells that take part per tile row, the same for the two ghost rows next to the own rows,
+  // "tile visited" per field
   unsigned long long *mbits = nullptr, *gmask[2] = {nullptr, nullptr};
   uint8_t *expanded[2] = {nullptr, nullptr};
   bool seeded[2] = {false, false};
@@ -3397,43 +2905,27 @@ template <class T>
 static void fs_relax(rdgpu_flat_shard *f, int phase) {
   hipStream_t s = f->stream;
   const int w = f->w, h = f->rows;
-  const uint32_t tilesX = (w + CW - 1) / CW, tilesY = (h + RCH - 1) / RCH;
-  const int row_lo = f->gtop, row_hi = h - f->gbot;   // the own rows: ghost rows feed, they are not relaxed here
+  const int row_lo = f->gtop, row_hi = h - f->gbot;   // the own rows: ghost rows feed, they are not searched here
   int32_t *D = f->D[phase];
-  if (f->bits) {
-    BitsScratch b;
-    b.tilesX = (w + BT - 1) / BT; b.tilesY = (row_hi - row_lo + BT - 1) / BT; b.ntiles = b.tilesX * b.tilesY;
-    b.mbits = f->mbits; b.tflags = f->tflags[phase]; b.expanded = f->expanded[phase]; b.tlist = f->tlist; b.ctr = f->ctr;
-    b.counts = nullptr;
-    const RowWin win{row_lo, row_hi, f->gtop ? f->gmask[0] : nullptr, f->gbot ? f->gmask[1] : nullptr};
-    if (!f->seeded[phase]) {
-      f->seeded[phase] = true;
-      RD_HIP(hipMemsetAsync(b.expanded, 0, b.ntiles, s));
-      if (phase == 0)
-        RD_LAUNCH("flats.bits_prepare", (k_bits_prepare<true, true>), dim3(b.ntiles), dim3(NTHR), 0, s, (const uint8_t *)f->flags,
-                  (const uint32_t *)nullptr, (const int32_t *)nullptr, D, b.mbits, b.tflags, (uint32_t *)nullptr, w, win,
-                  (const int32_t *)nullptr, b.tilesX, b.tilesY);
-      else   // away sources: the high edges of flats the towards levels reach ("has an outlet")
-        RD_LAUNCH("flats.bits_prepare", (k_bits_prepare<false, false>), dim3(b.ntiles), dim3(NTHR), 0, s, (const uint8_t *)f->flags,
-                  (const uint32_t *)nullptr, (const int32_t *)nullptr, D, b.mbits, b.tflags, (uint32_t *)nullptr, w, win,
-                  (const int32_t *)f->D[0], b.tilesX, b.tilesY);
-    }
-    f->rounds[phase] += phase ? relax_rounds_bits<1>(b, D, w, h, "flats.relax_away", s, win)
-                              : relax_rounds_bits<2>(b, D, w, h, "flats.relax_towards", s, win);
-    return;
-  }
+  BitsScratch b;
+  b.tilesX = (w + BT - 1) / BT; b.tilesY = (row_hi - row_lo + BT - 1) / BT; b.ntiles = b.tilesX * b.tilesY;
+  b.mbits = f->mbits; b.tflags = f->tflags[phase]; b.expanded = f->expanded[phase]; b.tlist = f->tlist; b.ctr = f->ctr;
+  b.counts = nullptr;
+  const RowWin win{row_lo, row_hi, f->gtop ? f->gmask[0] : nullptr, f->gbot ? f->gmask[1] : nullptr};
   if (!f->seeded[phase]) {
     f->seeded[phase] = true;
+    RD_HIP(hipMemsetAsync(b.expanded, 0, b.ntiles, s));
     if (phase == 0)
-      RD_LAUNCH("flats.init_towards", k_flat_init_towards, dim3(tilesX * tilesY), dim3(NTHR), 0, s, (const uint8_t *)f->flags, D,
-                f->tflags[0], w, h, row_lo, row_hi, tilesX, tilesY);
-    else if (f->nsrc[1])
-      RD_LAUNCH("flats.seed", k_flat_seed, dim3((f->nsrc[1] + NTHR - 1) / NTHR), dim3(NTHR), 0, s,
-                (const uint32_t *)f->src[1], f->nsrc[1], (const uint32_t *)f->L, (const int32_t *)nullptr, D,
-                f->tflags[1], w, tilesX, tilesY, (const int32_t *)f->D[0]);
+      RD_LAUNCH("flats.bits_prepare", (k_bits_prepare<true, true>), dim3(b.ntiles), dim3(NTHR), 0, s, (const uint8_t *)f->flags,
+                (const uint32_t *)nullptr, (const int32_t *)nullptr, D, b.mbits, b.tflags, (uint32_t *)nullptr, w, win,
+                (const int32_t *)nullptr, b.tilesX, b.tilesY);
+    else   // away sources: the high edges of flats the towards levels reach ("has an outlet")
+      RD_LAUNCH("flats.bits_prepare", (k_bits_prepare<false, false>), dim3(b.ntiles), dim3(NTHR), 0, s, (const uint8_t *)f->flags,
+                (const uint32_t *)nullptr, (const int32_t *)nullptr, D, b.mbits, b.tflags, (uint32_t *)nullptr, w, win,
+                (const int32_t *)f->D[0], b.tilesX, b.tilesY);
   }
-  f->rounds[phase] += relax_rounds((const uint8_t *)f->dirs, D, f->tflags[phase], f->tlist, f->ctr, w, h, row_lo, row_hi,
-                                   phase ? "flats.relax_away" : "flats.relax_towards", s);
+  f->rounds[phase] += phase ? relax_rounds_bits<1>(b, D, w, h, "flats.relax_away", s, win)
+                            : relax_rounds_bits<2>(b, D, w, h, "flats.relax_towards", s, win);
 }
 
 template <class T>
@@ -3469,8 +2961,9 @@ static rdgpu_flat_shard *fs_begin(const T *d_z, T nodata, int w, int rows, int g
       f->owned.push_back(p);
       return p;
     };
-    const uint32_t tilesX = (w + CW - 1) / CW, ntiles = tilesX * ((rows + CH - 1) / CH);   // labelling tiles
-    const uint32_t rtiles = tilesX * ((rows + RCH - 1) / RCH);                               // relaxation tiles
+    // labelling tiles (64 x 32, over all rows); the search's 64 x 64 tiles over the own rows are never more
+    const uint32_t tilesX = (w + CW - 1) / CW, ntiles = tilesX * ((rows + CH - 1) / CH);
+    const uint32_t btiles = tilesX * (uint32_t)((rows - gtop - gbot + BT - 1) / BT);
     f->dirs = (uint8_t *)alloc(n);
     f->flags = (uint8_t *)alloc(n);
     f->L = (uint32_t *)alloc(n * 4);
@@ -3478,42 +2971,26 @@ static rdgpu_flat_shard *fs_begin(const T *d_z, T nodata, int w, int rows, int g
     f->fh = (int32_t *)alloc(n * 4);
     f->D[0] = (int32_t *)alloc(n * 4);
     f->D[1] = (int32_t *)alloc(n * 4);
-    f->tflags[0] = (uint8_t *)alloc(rtiles);
-    f->tflags[1] = (uint8_t *)alloc(rtiles);
-    f->tlist = (uint32_t *)alloc((size_t)rtiles * 4);
+    f->tflags[0] = (uint8_t *)alloc(ntiles);
+    f->tflags[1] = (uint8_t *)alloc(ntiles);
+    f->tlist = (uint32_t *)alloc((size_t)ntiles * 4);
     f->ctr = (uint32_t *)alloc(BITS_BATCH * sizeof(uint32_t));
-    f->bits = use_bits_engine();
-    if (f->bits) {   // (64 x 64 tiles over the own rows: never more than the 64 x 32 tiles over all rows)
-      const uint32_t btiles = tilesX * (uint32_t)((rows - gtop - gbot + BT - 1) / BT);
-      f->mbits = (unsigned long long *)alloc((size_t)btiles * BT * 8);
-      f->gmask[0] = (unsigned long long *)alloc((size_t)tilesX * 8);
-      f->gmask[1] = (unsigned long long *)alloc((size_t)tilesX * 8);
-      f->expanded[0] = (uint8_t *)alloc(btiles);
-      f->expanded[1] = (uint8_t *)alloc(btiles);
-    }
+    f->mbits = (unsigned long long *)alloc((size_t)btiles * BT * 8);
+    f->gmask[0] = (unsigned long long *)alloc((size_t)tilesX * 8);
+    f->gmask[1] = (unsigned long long *)alloc((size_t)tilesX * 8);
+    f->expanded[0] = (uint8_t *)alloc(btiles);
+    f->expanded[1] = (uint8_t *)alloc(btiles);
     flowdirs_device<T>(d_z, nodata, w, rows, f->dirs, MODE_D8, s);
     launch_classify<T>(d_z, (const uint8_t *)f->dirs, w, rows, f->flags, s);
     // sources are own cells only; the ghost rows' distances arrive from their owners
     if (gtop) RD_HIP(hipMemsetAsync(f->flags, 0, (size_t)gtop * w, s));
     if (gbot) RD_HIP(hipMemsetAsync(f->flags + (size_t)(rows - gbot) * w, 0, (size_t)gbot * w, s));
-    const uint8_t masks[2] = {F_LOW, F_HIGH};
-    for (int ph = 0; ph < 2; ph++) {
-      uint32_t *list = nullptr;
-      const uint32_t cnt = compact_flags(f->flags, masks[ph], n, ph ? "flats.highall" : "flats.low", &list, s);
-      f->nsrc[ph] = cnt;
-      if (cnt) {
-        f->src[ph] = (uint32_t *)alloc((size_t)cnt * 4);
-        RD_HIP(hipMemcpyAsync(f->src[ph], list, (size_t)cnt * 4, hipMemcpyDeviceToDevice, s));
-      }
-    }
     // ghost cells are never relaxed or given a direction here: their NO_FLOW cells keep feeding (DIR_GHOST_NOFLOW),
     // the others are marked as "has a direction"
     if (gtop) RD_LAUNCH("flatshard.ghost_dirs", k_fs_ghost_dirs, dim3(((size_t)gtop * w + NTHR - 1) / NTHR), dim3(NTHR), 0, s, f->dirs, (uint32_t)gtop * (uint32_t)w);
     if (gbot) RD_LAUNCH("flatshard.ghost_dirs", k_fs_ghost_dirs, dim3(((size_t)gbot * w + NTHR - 1) / NTHR), dim3(NTHR), 0, s, f->dirs + (size_t)(rows - gbot) * w, (uint32_t)gbot * (uint32_t)w);
-    if (f->bits) {
-      if (gtop) RD_LAUNCH("flatshard.ghost_mask", k_fs_ghost_mask, dim3(tilesX), dim3(64), 0, s, (const uint8_t *)f->dirs + (size_t)(gtop - 1) * w, w, f->gmask[0]);
-      if (gbot) RD_LAUNCH("flatshard.ghost_mask", k_fs_ghost_mask, dim3(tilesX), dim3(64), 0, s, (const uint8_t *)f->dirs + (size_t)(rows - gbot) * w, w, f->gmask[1]);
-    }
+    if (gtop) RD_LAUNCH("flatshard.ghost_mask", k_fs_ghost_mask, dim3(tilesX), dim3(64), 0, s, (const uint8_t *)f->dirs + (size_t)(gtop - 1) * w, w, f->gmask[0]);
+    if (gbot) RD_LAUNCH("flatshard.ghost_mask", k_fs_ghost_mask, dim3(tilesX), dim3(64), 0, s, (const uint8_t *)f->dirs + (size_t)(rows - gbot) * w, w, f->gmask[1]);
     RD_LAUNCH("flats.ccl_tile", (k_ccl_tile<T>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, f->L, w, rows, tilesX, ntiles, (T *)nullptr,
               (uint32_t *)nullptr);
     launch_ccl_border<T>(d_z, f->L, w, rows, s);
@@ -3521,8 +2998,8 @@ static rdgpu_flat_shard *fs_begin(const T *d_z, T nodata, int w, int rows, int g
     RD_HIP(hipMemsetAsync(f->fh, 0, n * 4, s));
     RD_HIP(hipMemsetAsync(f->D[0], 0x7F, n * 4, s));
     RD_HIP(hipMemsetAsync(f->D[1], 0x7F, n * 4, s));
-    RD_HIP(hipMemsetAsync(f->tflags[0], 0, rtiles, s));
-    RD_HIP(hipMemsetAsync(f->tflags[1], 0, rtiles, s));
+    RD_HIP(hipMemsetAsync(f->tflags[0], 0, ntiles, s));
+    RD_HIP(hipMemsetAsync(f->tflags[1], 0, ntiles, s));
     RD_HIP(hipStreamSynchronize(s));
   } catch (...) {
     fs_free(f);
@@ -3548,9 +3025,8 @@ static void fs_inject(rdgpu_flat_shard *f, int phase, const int32_t *d_above, co
   const CutRows cr = cut_rows(f);
   const uint32_t tilesX = (f->w + CW - 1) / CW;
   const dim3 grid((f->w + NTHR - 1) / NTHR), blk(NTHR);
-  // the tile row of the own row next to the ghost row, in the engine's tiling (64-row tiles from the first own row / 32-row
-  // tiles from row 0)
-  auto tile_row = [&](int own_row) { return f->bits ? (own_row - f->gtop) / BT : own_row / RCH; };
+  // the tile row of the own row next to the ghost row (64-row tiles from the first own row)
+  auto tile_row = [&](int own_row) { return (own_row - f->gtop) / BT; };
   if (d_above && cr.row[0] >= 0)
     RD_LAUNCH("flatshard.inject", k_fs_inject, grid, blk, 0, f->stream, f->D[phase], d_above, cr.row[0], tile_row(cr.row[1]), f->w,
               f->tflags[phase], tilesX);
@@ -3730,12 +3206,10 @@ void resolve_flats_epsilon_device(T *d_z, T nodata, int w, int h, hipStream_t s)
   if (!d_z) throw Error(RDGPU_ERR_ARG, "rdgpu_resolve_flats_epsilon: null pointer");
   if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_resolve_flats_epsilon: width and height must be positive");
   if ((uint64_t)w * (uint64_t)h > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, "rdgpu_resolve_flats_epsilon: raster too large");
-  // r05: on the lean path (the default) FindFlats is part of the classification pass; RDGPU_RFE_FUSED_FINDFLATS=0 or the other
-  // paths: k_find_flats writes the pseudo direction raster first
-  const char *envf = getenv("RDGPU_RFE_FUSED_FINDFLATS");
-  const bool fused_ff = use_bits_engine() && lean_labels() && !(envf && envf[0] == '0');
+  // r05: on the lean path (the default) FindFlats is part of the classification pass; RDGPU_RFE_LEAN=0: k_find_flats
+  // writes the pseudo direction raster first
   uint8_t *flats = nullptr;
-  if (!fused_ff) {
+  if (!lean_labels()) {
     flats = Workspace::get().buf<uint8_t>("flats.findflats", (size_t)w * h);
     uint32_t tilesX;
     const uint32_t ntiles = stencil_tiles(w, h, &tilesX);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B timing of one stage under several environment switches, in ONE process on one GPU (a gpurun call is expensive):
 
-    python tools/ab_stage.py --stage flats --size 40000 --cfg "" --cfg "RDGPU_FLAT_SUPER=0" --cfg "RDGPU_FLAT_SUPER_OCC=5"
+    python tools/ab_stage.py --stage flats --size 40000 --cfg "" --cfg "RDGPU_FLAT_PLANES=0" --cfg "RDGPU_FLAT_STATIC=0"
 
 Every configuration's output is compared with the first one's (the engine's switches must not change results); the
 best of --reps wall times and the per-kernel HIP-event totals of one extra instrumented run are reported as one JSON line.

@@ -8,8 +8,8 @@ python - "$f" <<'PY' > $GRAFT_REPO_ROOT/gpurun_out/round_trace.txt
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-# the last stage call: take the last contiguous series after the last k_flat_classify
-idx = [i for i, r in enumerate(rows) if "k_flat_classify" in r["Kernel_Name"]]
+# the last stage call: take the last contiguous series after the last k_dirs_classify
+idx = [i for i, r in enumerate(rows) if "k_dirs_classify" in r["Kernel_Name"]]
 rows = rows[idx[-1]:]
 prev_end = None
 for r in rows:

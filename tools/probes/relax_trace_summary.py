@@ -4,7 +4,7 @@ rows=[l.split() for l in open('gpurun_out/relax_trace.txt')]
 phases=[];cur=None
 for t,d,nm,g in rows:
     t=float(t);d=float(d)
-    if nm in('seed','init','prep'):
+    if nm=='prep':
         cur={'kind':nm,'relax':[], 'compact':0.0,'t0':t}
         phases.append(cur)
     elif nm=='relax': cur['relax'].append((t,d,int(g)))

@@ -3111,6 +3111,12 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
       RD_HIP(hipStreamSynchronize(s));
       g_stats.host_syncs++;
       if (getenv("RDGPU_FILL_DEBUG")) fprintf(stderr, "fill_fused: pair pass: %u records, overflow %u, %u tiles on the slow road; %d rounds enqueued\n", hrc[4 + 1], hw[5], hw[12], rdone);
+      // Not reachable on purpose by a DEM a test can hold.  A thread of k_chase_links gives up after 16384 hops over links
+      // that nobody has shortened yet, so a round needs a chain of more than 16384 basins each spilling into the next (a
+      // staircase of pits: tests/test_fallback_engines_gpu.py builds one of 20 000) AND the threads behind a link must not
+      // have finished first: every thread of the round runs at once and stores its own shortened link as soon as it ends,
+      // so a walk from distance d meets a finished link after about sqrt(2 d) hops.  16384 hops taken alone would need a
+      // chain of ~10^8 basins, or a grid whose blocks run one after the other from the chain's far end -- timing, not input.
       if (hw[0] != 0) { if (getenv("RDGPU_FILL_DEBUG")) fprintf(stderr, "fill_fused: hook chain unfinished\n"); return false; }
       if (hw[5] != 0) { if (getenv("RDGPU_FILL_DEBUG")) fprintf(stderr, "fill_fused: pair list overflow (B %u cap %llu nseg %u segcap %u nwork %u)\n", B, (unsigned long long)cap, nseg, segcap, nwork1); return false; }   // the pair list overflowed: the DEM is untouched, the classic path takes over
       rounds_run = 0;

@@ -278,7 +278,10 @@ RDGPU_DECL_WS(u64, uint64_t)
  *   RDGPU_FILL_EDGE_CAP=<n>    capacity of that list in records (default min(12 per basin, cells/2)); a list
  *                              that does not fit falls back to raster passes
  *   RDGPU_FILL_ROUND_BATCH=<n> contraction rounds enqueued per stream synchronisation (default: all of them at once --
- *                              a fill synchronises twice, rdgpu_fill_stats::host_syncs) */
+ *                              a fill synchronises twice, rdgpu_fill_stats::host_syncs)
+ *   RDGPU_FILL_TAIL_ROOTS=<n>  a round entered by at most n live roots and 8 n pair records, and every round after it,
+ *                              runs in the single-workgroup tail kernel (default 1024); 0: never, every round is
+ *                              full-width launches; a huge value: from round 2 on */
 /* Statistics of the last fill on this process (for DESIGN.md / bench.py reporting). */
 typedef struct rdgpu_fill_stats {
   uint64_t cells;       /* width*height                                   */

@@ -20,7 +20,7 @@
 //                     rounds 2..: k_edge_round on the pair list (raster k_scan passes as overflow fallback);
 //                     k_hook (hook every component along its lowest pass; mutual pairs keep the
 //                     smaller id as root), k_chase_links (pointer jumping carrying the path
-//                     maximum), k_update_basins, k_compact_roots.  This is Boruvka's contraction:
+//                     maximum), k_update_basins (compact labels: k_settle_basins, once), k_compact_roots.  This is Boruvka's contraction:
 //                     the number of live components at least halves per round.
 //   4. k_finalize     z(c) <- max(z(c), acc[lab[c]]).
 //
@@ -468,10 +468,28 @@ __global__ __launch_bounds__(NTHR) void k_mark_terminals(const uint32_t *__restr
 // (r06) dyn != nullptr in the round kernels below: the count is read from the device -- the rounds of a fill are enqueued
 // without a host read-back between them, over grids the host sizes from upper bounds (grid-stride loops: a launch
 // whose list turns out empty costs a few microseconds).
+// (r07) The bodies of the round kernels are __device__ functions over (block index, block count) and NT threads per
+// block: the __global__ kernels below are their full-width launches, k_rounds_tail runs them in ONE workgroup, round after
+// round, once a round's lists are small.  A full-width round kernel returns at once when its gate says that the tail
+// kernel takes the round: the live roots and the records entering it (cnt[0], cnt[1]: final before the round's first
+// launch, and never growing from round to round) are both under the tail's thresholds.
+struct TailGate {
+  const uint32_t *cnt = nullptr;   // rc + 4 r of the round; nullptr: the round is never the tail's
+  uint32_t roots = 0, recs = 0;
+  __device__ __forceinline__ bool taken() const { return cnt && cnt[0] <= roots && cnt[1] <= recs; }
+};
+
+template <int NT>
+__device__ __forceinline__ void best_reset_body(const uint32_t *roots, uint32_t nroots, unsigned long long *best,
+                                                uint32_t blk, uint32_t nblk) {
+  for (uint32_t i = blk * NT + threadIdx.x; i < nroots; i += nblk * NT) best[roots[i]] = ~0ull;
+}
 __global__ __launch_bounds__(NTHR) void k_best_reset(const uint32_t *__restrict__ roots, uint32_t nroots,
-                                                     unsigned long long *best, const uint32_t *__restrict__ dyn = nullptr) {
+                                                     unsigned long long *best, const uint32_t *__restrict__ dyn = nullptr,
+                                                     TailGate gate = TailGate()) {
+  if (gate.taken()) return;
   if (dyn) nroots = *dyn;
-  for (uint32_t i = blockIdx.x * NTHR + threadIdx.x; i < nroots; i += gridDim.x * NTHR) best[roots[i]] = ~0ull;
+  best_reset_body<NTHR>(roots, nroots, best, blockIdx.x, gridDim.x);
 }
 
 // One raster pass of a Boruvka round.  tiles_in == nullptr: all tiles (XCD-banded order); otherwise
@@ -891,37 +909,35 @@ constexpr int DT_SLOTS = 4096;   // the dense rounds' pair table of a block (204
 // most records of a block connect the same few large components, and without this the lists stop shrinking and
 // thousands of lanes hit the same best[] entries with atomics.  (Merging per pair in the first list round was measured
 // slower: 2.5 vs 1.4 ms -- its records are already merged per tile.)
-template <bool SEG>
-__global__ __launch_bounds__(NTHR) void k_edge_round(const uint32_t *__restrict__ ea, const uint32_t *__restrict__ eb,
-                                                     const uint32_t *__restrict__ ek, uint32_t n,
-                                                     const uint32_t *__restrict__ segcount, uint32_t segcap,
-                                                     const uint32_t *__restrict__ cur, unsigned long long *best, uint32_t B,
-                                                     uint32_t *oa, uint32_t *ob, uint32_t *ok, uint32_t *ocount,
-                                                     const uint32_t *__restrict__ dyn = nullptr) {
+template <bool SEG, int NT>
+__device__ __forceinline__ void edge_round_body(const uint32_t *ea, const uint32_t *eb, const uint32_t *ek, uint32_t n,
+                                                const uint32_t *segcount, uint32_t segcap, const uint32_t *cur,
+                                                unsigned long long *best, uint32_t B, uint32_t *oa, uint32_t *ob, uint32_t *ok,
+                                                uint32_t *ocount, uint32_t blk, uint32_t nblk) {
   constexpr bool DEDUP = !SEG;
-  __shared__ uint32_t wtot[NTHR / 64];
+  __shared__ uint32_t wtot[NT / 64];
   __shared__ uint32_t bbase, dn;
   __shared__ unsigned long long dt_pair[DEDUP ? DT_SLOTS : 1];
   __shared__ uint32_t dt_key[DEDUP ? DT_SLOTS : 1];
   __shared__ uint16_t dt_list[DEDUP ? DT_SLOTS : 1];
-  if (dyn) n = *dyn;   // (the dense rounds: the record count the round before left on the device)
-  for (size_t i0 = (size_t)blockIdx.x * (NTHR * EPT); i0 < (size_t)n; i0 += (size_t)gridDim.x * (NTHR * EPT)) {
+  for (size_t i0 = (size_t)blk * (NT * EPT); i0 < (size_t)n; i0 += (size_t)nblk * (NT * EPT)) {
   size_t lim = n;   // records of this block's range that exist
-  if (SEG) {
+  if (SEG && NT == NTHR) {   // (a block's range lies in one segment; a wider workgroup's may not: per record below)
     const uint32_t seg = (uint32_t)(i0 / segcap);
     lim = (size_t)seg * segcap + segcount[seg];
     if (i0 >= lim) continue;
   }
   if (DEDUP) {
-    for (int i = threadIdx.x; i < DT_SLOTS; i += NTHR) { dt_pair[i] = ~0ull; dt_key[i] = 0xFFFFFFFFu; }
+    for (int i = threadIdx.x; i < DT_SLOTS; i += NT) { dt_pair[i] = ~0ull; dt_key[i] = 0xFFFFFFFFu; }
     if (threadIdx.x == 0) dn = 0;
   }
   uint32_t a[EPT], b[EPT], k[EPT];
   bool ok_[EPT];
 #pragma unroll
   for (int r = 0; r < EPT; r++) {
-    const size_t i = i0 + (size_t)r * NTHR + threadIdx.x;
+    const size_t i = i0 + (size_t)r * NT + threadIdx.x;
     ok_[r] = i < lim;
+    if (SEG && NT != NTHR && ok_[r]) ok_[r] = i % segcap < segcount[i / segcap];
     a[r] = ok_[r] ? ea[i] : B;   // an absent record reads as (outside, outside): dead
     b[r] = ok_[r] ? eb[i] : B;
     k[r] = ok_[r] ? ek[i] : 0u;
@@ -944,7 +960,7 @@ __global__ __launch_bounds__(NTHR) void k_edge_round(const uint32_t *__restrict_
       }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < DT_SLOTS; i += NTHR) {
+    for (int i = threadIdx.x; i < DT_SLOTS; i += NT) {
       const bool occ = dt_pair[i] != ~0ull;
       const unsigned long long bal = __ballot(occ);
       uint32_t base = 0;
@@ -954,7 +970,7 @@ __global__ __launch_bounds__(NTHR) void k_edge_round(const uint32_t *__restrict_
     }
     __syncthreads();
     nd = dn;
-    for (uint32_t i = threadIdx.x; i < nd; i += NTHR) {
+    for (uint32_t i = threadIdx.x; i < nd; i += NT) {
       const int sl = dt_list[i];
       const unsigned long long pr = dt_pair[sl];
       const uint32_t lo = (uint32_t)(pr >> 32), hi = (uint32_t)pr, key = dt_key[sl];
@@ -984,13 +1000,14 @@ __global__ __launch_bounds__(NTHR) void k_edge_round(const uint32_t *__restrict_
   if (lane == 0) wtot[wv] = mine;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const uint32_t tot = wtot[0] + wtot[1] + wtot[2] + wtot[3] + nd;
+    uint32_t tot = nd;
+    for (int q = 0; q < NT / 64; q++) tot += wtot[q];
     bbase = tot ? atomicAdd(ocount, tot) : 0;
   }
   __syncthreads();
   uint32_t off = bbase;
   if (DEDUP) {
-    for (uint32_t i = threadIdx.x; i < nd; i += NTHR) {
+    for (uint32_t i = threadIdx.x; i < nd; i += NT) {
       const int sl = dt_list[i];
       const unsigned long long pr = dt_pair[sl];
       oa[off + i] = (uint32_t)(pr >> 32); ob[off + i] = (uint32_t)pr; ok[off + i] = dt_key[sl];
@@ -1009,8 +1026,20 @@ __global__ __launch_bounds__(NTHR) void k_edge_round(const uint32_t *__restrict_
   __syncthreads();   // (the next chunk of the block reuses the tables)
   }
 }
+template <bool SEG>
+__global__ __launch_bounds__(NTHR) void k_edge_round(const uint32_t *__restrict__ ea, const uint32_t *__restrict__ eb,
+                                                     const uint32_t *__restrict__ ek, uint32_t n,
+                                                     const uint32_t *__restrict__ segcount, uint32_t segcap,
+                                                     const uint32_t *__restrict__ cur, unsigned long long *best, uint32_t B,
+                                                     uint32_t *oa, uint32_t *ob, uint32_t *ok, uint32_t *ocount,
+                                                     const uint32_t *__restrict__ dyn = nullptr, TailGate gate = TailGate()) {
+  if (gate.taken()) return;
+  if (dyn) n = *dyn;   // (the dense rounds: the record count the round before left on the device)
+  edge_round_body<SEG, NTHR>(ea, eb, ek, n, segcount, segcap, cur, best, B, oa, ob, ok, ocount, blockIdx.x, gridDim.x);
+}
 
-__global__ __launch_bounds__(NTHR) void k_sum_segments(const uint32_t *__restrict__ segcount, uint32_t nseg, uint32_t *total) {
+__global__ __launch_bounds__(NTHR) void k_sum_segments(const uint32_t *__restrict__ segcount, uint32_t nseg, uint32_t *total,
+                                                       uint32_t *total2 = nullptr) {
   __shared__ uint32_t part[NTHR];
   uint32_t v = 0;
   for (uint32_t i = threadIdx.x; i < nseg; i += NTHR) v += segcount[i];
@@ -1020,7 +1049,10 @@ __global__ __launch_bounds__(NTHR) void k_sum_segments(const uint32_t *__restric
     if ((int)threadIdx.x < st) part[threadIdx.x] += part[threadIdx.x + st];
     __syncthreads();
   }
-  if (threadIdx.x == 0) *total = part[0];
+  if (threadIdx.x == 0) {
+    *total = part[0];
+    if (total2) *total2 = part[0];
+  }
 }
 
 // alive flags -> list of tiles for the next round (roughly ascending: blocks append in launch order) + count
@@ -1032,11 +1064,10 @@ __global__ __launch_bounds__(NTHR) void k_compact_alive(const uint8_t *__restric
   if (hit) list[slot] = i;
 }
 
-__global__ __launch_bounds__(NTHR) void k_hook(const uint32_t *__restrict__ roots, uint32_t nroots,
-                                               const unsigned long long *__restrict__ best,
-                                               unsigned long long *link, const uint32_t *__restrict__ dyn = nullptr) {
-  if (dyn) nroots = *dyn;
-  for (uint32_t i = blockIdx.x * NTHR + threadIdx.x; i < nroots; i += gridDim.x * NTHR) {
+template <int NT>
+__device__ __forceinline__ void hook_body(const uint32_t *roots, uint32_t nroots, const unsigned long long *best,
+                                          unsigned long long *link, uint32_t blk, uint32_t nblk) {
+  for (uint32_t i = blk * NT + threadIdx.x; i < nroots; i += nblk * NT) {
     const uint32_t r = roots[i];
     const unsigned long long b = best[r];
     const uint32_t t = (uint32_t)b;
@@ -1050,13 +1081,20 @@ __global__ __launch_bounds__(NTHR) void k_hook(const uint32_t *__restrict__ root
     link[r] = keep_root ? (unsigned long long)r : b;
   }
 }
+__global__ __launch_bounds__(NTHR) void k_hook(const uint32_t *__restrict__ roots, uint32_t nroots,
+                                               const unsigned long long *__restrict__ best,
+                                               unsigned long long *link, const uint32_t *__restrict__ dyn = nullptr,
+                                               TailGate gate = TailGate()) {
+  if (gate.taken()) return;
+  if (dyn) nroots = *dyn;
+  hook_body<NTHR>(roots, nroots, best, link, blockIdx.x, gridDim.x);
+}
 
 // pointer jumping over this round's hook forest, carrying the path maximum in the high word.
-__global__ __launch_bounds__(NTHR) void k_chase_links(const uint32_t *__restrict__ roots, uint32_t nroots,
-                                                      unsigned long long *link, int maxhops, uint32_t *flag,
-                                                      const uint32_t *__restrict__ dyn = nullptr) {
-  if (dyn) nroots = *dyn;
-  for (uint32_t i = blockIdx.x * NTHR + threadIdx.x; i < nroots; i += gridDim.x * NTHR) {
+template <int NT>
+__device__ __forceinline__ void chase_links_body(const uint32_t *roots, uint32_t nroots, unsigned long long *link, int maxhops,
+                                                 uint32_t *flag, uint32_t blk, uint32_t nblk) {
+  for (uint32_t i = blk * NT + threadIdx.x; i < nroots; i += nblk * NT) {
     const uint32_t r = roots[i];
     unsigned long long l = __hip_atomic_load(&link[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     uint32_t p = (uint32_t)l, m = (uint32_t)(l >> 32);
@@ -1079,6 +1117,13 @@ __global__ __launch_bounds__(NTHR) void k_chase_links(const uint32_t *__restrict
     if (unfinished) *flag = 1;
   }
 }
+__global__ __launch_bounds__(NTHR) void k_chase_links(const uint32_t *__restrict__ roots, uint32_t nroots,
+                                                      unsigned long long *link, int maxhops, uint32_t *flag,
+                                                      const uint32_t *__restrict__ dyn = nullptr, TailGate gate = TailGate()) {
+  if (gate.taken()) return;
+  if (dyn) nroots = *dyn;
+  chase_links_body<NTHR>(roots, nroots, link, maxhops, flag, blockIdx.x, gridDim.x);
+}
 
 __global__ __launch_bounds__(NTHR) void k_update_basins(uint32_t *cur, uint32_t *acc,
                                                         const unsigned long long *__restrict__ link, uint32_t B,
@@ -1097,25 +1142,32 @@ __global__ __launch_bounds__(NTHR) void k_update_basins(uint32_t *cur, uint32_t 
 }
 
 constexpr int RPT = 8;   // roots per thread: 2048 per block, so a round over 1e7 roots is 5e3 same-address atomics
-__global__ __launch_bounds__(NTHR) void k_compact_roots(const uint32_t *__restrict__ roots_in, uint32_t nroots,
-                                                        const unsigned long long *__restrict__ link,
-                                                        uint32_t *roots_out, uint32_t *counter,
-                                                        const uint32_t *__restrict__ dyn = nullptr) {
-  __shared__ uint32_t wtot[NTHR / 64];
+// curw (the compact-label fill): cur[r] = parent of r for EVERY root of the round.  The next round's k_edge_round looks
+// cur[] up for the ids in its records only, and those are this round's roots (round 2: basin ids, every open basin being a
+// root of round 1) or closed ids, whose cur[] k_init_tables wrote for good.  All other entries of cur[] are stale until
+// k_settle_basins.
+template <int NT>
+__device__ __forceinline__ void compact_roots_body(const uint32_t *roots_in, uint32_t nroots, const unsigned long long *link,
+                                                   uint32_t *roots_out, uint32_t *counter, uint32_t *curw, uint32_t blk,
+                                                   uint32_t nblk) {
+  __shared__ uint32_t wtot[NT / 64];
   __shared__ uint32_t bbase;
-  if (dyn) nroots = *dyn;
-  for (uint32_t i0 = blockIdx.x * (NTHR * RPT); i0 < nroots; i0 += gridDim.x * (NTHR * RPT)) {
+  for (uint32_t i0 = blk * (NT * RPT); i0 < nroots; i0 += nblk * (NT * RPT)) {
   uint32_t r[RPT];
   bool ok[RPT];
 #pragma unroll
   for (int q = 0; q < RPT; q++) {
-    const uint32_t i = i0 + q * NTHR + threadIdx.x;
+    const uint32_t i = i0 + q * NT + threadIdx.x;
     ok[q] = i < nroots;
     r[q] = ok[q] ? roots_in[i] : 0u;
   }
   bool keep[RPT];
 #pragma unroll
-  for (int q = 0; q < RPT; q++) keep[q] = ok[q] && (uint32_t)link[r[q]] == r[q];
+  for (int q = 0; q < RPT; q++) {
+    const uint32_t p = ok[q] ? (uint32_t)link[r[q]] : 0u;
+    keep[q] = ok[q] && p == r[q];
+    if (curw && ok[q]) curw[r[q]] = p;   // (the parent as k_hook / k_chase_links left it: its CLOSED bit included)
+  }
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   unsigned long long bal[RPT];
   uint32_t mine = 0;
@@ -1124,7 +1176,8 @@ __global__ __launch_bounds__(NTHR) void k_compact_roots(const uint32_t *__restri
   if (lane == 0) wtot[wv] = mine;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const uint32_t tot = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    uint32_t tot = 0;
+    for (int k = 0; k < NT / 64; k++) tot += wtot[k];
     bbase = tot ? atomicAdd(counter, tot) : 0;
   }
   __syncthreads();
@@ -1137,6 +1190,103 @@ __global__ __launch_bounds__(NTHR) void k_compact_roots(const uint32_t *__restri
   }
   __syncthreads();   // (the next chunk of the block reuses wtot / bbase)
   }
+}
+__global__ __launch_bounds__(NTHR) void k_compact_roots(const uint32_t *__restrict__ roots_in, uint32_t nroots,
+                                                        const unsigned long long *__restrict__ link,
+                                                        uint32_t *roots_out, uint32_t *counter,
+                                                        const uint32_t *__restrict__ dyn = nullptr, uint32_t *curw = nullptr,
+                                                        TailGate gate = TailGate()) {
+  if (gate.taken()) return;
+  if (dyn) nroots = *dyn;
+  compact_roots_body<NTHR>(roots_in, nroots, link, roots_out, counter, curw, blockIdx.x, gridDim.x);
+}
+
+// The basins' final components and levels, once, after the last round (the compact-label fill; the other paths update
+// cur[] / acc[] in every round, k_update_basins).  link[r] of a root that died is never written again -- k_hook and
+// k_chase_links run over the live roots only -- so after the rounds link[] is the whole merge forest, each word carrying the
+// highest pass on its hop: cur[b] = the end of b's chain (a self-link or a closed parent), acc[b] = the highest pass on the
+// way, which is what the per-round updates accumulated.  A basin that never hooked (a frozen terminal, the outside) keeps
+// what k_init_tables wrote.  A chain has at most one hop per round with work; it is stored back shortened (any value ever
+// stored is a valid continuation: concurrent walkers and stale reads are harmless).
+__global__ __launch_bounds__(NTHR) void k_settle_basins(uint32_t *cur, uint32_t *acc, unsigned long long *link, uint32_t B,
+                                                        int maxhops, uint32_t *flag) {
+  const uint32_t b = blockIdx.x * NTHR + threadIdx.x;
+  if (b >= B) return;
+  const unsigned long long l = __hip_atomic_load(&link[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  uint32_t p = (uint32_t)l, m = (uint32_t)(l >> 32);
+  if (p == b) return;
+  const uint32_t p0 = p;
+  int hops = 0;
+  for (;;) {
+    if (p & CLOSED) break;
+    const unsigned long long lp = __hip_atomic_load(&link[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t pp = (uint32_t)lp;
+    if (pp == p) break;
+    const uint32_t mm = (uint32_t)(lp >> 32);
+    p = pp;
+    m = mm > m ? mm : m;
+    if (++hops >= maxhops) { *flag = 1; break; }
+  }
+  if (p != p0)
+    __hip_atomic_store(&link[b], ((unsigned long long)m << 32) | p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  cur[b] = p;
+  acc[b] = m;
+}
+
+// The small rounds of the compact-label fill in ONE launch: a single workgroup runs best_reset -> edge_round -> hook ->
+// chase -> compact round after round, __syncthreads() between the phases (no grid-wide barrier, no waiting on another
+// block), the root and record lists ping-ponging by the round's parity as on the host.  It takes over at the first round of
+// [rlo, rhi] whose gate holds (the full-width kernels of that round and of every later one have returned at once), runs until
+// no live root is left or round rmax is done, and leaves rc[4 r] / rc[4 r + 1] as the full-width kernels would, plus the
+// last round anybody ran in rc[2].  No gate holds: it does nothing, and the host enqueues more rounds.
+constexpr int TAILT = 1024;
+// Thresholds, measured at S3 (40000^2, 1.03e7 basins, ms per fill): 0 (no tail kernel) 15.37, 1024 roots 15.36, 4096 15.40,
+// 16384 15.50, 131072 18.0 -- one workgroup pays ~20 us a round in dependent round trips whatever the round's size, which is
+// what five launches of an almost empty round cost too, and it loses as soon as a round has more than a few chunks of records.
+constexpr uint32_t TAIL_ROOTS = 1024, TAIL_RECS_PER_ROOT = 8;   // take a round of <= 1024 roots and <= 8192 records
+struct TailArgs {
+  uint32_t *roots[2];   // round r reads roots[(r - 1) & 1]
+  uint32_t *el[2];      // round r >= 2 reads el[r & 1]: three arrays of pcap records
+  size_t pcap;
+  const uint32_t *segcount;   // round 2: the raster pass's segmented list
+  uint32_t segcap;
+  uint32_t *cur;
+  unsigned long long *best, *link;
+  uint32_t B;
+  uint32_t *rc, *flag;
+  uint32_t troots, trecs;
+  int rlo, rhi, rmax, maxhops;
+};
+__global__ __launch_bounds__(TAILT) void k_rounds_tail(TailArgs a) {
+  auto count = [&](int i) { return __hip_atomic_load(&a.rc[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+  int r = a.rlo;
+  for (; r <= a.rhi; r++)
+    if (count(4 * r) <= a.troots && count(4 * r + 1) <= a.trecs) break;
+  if (r > a.rhi) return;
+  for (; r <= a.rmax; r++) {
+    const uint32_t nr = count(4 * r), ne = count(4 * r + 1);
+    if (nr == 0) break;
+    const uint32_t *rin = a.roots[(r - 1) & 1];
+    uint32_t *rout = a.roots[r & 1];
+    const uint32_t *ei = a.el[r & 1];
+    uint32_t *eo = a.el[(r + 1) & 1];
+    best_reset_body<TAILT>(rin, nr, a.best, 0, 1);
+    __syncthreads();
+    if (r == 2)
+      edge_round_body<true, TAILT>(ei, ei + a.pcap, ei + 2 * a.pcap, (uint32_t)a.pcap, a.segcount, a.segcap, a.cur, a.best, a.B, eo,
+                                   eo + a.pcap, eo + 2 * a.pcap, &a.rc[4 * (r + 1) + 1], 0, 1);
+    else
+      edge_round_body<false, TAILT>(ei, ei + a.pcap, ei + 2 * a.pcap, ne, nullptr, 0u, a.cur, a.best, a.B, eo, eo + a.pcap,
+                                    eo + 2 * a.pcap, &a.rc[4 * (r + 1) + 1], 0, 1);
+    __syncthreads();
+    hook_body<TAILT>(rin, nr, a.best, a.link, 0, 1);
+    __syncthreads();
+    chase_links_body<TAILT>(rin, nr, a.link, a.maxhops, a.flag, 0, 1);
+    __syncthreads();
+    compact_roots_body<TAILT>(rin, nr, a.link, rout, &a.rc[4 * (r + 1)], a.cur, 0, 1);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) a.rc[2] = (uint32_t)(r - 1);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3055,12 +3205,33 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   const uint32_t gcap = 2048;   // blocks of a grid-stride launch: 8 per CU
   int rdone = 0;                // rounds enqueued so far
   uint32_t rounds_run = 0;
+  // r07: cur[] is kept for the round's roots only (k_compact_roots) and the basins are settled once after the rounds
+  // (k_settle_basins) -- k_update_basins rewrote all B entries of cur[] and acc[] in every enqueued round, 11 gather passes
+  // over 1e7 basins at S3 where one does.  And the small rounds are ONE launch: a round whose live roots and records are
+  // under the thresholds is k_rounds_tail's, with every round after it; the full-width kernels enqueued for it return at once.
+  uint32_t troots = TAIL_ROOTS;
+  if (const char *env_tail = getenv("RDGPU_FILL_TAIL_ROOTS")) troots = (uint32_t)std::min<unsigned long long>(strtoull(env_tail, nullptr, 10), 0xFFFFFFFFull);
+  const uint32_t trecs = (uint32_t)std::min<unsigned long long>((unsigned long long)troots * TAIL_RECS_PER_ROOT, 0xFFFFFFFFull);
+  uint32_t *const rootsP[2] = {rootsA, rootsB};   // round r reads rootsP[(r - 1) & 1] and leaves its survivors in the other
+  auto enqueue_tail = [&](int rlo, int rhi, int rmax) {
+    TailArgs ta;
+    ta.roots[0] = rootsP[0]; ta.roots[1] = rootsP[1];
+    ta.el[0] = elist[0]; ta.el[1] = elist[1];
+    ta.pcap = ecap; ta.segcount = segcount; ta.segcap = segcap;
+    ta.cur = cur; ta.best = best; ta.link = link; ta.B = B; ta.rc = rc; ta.flag = dflags;
+    ta.troots = troots; ta.trecs = trecs;
+    ta.rlo = std::max(2, rlo); ta.rhi = rhi; ta.rmax = rmax; ta.maxhops = 1 << 14;
+    RD_LAUNCH("fill.rounds_tail", k_rounds_tail, dim3(1), dim3(TAILT), 0, s, ta);
+  };
   auto enqueue_round = [&](int r) {   // r = 1, 2, ...
+    uint32_t *rootsA = rootsP[(r - 1) & 1], *rootsB = rootsP[r & 1];
+    TailGate gate;
+    if (troots && r >= 2) { gate.cnt = rc + 4 * r; gate.roots = troots; gate.recs = trecs; }
     const uint32_t bound = std::max(1u, r - 1 < 31 ? nroots0 >> (r - 1) : 1u);   // live roots at most halve... at least
     const uint32_t rgrid = std::min(gcap, cdiv(bound, NTHR));
     const uint32_t *nr = rc + 4 * r, *ne = rc + 4 * r + 1;
     uint32_t *nr_next = rc + 4 * (r + 1), *ne_next = rc + 4 * (r + 1) + 1;
-    RD_LAUNCH("fill.best_reset", k_best_reset, dim3(rgrid), dim3(NTHR), 0, s, rootsA, 0u, best, nr);
+    RD_LAUNCH("fill.best_reset", k_best_reset, dim3(rgrid), dim3(NTHR), 0, s, (const uint32_t *)rootsA, 0u, best, nr, gate);
     if (r == 1) {   // round 1: the one raster pass (components gathered from the node table)
       const uint32_t nwork = listed ? lists->n[1] : ntiles;
       if (nwork > 0)   // (none although basins exist cannot happen -- a pit is a wet cell; kept safe)
@@ -3069,7 +3240,8 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
                     (const uint32_t *)curN, best, w, h, B, tilesX, sl_, nwork, eo, (const uint32_t *)fo.tile_base,
                     (const uint32_t *)fo.tile_count, dtx, skip, (const uint32_t *)fo.edgeK, (const uint16_t *)fo.edgeS);
         });
-      RD_LAUNCH("fill.sum_segments", k_sum_segments, dim3(1), dim3(NTHR), 0, s, (const uint32_t *)eo.segcount, nseg, rc + 4 * 1 + 1);
+      RD_LAUNCH("fill.sum_segments", k_sum_segments, dim3(1), dim3(NTHR), 0, s, (const uint32_t *)eo.segcount, nseg, rc + 4 * 1 + 1,
+                rc + 4 * 2 + 1);   // (and where round 2's gate reads it)
       g_stats.scan_tiles += ntiles;
     } else {
       const int eout = ein ^ 1;
@@ -3077,22 +3249,23 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
       uint32_t *oa = elist[eout], *ob = elist[eout] + pcap[eout], *ok = elist[eout] + 2 * pcap[eout];
       if (eseg)   // round 2 reads the segmented list of the raster pass: the segments' fill counts are on the device
         RD_LAUNCH("fill.edge_round", (k_edge_round<true>), dim3(std::min<uint32_t>(4 * gcap, cdiv(ecap, NTHR * EPT))), dim3(NTHR), 0,
-                  s, ia, ib, ik, (uint32_t)ecap, (const uint32_t *)segcount, segcap, (const uint32_t *)cur, best, B, oa, ob, ok, ne_next);
+                  s, ia, ib, ik, (uint32_t)ecap, (const uint32_t *)segcount, segcap, (const uint32_t *)cur, best, B, oa, ob, ok, ne_next,
+                  (const uint32_t *)nullptr, gate);
       else
         RD_LAUNCH("fill.edge_round", (k_edge_round<false>), dim3(gcap), dim3(NTHR), 0, s, ia, ib, ik, 0u,
-                  (const uint32_t *)nullptr, 0u, (const uint32_t *)cur, best, B, oa, ob, ok, ne_next, ne);
+                  (const uint32_t *)nullptr, 0u, (const uint32_t *)cur, best, B, oa, ob, ok, ne_next, ne, gate);
       eseg = false;
       ein = eout;
     }
-    RD_LAUNCH("fill.hook", k_hook, dim3(rgrid), dim3(NTHR), 0, s, rootsA, 0u, best, link, nr);
+    RD_LAUNCH("fill.hook", k_hook, dim3(rgrid), dim3(NTHR), 0, s, (const uint32_t *)rootsA, 0u, (const unsigned long long *)best, link, nr,
+              gate);
     // One pass: a thread follows its chain of hooks for up to 16384 steps (the chains of a round are a handful of hooks
     // long).  "A chain was left unfinished" stays in dflags[0] for the read-back after the batch and sends the raster to
     // the classic path, whose loop repeats the pass: nothing has been written to the DEM yet.
-    RD_LAUNCH("fill.chase_links", k_chase_links, dim3(rgrid), dim3(NTHR), 0, s, rootsA, 0u, link, 1 << 14, dflags, nr);
-    RD_LAUNCH("fill.update_basins", k_update_basins, dim3(cdiv(B, NTHR)), dim3(NTHR), 0, s, cur, acc, link, B, nr);
-    RD_LAUNCH("fill.compact_roots", k_compact_roots, dim3(std::min(gcap, cdiv(bound, NTHR * RPT))), dim3(NTHR), 0, s, rootsA, 0u, link,
-              rootsB, nr_next, nr);
-    std::swap(rootsA, rootsB);
+    RD_LAUNCH("fill.chase_links", k_chase_links, dim3(rgrid), dim3(NTHR), 0, s, (const uint32_t *)rootsA, 0u, link, 1 << 14, dflags,
+              nr, gate);
+    RD_LAUNCH("fill.compact_roots", k_compact_roots, dim3(std::min(gcap, cdiv(bound, NTHR * RPT))), dim3(NTHR), 0, s,
+              (const uint32_t *)rootsA, 0u, (const unsigned long long *)link, rootsB, nr_next, nr, cur, gate);
   };
   // round 1 writes the records' total where round 2 expects it
   // (k_sum_segments above: rc[4 * 1 + 1] is unused by round 1 itself; round 2 reads the segmented list and needs no count)
@@ -3101,11 +3274,22 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
     uint32_t lg = 0;
     while ((1ull << lg) < (unsigned long long)nroots0 + 1ull) lg++;
     int batch = std::min(MAXR, std::max(4, (int)(2 * lg + 4) / 5 + 1));   // ~log5.7(roots) + 1: S3 enqueues 11, runs 9
+    if (troots) {
+      // full-width rounds up to the first whose roots are under the threshold if they shrink by 4 a round (measured: 4 - 9),
+      // that one included as a margin; the tail kernel takes over wherever the counts on the device say, or not at all --
+      // then the fill is not finished after the batch and enqueues more, as before
+      int r4 = 2;
+      while (r4 < batch && (2 * (r4 - 1) < 32 ? nroots0 >> (2 * (r4 - 1)) : 0u) > troots) r4++;
+      batch = std::min(batch, r4);
+    }
     const char *env_batch = getenv("RDGPU_FILL_ROUND_BATCH");
     if (env_batch) batch = std::min(MAXR, std::max(1, atoi(env_batch)));   // (tests: several batches)
     uint32_t last_live = 0xFFFFFFFFu;
     for (;;) {
+      const int rfirst = rdone + 1;
       for (int k = 0; k < batch && rdone < MAXR; k++) enqueue_round(++rdone);
+      // (with RDGPU_FILL_ROUND_BATCH a batch stays a batch: the tail kernel runs the rounds enqueued for it and no more)
+      if (troots) enqueue_tail(rfirst, env_batch ? rdone : std::min(rdone + 1, MAXR), env_batch ? rdone : MAXR);
       RD_HIP(hipMemcpyAsync(hrc, rc, 4 * (MAXR + 2) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
       RD_HIP(hipMemcpyAsync(hw, dflags, 14 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
       RD_HIP(hipStreamSynchronize(s));
@@ -3119,6 +3303,7 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
       // chain of ~10^8 basins, or a grid whose blocks run one after the other from the chain's far end -- timing, not input.
       if (hw[0] != 0) { if (getenv("RDGPU_FILL_DEBUG")) fprintf(stderr, "fill_fused: hook chain unfinished\n"); return false; }
       if (hw[5] != 0) { if (getenv("RDGPU_FILL_DEBUG")) fprintf(stderr, "fill_fused: pair list overflow (B %u cap %llu nseg %u segcap %u nwork %u)\n", B, (unsigned long long)cap, nseg, segcap, nwork1); return false; }   // the pair list overflowed: the DEM is untouched, the classic path takes over
+      if ((int)hrc[2] > rdone) rdone = std::min<int>(hrc[2], MAXR);   // (rounds the tail kernel ran past the enqueued ones)
       rounds_run = 0;
       for (int r = 1; r <= rdone; r++) rounds_run += hrc[4 * r] != 0;
       g_stats.edge_records = hrc[4 + 1];
@@ -3130,6 +3315,7 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
     }
   }
   g_stats.rounds += rounds_run;
+  RD_LAUNCH("fill.settle_basins", k_settle_basins, dim3(cdiv(B, NTHR)), dim3(NTHR), 0, s, cur, acc, link, B, 1 << 14, dflags);
   uint32_t *lvl = fo.G;   // (the node table is dead: its storage holds the nodes' levels)
   RD_LAUNCH("fill.node_levels", k_node_levels, ngrid, dim3(NTHR), 0, s, (const uint32_t *)curN, (const uint32_t *)acc,
             (const unsigned long long *)fo.counters, fo.rcap, lvl);

@@ -636,6 +636,49 @@ def fa_tarboton_dev(dem, nodata, accum) -> None:
                                                        ctypes.c_void_p(accum.data_ptr()), _stream_ptr()), "rdgpu_fa_tarboton_dev")
 
 
+def flow_accumulation_rounds() -> int:
+    """Launches of the work-list kernels (k_mfd_round / k_mfd_stack, csrc/mfd.hip) in the last generic accumulation --
+    FlowAccumFromProps, FA_Tarboton, FA_Holmgren / Freeman / Quinn / D4 and their _dev forms (rdgpu_flow_accumulation_rounds)."""
+    r = ctypes.c_uint32()
+    check(lib().rdgpu_flow_accumulation_rounds(ctypes.byref(r)), "rdgpu_flow_accumulation_rounds")
+    return int(r.value)
+
+
+def flow_accumulation_dev(props9, accum) -> None:
+    """FlowAccumulation(Array3D<float>, Array2D<double>) (methods/flow_accumulation_generic.hpp:33-100): accum (float64 CUDA
+    tensor [h, w], in: the cells' weights, out: the accumulation) from the float32 CUDA proportions tensor [h, w, 9], on
+    torch's current stream."""
+    import torch
+
+    if not (props9.is_cuda and props9.dim() == 3 and props9.shape[2] == 9 and props9.is_contiguous()
+            and props9.dtype == torch.float32):
+        raise RdgpuError("flow_accumulation_dev: props9 must be a contiguous float32 CUDA tensor [h, w, 9]")
+    h, w = int(props9.shape[0]), int(props9.shape[1])
+    if accum.dtype != torch.float64 or tuple(accum.shape) != (h, w) or not accum.is_contiguous() or not accum.is_cuda:
+        raise RdgpuError("flow_accumulation_dev: accum must be a contiguous float64 CUDA tensor of the proportions' shape")
+    check(lib().rdgpu_flow_accumulation_dev_f64(ctypes.c_void_p(props9.data_ptr()), w, h, ctypes.c_void_p(accum.data_ptr()),
+                                                _stream_ptr()), "rdgpu_flow_accumulation_dev_f64")
+
+
+def fa_mfd_dev(dem, nodata, method, accum, exponent=None) -> None:
+    """FA_Holmgren / FA_Freeman / FA_Quinn / FA_D4 (methods/flow_accumulation.hpp:18-20,28): accum (float64 CUDA tensor, in:
+    the cells' weights, out: the accumulation) from the DEM, on torch's current stream."""
+    import torch
+
+    kind, code, xp = _method("fa_mfd_dev", method, exponent)
+    if kind != "mfd":
+        raise RdgpuError("fa_mfd_dev: method must be Holmgren, Freeman, Quinn or D4 (D8: fa_d8_dev, Dinf: fa_tarboton_dev)")
+    h, w = _dev2d(dem, "fa_mfd_dev")
+    if accum.dtype != torch.float64 or tuple(accum.shape) != (h, w) or not accum.is_contiguous() or not accum.is_cuda:
+        raise RdgpuError("fa_mfd_dev: accum must be a contiguous float64 CUDA tensor of the DEM's shape")
+    s = _torch_elev_suffix(dem)
+    if s not in _MFD_SUFFIX.values():
+        raise RdgpuError(f"fa_mfd_dev: unsupported elevation dtype {dem.dtype}")
+    check(getattr(lib(), f"rdgpu_fa_mfd_dev_{s}")(ctypes.c_void_p(dem.data_ptr()), _scalar(s, nodata), w, h, code,
+                                                  ctypes.c_double(xp), ctypes.c_void_p(accum.data_ptr()), _stream_ptr()),
+          "rdgpu_fa_mfd_dev")
+
+
 class _MaxDepStats(ctypes.Structure):
     _fields_ = [("pockets", ctypes.c_uint64), ("tie_pockets", ctypes.c_uint64), ("tie_cluster_cells", ctypes.c_uint64),
                 ("pocket_cells", ctypes.c_uint64)]

@@ -820,6 +820,54 @@ int rdgpu_d8_upslope_cells_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int wi
                                uint8_t *d_out, void *hip_stream);
 int rdgpu_d8_upslope_line(int width, int height, int x0, int y0, int x1, int y1, uint32_t *cells, uint32_t capacity, uint32_t *n);
 
+/* ---- channel network and Strahler stream order on the D8 direction forest ---------------------
+ * No reference counterpart (include/richdem/methods/strahler.hpp is a commented-out draft).  Directions are uint8 D8
+ * codes (0 NO_FLOW, 1..8, dir_nodata); chan is an optional channel mask (uint8, non-zero = channel), and chan == NULL
+ * means every cell whose direction is not dir_nodata is a channel.
+ *   A CHANNEL CELL is a cell with chan != 0 and dirs != dir_nodata.  The CHANNEL CHILDREN of v are the channel cells
+ *   among its eight neighbours whose direction 1..8 points at v.
+ *   order(v) = 1                 for a channel cell without channel children,
+ *            = m + 1 or m        for any other channel cell, m being the largest order among its children: m + 1 if at
+ *                                least two children have order m (three equal children give m + 1, not m + 2), else m,
+ *            = 0                 for a cell that is no channel cell, NoData cells included,
+ *            = 255               for a channel cell on a direction loop, or downstream of one: its order has no finite
+ *                                derivation.  (A cell has one target, so what lies downstream of a loop lies on it; the
+ *                                channel cells that drain INTO a loop are ordinary trees and get finite orders.)
+ *   The mask need not be closed downstream: a channel cell whose target is no channel cell, lies off the raster, or
+ *   whose code is not 1..8 simply ends its tree.  An order k needs 2^(k-1) heads, so no order above 32 (let alone 254)
+ *   can occur on a raster the engine accepts.  Exact.
+ *   rdgpu_d8_channels_f64   chan = (accum != accum_nodata && accum >= threshold) ? 1 : 0; a threshold that is not
+ *                           finite is RDGPU_ERR_ARG.
+ *   rdgpu_d8_stream_links   classifies every channel cell from one 3 x 3 pass over dirs, chan and order; the kinds are
+ *                           exclusive, the first that applies in the order of enum rdgpu_stream_kind; 0 on cells that
+ *                           are no channel cells.
+ *   rdgpu_d8_stream_order_get_stats   of the calling thread's last stream-order call: the levels and the node rounds
+ *                           per level it ENQUEUED (bounds fixed by the raster's size; what has nothing to do returns
+ *                           at once on the device), and its number of kernel launches.
+ * A null pointer other than chan, a non-positive size or more cells than the engine accepts (0xFFFF0000) returns
+ * RDGPU_ERR_ARG before any device work; nothing is written then.  The _dev forms take device pointers and are ordered
+ * on hip_stream without synchronising it.  Scratch (13 bytes per 16 cells) comes from the workspace pool. */
+enum rdgpu_stream_kind {
+  RDGPU_STREAM_NONE = 0,       /* no channel cell */
+  RDGPU_STREAM_HEAD = 1,       /* no channel child */
+  RDGPU_STREAM_JUNCTION = 2,   /* at least two channel children */
+  RDGPU_STREAM_ORDER_STEP = 3, /* one channel child of another order: cannot occur by the definition, an assertion value */
+  RDGPU_STREAM_MOUTH = 4,      /* its target is no channel cell */
+  RDGPU_STREAM_PLAIN = 5
+};
+int rdgpu_d8_stream_order(const uint8_t *dirs, uint8_t dir_nodata, int width, int height, const uint8_t *chan /* nullable */,
+                          uint8_t *order);
+int rdgpu_d8_stream_order_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int width, int height,
+                              const uint8_t *d_chan /* nullable */, uint8_t *d_order, void *hip_stream);
+int rdgpu_d8_stream_order_get_stats(int *levels, int *rounds_per_level, int *launches);
+int rdgpu_d8_channels_f64(const double *accum, double accum_nodata, double threshold, int width, int height, uint8_t *chan);
+int rdgpu_d8_channels_dev_f64(const double *d_accum, double accum_nodata, double threshold, int width, int height,
+                              uint8_t *d_chan, void *hip_stream);
+int rdgpu_d8_stream_links(const uint8_t *dirs, uint8_t dir_nodata, int width, int height, const uint8_t *chan /* nullable */,
+                          const uint8_t *order, uint8_t *kind);
+int rdgpu_d8_stream_links_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int width, int height,
+                              const uint8_t *d_chan /* nullable */, const uint8_t *d_order, uint8_t *d_kind, void *hip_stream);
+
 /* ---- synthetic input (test/bench input generator) ----------- */
 int rdgpu_synth_dem_dev_f32(float *d_dem, int width, int height, int seed, int x0, int y0,
                             float tilt, void *hip_stream);

@@ -457,6 +457,49 @@ void d8_outlets(const F &flowdirs, G &out) {
   detail::check(rdgpu_d8_outlets(flowdirs.data(), flowdirs.noData(), flowdirs.width(), flowdirs.height(), out.data()), "d8_outlets");
 }
 
+// ---- channel network, Strahler stream order (no reference counterpart; the definition is in rdgpu.h) ----------------
+// chan <- 1 where accum is not its NoData and accum >= threshold, 0 elsewhere
+template <class A, class G>
+void d8_channels(const A &accum, double threshold, G &chan) {
+  static_assert(std::is_same<detail::elem_t<const A>, double>::value || std::is_same<detail::elem_t<A>, double>::value,
+                "d8_channels: the accumulation must be double");
+  static_assert(std::is_same<detail::elem_t<G>, uint8_t>::value, "d8_channels: the channel mask must be uint8_t");
+  chan.resize(accum);
+  chan.setNoData(0);
+  if (accum.width() == 0 || accum.height() == 0) return;
+  detail::check(rdgpu_d8_channels_f64(accum.data(), accum.noData(), threshold, accum.width(), accum.height(), chan.data()),
+                "d8_channels");
+}
+
+// order <- the Strahler order of every channel cell, 0 (the output's NoData) off the channels, 255 on direction loops
+template <class F, class C, class G>
+void d8_stream_order(const F &flowdirs, const C &chan, G &order) {
+  static_assert(std::is_same<detail::elem_t<const F>, uint8_t>::value || std::is_same<detail::elem_t<F>, uint8_t>::value,
+                "d8_stream_order: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<detail::elem_t<const C>, uint8_t>::value || std::is_same<detail::elem_t<C>, uint8_t>::value,
+                "d8_stream_order: the channel mask must be uint8_t");
+  static_assert(std::is_same<detail::elem_t<G>, uint8_t>::value, "d8_stream_order: the order raster must be uint8_t");
+  if (chan.width() != flowdirs.width() || chan.height() != flowdirs.height())
+    throw std::runtime_error("d8_stream_order: the channel mask must have the directions' size");
+  order.resize(flowdirs);
+  order.setNoData(0);
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  detail::check(rdgpu_d8_stream_order(flowdirs.data(), flowdirs.noData(), flowdirs.width(), flowdirs.height(), chan.data(),
+                                      order.data()), "d8_stream_order");
+}
+// every cell with a direction is a channel
+template <class F, class G>
+void d8_stream_order(const F &flowdirs, G &order) {
+  static_assert(std::is_same<detail::elem_t<const F>, uint8_t>::value || std::is_same<detail::elem_t<F>, uint8_t>::value,
+                "d8_stream_order: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<detail::elem_t<G>, uint8_t>::value, "d8_stream_order: the order raster must be uint8_t");
+  order.resize(flowdirs);
+  order.setNoData(0);
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  detail::check(rdgpu_d8_stream_order(flowdirs.data(), flowdirs.noData(), flowdirs.width(), flowdirs.height(), nullptr,
+                                      order.data()), "d8_stream_order");
+}
+
 // richdem::FA_D8(const Array2D<elev_t>&, Array2D<accum_t>&)   methods/flow_accumulation.hpp:27
 // accum is in/out: pre-loaded with the flow each cell generates.
 template <class E, class G>

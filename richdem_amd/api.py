@@ -1037,3 +1037,108 @@ def d8_outlets_dev(dirs, out, nodata: int = 255) -> None:
         raise RdgpuError("d8_outlets_dev: shape mismatch")
     check(lib().rdgpu_d8_outlets_dev(ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(nodata), w, h,
                                      ctypes.c_void_p(out.data_ptr()), _stream_ptr()), "rdgpu_d8_outlets_dev")
+
+
+# ---- channel network and Strahler stream order (csrc/streams.hip) ----------------------------
+STREAM_KINDS = {"none": 0, "head": 1, "junction": 2, "order_step": 3, "mouth": 4, "plain": 5}
+
+
+def _mask2d(mask, shape, who):
+    if mask is None:
+        return None
+    if not isinstance(mask, np.ndarray) or mask.dtype != np.uint8 or mask.shape != tuple(shape):
+        raise RdgpuError(f"{who}: the channel mask is a uint8 array of the directions' shape")
+    return np.ascontiguousarray(mask)
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def d8_channels(accum: np.ndarray, threshold: float, accum_nodata: float = -1.0) -> np.ndarray:
+    """uint8 mask: 1 where accum is not accum_nodata and accum >= threshold (float64 accumulation, as d8_flow_accum's)."""
+    if not isinstance(accum, np.ndarray) or accum.ndim != 2 or accum.dtype != np.float64:
+        raise RdgpuError("d8_channels: expected a 2-D float64 accumulation raster")
+    accum = np.ascontiguousarray(accum)
+    h, w = accum.shape
+    out = np.empty((h, w), np.uint8)
+    check(lib().rdgpu_d8_channels_f64(_ptr(accum), ctypes.c_double(accum_nodata), ctypes.c_double(threshold), w, h, _ptr(out)),
+          "rdgpu_d8_channels_f64")
+    return out
+
+
+def d8_stream_order(dirs: np.ndarray, dir_nodata: int = 255, channels: np.ndarray | None = None) -> np.ndarray:
+    """uint8 raster: the Strahler order of every channel cell (channels=None: every cell with a direction), 0 elsewhere,
+    255 on the cells of a direction loop (include/rdgpu.h states the definition)."""
+    dirs = _dirs2d(dirs, "d8_stream_order")
+    chan = _mask2d(channels, dirs.shape, "d8_stream_order")
+    h, w = dirs.shape
+    out = np.empty((h, w), np.uint8)
+    check(lib().rdgpu_d8_stream_order(_ptr(dirs), ctypes.c_uint8(dir_nodata), w, h, _ptr(chan), _ptr(out)), "rdgpu_d8_stream_order")
+    return out
+
+
+def d8_stream_links(dirs: np.ndarray, order: np.ndarray, dir_nodata: int = 255, channels: np.ndarray | None = None) -> np.ndarray:
+    """uint8 raster of STREAM_KINDS: head, junction, order step (never, by the definition), mouth, plain; 0 off the channels."""
+    dirs = _dirs2d(dirs, "d8_stream_links")
+    chan = _mask2d(channels, dirs.shape, "d8_stream_links")
+    order = _mask2d(order, dirs.shape, "d8_stream_links")
+    if order is None:
+        raise RdgpuError("d8_stream_links: the order raster is required")
+    h, w = dirs.shape
+    out = np.empty((h, w), np.uint8)
+    check(lib().rdgpu_d8_stream_links(_ptr(dirs), ctypes.c_uint8(dir_nodata), w, h, _ptr(chan), _ptr(order), _ptr(out)),
+          "rdgpu_d8_stream_links")
+    return out
+
+
+def d8_stream_order_stats() -> dict:
+    """of this thread's last stream-order call: levels and node rounds per level enqueued, kernel launches"""
+    v = [ctypes.c_int(0) for _ in range(3)]
+    check(lib().rdgpu_d8_stream_order_get_stats(*[ctypes.byref(x) for x in v]), "rdgpu_d8_stream_order_get_stats")
+    return {"levels": v[0].value, "rounds_per_level": v[1].value, "launches": v[2].value}
+
+
+def _dev_mask(t, shape, who):
+    import torch
+
+    if t is None:
+        return None
+    if _dev2d(t, who, torch.uint8) != shape:
+        raise RdgpuError(f"{who}: shape mismatch")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def d8_channels_dev(accum, threshold: float, out, accum_nodata: float = -1.0) -> None:
+    """out (uint8 CUDA tensor) <- the channel mask of a float64 CUDA accumulation, on torch's current stream."""
+    import torch
+
+    h, w = _dev2d(accum, "d8_channels_dev", torch.float64)
+    if _dev2d(out, "d8_channels_dev", torch.uint8) != (h, w):
+        raise RdgpuError("d8_channels_dev: shape mismatch")
+    check(lib().rdgpu_d8_channels_dev_f64(ctypes.c_void_p(accum.data_ptr()), ctypes.c_double(accum_nodata), ctypes.c_double(threshold),
+                                          w, h, ctypes.c_void_p(out.data_ptr()), _stream_ptr()), "rdgpu_d8_channels_dev_f64")
+
+
+def d8_stream_order_dev(dirs, out, dir_nodata: int = 255, channels=None) -> None:
+    """out (uint8 CUDA tensor) <- the stream order of dirs (uint8 CUDA tensor), channels an optional uint8 CUDA mask."""
+    import torch
+
+    h, w = _dev2d(dirs, "d8_stream_order_dev", torch.uint8)
+    if _dev2d(out, "d8_stream_order_dev", torch.uint8) != (h, w):
+        raise RdgpuError("d8_stream_order_dev: shape mismatch")
+    check(lib().rdgpu_d8_stream_order_dev(ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata), w, h,
+                                          _dev_mask(channels, (h, w), "d8_stream_order_dev"), ctypes.c_void_p(out.data_ptr()),
+                                          _stream_ptr()), "rdgpu_d8_stream_order_dev")
+
+
+def d8_stream_links_dev(dirs, order, out, dir_nodata: int = 255, channels=None) -> None:
+    """out (uint8 CUDA tensor) <- the kinds of the channel cells of dirs / channels / order (uint8 CUDA tensors)."""
+    import torch
+
+    h, w = _dev2d(dirs, "d8_stream_links_dev", torch.uint8)
+    if _dev2d(out, "d8_stream_links_dev", torch.uint8) != (h, w) or _dev2d(order, "d8_stream_links_dev", torch.uint8) != (h, w):
+        raise RdgpuError("d8_stream_links_dev: shape mismatch")
+    check(lib().rdgpu_d8_stream_links_dev(ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata), w, h,
+                                          _dev_mask(channels, (h, w), "d8_stream_links_dev"), ctypes.c_void_p(order.data_ptr()),
+                                          ctypes.c_void_p(out.data_ptr()), _stream_ptr()), "rdgpu_d8_stream_links_dev")

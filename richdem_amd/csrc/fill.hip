@@ -2092,11 +2092,12 @@ static void fill_max_dep_host(T *dem, int w, int h, int topology, uint64_t max_d
 //                    cell draining off the raster, a cell whose descent neighbour lies outside the tile -- becomes a
 //                    NODE: local slot 0.., global id tile_base + slot, G[node] = basin id | PEND | first cell outside
 //                    the tile | OUTP.  A cell's label is the SLOT of its root: 2 bytes per cell (lab16).
-//   k_resolve_nodes  node -> basin (curN): a pending node follows lab16 / G from tile to tile.  A table pass over ~2 % of
-//                    the cell count replaces k_tile_label's raster pass (10.7 GB at S3).
+//   k_resolve_nodes  node -> basin (curN): a pending node follows the tiles' edge records / G from tile to tile.  A table
+//                    pass over ~2 % of the cell count replaces k_tile_label's raster pass (10.7 GB at S3).
 //   k_pairs16        the one pair pass, reading z + lab16 (6 B / cell) and taking the components from curN.
 //   rounds           unchanged (pair list).
-//   k_finalize16     z <- max(z, level of the cell's node): z + lab16 and the tile's node levels from LDS.
+//   k_finalize16     z <- max(z, level of the cell's node): z + lab16 and the tile's node levels from LDS, formed from curN
+//                    and the basins' levels as they are staged (the shards keep a table of them: k_node_levels).
 // (Tried first and dropped: the pairs in the descent kernel itself, on slots, with the pairs across tile edges from edge
 // strips -- correct, but slot boundaries are several times as many as basin boundaries, since every exit of a tile is a
 // slot of its own until it is resolved: 22 ms for the kernel, 80 M records; profiles/r03h_fill_fused_ab.json.)
@@ -2121,6 +2122,10 @@ struct FusedBuf {
   // for one cell (12.5 GB per pass at S3 once the neighbouring tile's rows are no longer in L2; r04a counters)
   uint32_t *edgeK = nullptr;
   uint16_t *edgeS = nullptr;
+  // the first and last ROW of every descent tile, slots only, [tile][top / bottom][column].  With the columns' slots these
+  // are every label the node chase can ask for (k_resolve_nodes: a pending node names a cell on the outer ring of a
+  // neighbouring tile): two 128-byte lines per tile side instead of one sector of the 2-byte raster per hop
+  uint16_t *edgeR = nullptr;
 };
 
 // after the descent: dense basin ids.  out[0] = basins, out[1] = nodes in use, out[2] = the fullest stripe's node count
@@ -2421,6 +2426,15 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
       const bool in = x0 + lxe < w && y0 + lye < h;
       fo.edgeS[((size_t)t * 2 + side) * DH + lye] = in ? *reinterpret_cast<const uint16_t *>(sl + v) : (uint16_t)0;
     }
+    // the tile's first and last ROW likewise, for the node chase (k_resolve_nodes): the other two wavefronts, one column
+    // per lane.  No keys go with them: the pair pass reads its ring rows from the raster, coalesced.
+    if (fo.edgeR && threadIdx.x >= 2 * DH) {
+      static_assert(NTHR == 2 * DH + 2 * DW, "two wavefronts for the columns, two for the rows");
+      const int side = (threadIdx.x >> 6) & 1, lxe = threadIdx.x & (DW - 1), lye = side ? DH - 1 : 0;
+      const uint16_t v = lp[lye * LPD + lxe];
+      const bool in = x0 + lxe < w && y0 + lye < h;
+      fo.edgeR[((size_t)t * 2 + side) * DW + lxe] = in ? *reinterpret_cast<const uint16_t *>(sl + v) : (uint16_t)0;
+    }
   }
 }
 
@@ -2430,12 +2444,22 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
 // being that of the node the word was found in.  A chain of several hops is shortened for the others: the node's word
 // becomes the last cell of the chain (any value ever stored in G is a valid continuation: concurrent chasers and stale
 // reads are harmless).  grid: (nodes of the fullest stripe, stripes).
+// edgeS / edgeR (optional, both or none): the label of the cell comes from the edge records of its tile instead of the
+// raster.  That is complete because every value ever stored in G with LAB_PEND is the first cell outside some tile on a
+// descent path -- the words of the descent kernel by construction, the shortened words `LAB_PEND | last` because `last`
+// was itself the target of a hop -- and such a cell lies on the outer ring of its own tile: its first or last column
+// (edgeS), its first or last row (edgeR), a corner in both.  A tile's nodes point into the edges of its 8 neighbours, so
+// the records are read with locality where the raster gave a sector per 2-byte label.  (A cell on no edge cannot occur;
+// it takes the raster's label all the same.)  Without records -- the fills with outlets, whose skipped tiles write
+// none -- every label comes from lab16.
 __global__ __launch_bounds__(NTHR) void k_resolve_nodes(uint32_t *G, const unsigned long long *__restrict__ counters,
                                                         const uint32_t *__restrict__ pitoff, uint32_t rcap,
                                                         const uint16_t *__restrict__ lab16,
                                                         const uint32_t *__restrict__ tile_base, int w, uint32_t tilesX,
                                                         uint32_t B, uint32_t *curN, uint32_t *flag,
-                                                        const uint32_t *__restrict__ tid = nullptr) {
+                                                        const uint32_t *__restrict__ tid = nullptr,
+                                                        const uint16_t *__restrict__ edgeS = nullptr,
+                                                        const uint16_t *__restrict__ edgeR = nullptr) {
   const uint32_t st = blockIdx.y, i = blockIdx.x * NTHR + threadIdx.x;
   if (i >= (uint32_t)(counters[st * FSTRIDE] >> 32)) return;
   const uint32_t n = st * rcap + i;
@@ -2444,7 +2468,14 @@ __global__ __launch_bounds__(NTHR) void k_resolve_nodes(uint32_t *G, const unsig
   while ((v & LAB_PEND) && v != OUTP) {
     const uint32_t cell = v & ~LAB_PEND;
     const uint32_t cx = cell % (uint32_t)w, cy = cell / (uint32_t)w;
-    fn = tile_base[(cy / DH) * tilesX + cx / DW] + lab16[cell];
+    const uint32_t tile = (cy / DH) * tilesX + cx / DW;
+    const uint32_t lx = cx % DW, ly = cy % DH;
+    const uint16_t *src = lab16 + cell;
+    if (edgeS) {
+      if (lx == 0u || lx == (uint32_t)(DW - 1)) src = edgeS + ((size_t)tile * 2 + (lx != 0u)) * DH + ly;
+      else if (ly == 0u || ly == (uint32_t)(DH - 1)) src = edgeR + ((size_t)tile * 2 + (ly != 0u)) * DW + lx;
+    }
+    fn = tile_base[tile] + *src;
     last = cell;
     v = __hip_atomic_load(&G[fn], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (++hops > (1 << 22)) { *flag = 1; break; }   // (cannot happen: descent paths are loop free)
@@ -2572,12 +2603,16 @@ __global__ __launch_bounds__(NTHR) void k_node_levels(const uint32_t *__restrict
 
 // z <- max(z, level of the cell's node).  One block per descent tile: its node levels (<= 4096) in LDS, then z and the
 // 16-bit labels in quads; a quad is written back only when one of its cells is raised.
+// curN / acc (optional, both or none; lvl is not read then): the kernel forms the levels itself, level of a node = acc[its
+// basin], while it stages them -- the table pass that wrote lvl[] for this one reader (k_node_levels) is not needed.
 template <class T, bool VEC>
 __global__ __launch_bounds__(NTHR) void k_finalize16(T *z, const uint16_t *__restrict__ lab16, const uint32_t *__restrict__ lvl,
                                                      const uint32_t *__restrict__ tile_base, const uint32_t *__restrict__ tile_count,
                                                      int w, int h, uint32_t tilesX, uint32_t ntiles,
                                                      const uint8_t *__restrict__ skip = nullptr,
-                                                     const uint32_t *__restrict__ tlist = nullptr) {
+                                                     const uint32_t *__restrict__ tlist = nullptr,
+                                                     const uint32_t *__restrict__ curN = nullptr,
+                                                     const uint32_t *__restrict__ acc = nullptr) {
   __shared__ uint32_t sl[DH * DW];
   const uint32_t t = tlist ? tlist[blockIdx.x] : xcd_tile(blockIdx.x, ntiles);
   if (t >= ntiles) return;
@@ -2597,7 +2632,11 @@ __global__ __launch_bounds__(NTHR) void k_finalize16(T *z, const uint16_t *__res
     lqs[r] = load_quad<uint16_t, VEC>(lab16 + (g - (in ? gx : 0)), in ? gx : 0, w, (uint16_t)0);
   }
   const uint32_t base = tile_base[t], cnt = tile_count[t];
-  for (uint32_t i = threadIdx.x; i < cnt; i += NTHR) sl[i] = lvl[base + i];
+  if (curN) {
+    for (uint32_t i = threadIdx.x; i < cnt; i += NTHR) sl[i] = acc[curN[base + i] & ~CLOSED];
+  } else {
+    for (uint32_t i = threadIdx.x; i < cnt; i += NTHR) sl[i] = lvl[base + i];
+  }
   __syncthreads();
 #pragma unroll
   for (int r = 0; r < DH / 16; r++) {
@@ -3098,6 +3137,7 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   if (!outlet) {   // (with outlets, tiles are skipped: their records would be stale)
     fo.edgeK = ws.buf<uint32_t>("fused.edgeK", (size_t)dnt * 2 * DH);
     fo.edgeS = ws.buf<uint16_t>("fused.edgeS", (size_t)dnt * 2 * DH);
+    fo.edgeR = ws.buf<uint16_t>("fused.edgeR", (size_t)dnt * 2 * DW);
   }
   RD_HIP(hipMemsetAsync(dflags, 0, 16 * sizeof(uint32_t), s));
   RD_HIP(hipMemsetAsync(fo.counters, 0, (size_t)FSTRIPES * FSTRIDE * sizeof(unsigned long long), s));
@@ -3145,7 +3185,7 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   }
   RD_LAUNCH("fill.resolve_nodes", k_resolve_nodes, ngrid, dim3(NTHR), 0, s, fo.G, (const unsigned long long *)fo.counters,
             (const uint32_t *)pitoff, fo.rcap, (const uint16_t *)fo.lab16, (const uint32_t *)fo.tile_base, w, dtx, B, curN, dflags,
-            (const uint32_t *)tid);
+            (const uint32_t *)tid, (const uint16_t *)fo.edgeS, (const uint16_t *)fo.edgeR);
   g_stats.jump_passes = 1;
   uint32_t *cur = sharded ? alloc->get<uint32_t>("fill.cur", (size_t)B + 1) : ws.buf<uint32_t>("fill.cur", (size_t)B + 1);
   uint32_t *acc = sharded ? alloc->get<uint32_t>("fill.acc", (size_t)B + 1) : ws.buf<uint32_t>("fill.acc", (size_t)B + 1);
@@ -3316,10 +3356,10 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   }
   g_stats.rounds += rounds_run;
   RD_LAUNCH("fill.settle_basins", k_settle_basins, dim3(cdiv(B, NTHR)), dim3(NTHR), 0, s, cur, acc, link, B, 1 << 14, dflags);
-  uint32_t *lvl = fo.G;   // (the node table is dead: its storage holds the nodes' levels)
-  RD_LAUNCH("fill.node_levels", k_node_levels, ngrid, dim3(NTHR), 0, s, (const uint32_t *)curN, (const uint32_t *)acc,
-            (const unsigned long long *)fo.counters, fo.rcap, lvl);
-  if (sharded) {   // the watershed of every node, and everything rdgpu_fill_shard_export / _finish need
+  if (sharded) {   // the level and the watershed of every node, and everything rdgpu_fill_shard_export / _finish need
+    uint32_t *lvl = fo.G;   // (the node table is dead: its storage holds the nodes' levels)
+    RD_LAUNCH("fill.node_levels", k_node_levels, ngrid, dim3(NTHR), 0, s, (const uint32_t *)curN, (const uint32_t *)acc,
+              (const unsigned long long *)fo.counters, fo.rcap, lvl);
     uint32_t *nodeW = alloc->get<uint32_t>("fused.nodeW", fo.gcap);
     RD_LAUNCH("fill.node_watersheds", k_node_watersheds, ngrid, dim3(NTHR), 0, s, (const uint32_t *)curN, (const uint32_t *)cur,
               (const uint32_t *)tid, (const unsigned long long *)fo.counters, fo.rcap, B, nodeW);
@@ -3331,10 +3371,11 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
     return true;
   }
   if (listed && lists->n[2] == 0) return true;
+  // (no table of node levels on this path: the finalize takes a tile's levels from curN and acc as it stages them)
   with_flag(vec, [&](auto V) {
     RD_LAUNCH("fill.finalize", (k_finalize16<T, V>), dim3(listed ? lists->n[2] : xcd_grid(dnt)), dim3(NTHR), 0, s, d_z,
-              (const uint16_t *)fo.lab16, (const uint32_t *)lvl, (const uint32_t *)fo.tile_base, (const uint32_t *)fo.tile_count, w, h, dtx,
-              dnt, skip, fl);
+              (const uint16_t *)fo.lab16, (const uint32_t *)nullptr, (const uint32_t *)fo.tile_base, (const uint32_t *)fo.tile_count, w,
+              h, dtx, dnt, skip, fl, (const uint32_t *)curN, (const uint32_t *)acc);
   });
   return true;
 }

@@ -868,6 +868,57 @@ int rdgpu_d8_stream_links(const uint8_t *dirs, uint8_t dir_nodata, int width, in
 int rdgpu_d8_stream_links_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int width, int height,
                               const uint8_t *d_chan /* nullable */, const uint8_t *d_order, uint8_t *d_kind, void *hip_stream);
 
+/* ---- flow distance, drainage cell and HAND on the D8 direction forest --------------------------
+ * No reference counterpart.  Directions are uint8 D8 codes (0 NO_FLOW, 1..8 index the neighbour in the reference's
+ * dx / dy tables, dir_nodata); "the path of cell c" is the one of the upslope entries above; chan is an optional uint8
+ * mask as in the stream-order entries.
+ *   A STOP CELL is a cell with chan != 0 and dirs != dir_nodata.
+ *   With chan given, the DRAINAGE CELL of c is the first stop cell on c's path, c included.  With chan == NULL it is the
+ *   last cell of c's path that is not NoData: rdgpu_d8_outlets' answer, bit for bit.
+ *   A cell has NO drainage cell when its direction is NoData, when its path ends without meeting a stop cell, or when
+ *   its path runs into a direction loop before meeting one.  A stop cell on a loop is its own drainage cell and breaks
+ *   the loop for everything upstream of it.
+ * Per-cell outputs, each a nullable pointer (a call must request at least one):
+ *   to_cell  uint32                    flat index y * width + x of the drainage cell, 0xFFFFFFFF where there is none.
+ *   steps    uint32 [3][height][width] the steps from c to its drainage cell: plane 0 along x (codes 1, 5: dy == 0),
+ *                                      plane 1 along y (codes 3, 7: dx == 0), plane 2 diagonal.  All 0 on a drainage
+ *                                      cell, all 0xFFFFFFFF where there is none.  A path has fewer steps than the
+ *                                      raster has cells, so no count overflows.
+ *   dist     float64                   (double)nx * cell_x + (double)ny * cell_y + (double)nd * diag, evaluated in that
+ *                                      order with a rounding after every product and every sum (no fused multiply-add),
+ *                                      diag = sqrt(cell_x * cell_x + cell_y * cell_y) computed once on the host;
+ *                                      dist_nodata where there is no drainage cell.  A function of three integers:
+ *                                      exact, independent of any summation order.
+ *   hand     float64 (rdgpu_d8_hand_<T>, which also takes the DEM): (double)dem[c] - (double)dem[to_cell[c]];
+ *                                      out_nodata where there is no drainage cell or where either elevation equals
+ *                                      dem_nodata (compared in T).  Not clamped: an unfilled DEM may give negative
+ *                                      values.  T: i8 u8 i16 u16 i32 u32 f32 f64 -- one rounding of exact operands.
+ * cell_x and cell_y: their sign is ignored; zero or not finite is RDGPU_ERR_ARG.  A null dirs (dem, hand), no output
+ * requested, a non-positive size or more than 0xFFFF0000 cells returns RDGPU_ERR_ARG before any device work; nothing
+ * is written then.  The _dev forms take device pointers and are ordered on hip_stream without synchronising it.
+ * Scratch (2.5 bytes per cell; HAND 4 more) comes from the workspace pool. */
+int rdgpu_d8_flow_path(const uint8_t *dirs, uint8_t dir_nodata, int width, int height, const uint8_t *chan /* nullable */,
+                       double cell_x, double cell_y, uint32_t *to_cell /* nullable */, uint32_t *steps /* nullable */,
+                       double *dist /* nullable */, double dist_nodata);
+int rdgpu_d8_flow_path_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int width, int height, const uint8_t *d_chan /* nullable */,
+                           double cell_x, double cell_y, uint32_t *d_to_cell /* nullable */, uint32_t *d_steps /* nullable */,
+                           double *d_dist /* nullable */, double dist_nodata, void *hip_stream);
+#define RDGPU_DECL_HAND(SUF, T)                                                                                       \
+  int rdgpu_d8_hand_##SUF(const uint8_t *dirs, uint8_t dir_nodata, const T *dem, T dem_nodata, int width, int height, \
+                          const uint8_t *chan /* nullable */, double *hand, double out_nodata);                       \
+  int rdgpu_d8_hand_dev_##SUF(const uint8_t *d_dirs, uint8_t dir_nodata, const T *d_dem, T dem_nodata, int width,     \
+                              int height, const uint8_t *d_chan /* nullable */, double *d_hand, double out_nodata,    \
+                              void *hip_stream);
+RDGPU_DECL_HAND(i8, int8_t)
+RDGPU_DECL_HAND(u8, uint8_t)
+RDGPU_DECL_HAND(i16, int16_t)
+RDGPU_DECL_HAND(u16, uint16_t)
+RDGPU_DECL_HAND(i32, int32_t)
+RDGPU_DECL_HAND(u32, uint32_t)
+RDGPU_DECL_HAND(f32, float)
+RDGPU_DECL_HAND(f64, double)
+#undef RDGPU_DECL_HAND
+
 /* ---- synthetic input (test/bench input generator) ----------- */
 int rdgpu_synth_dem_dev_f32(float *d_dem, int width, int height, int seed, int x0, int y0,
                             float tilt, void *hip_stream);

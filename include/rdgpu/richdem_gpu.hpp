@@ -771,4 +771,69 @@ void TA_CTI(const A &flow_accumulation, const S &riserun_slope, R &result) {
   detail::spi_cti(flow_accumulation, riserun_slope, result, true);
 }
 
+// ---- flow distance and HAND on the D8 forest (no reference counterpart; the definition is in rdgpu.h) ---------------
+namespace detail {
+#define RDGPU_SHIM_HAND(SUF, T)                                                                                            \
+  inline int c_hand(const uint8_t *d, uint8_t dnd, const T *z, T znd, int w, int h, const uint8_t *c, double *o, double ond) { \
+    return rdgpu_d8_hand_##SUF(d, dnd, z, znd, w, h, c, o, ond);                                                           \
+  }
+RDGPU_SHIM_HAND(u8, uint8_t) RDGPU_SHIM_HAND(i8, int8_t) RDGPU_SHIM_HAND(u16, uint16_t) RDGPU_SHIM_HAND(i16, int16_t)
+RDGPU_SHIM_HAND(u32, uint32_t) RDGPU_SHIM_HAND(i32, int32_t) RDGPU_SHIM_HAND(f32, float) RDGPU_SHIM_HAND(f64, double)
+#undef RDGPU_SHIM_HAND
+template <class T>
+int c_hand(const uint8_t *, uint8_t, const T *, T, int, int, const uint8_t *, double *, double) { unsupported("d8_hand"); }
+
+template <class F, class C>
+const uint8_t *path_mask(const F &flowdirs, const C *channels, const char *fn) {
+  if (!channels) return nullptr;
+  if (channels->width() != flowdirs.width() || channels->height() != flowdirs.height())
+    throw std::runtime_error(std::string(fn) + ": the channel mask must have the directions' size");
+  return channels->data();
+}
+}  // namespace detail
+
+// dist <- the length of every cell's flow path to its drainage cell: the outlet, or with a channel mask the first channel
+// cell on the path.  The cell lengths are the directions' |geotransform[1]|, |geotransform[5]|; the output takes the
+// directions' size, geotransform and projection, NoData -1 (no drainage cell: NoData, a loop, no channel on the path).
+template <class F, class G, class C>
+void d8_flow_distance(const F &flowdirs, G &dist, const C *channels) {
+  static_assert(std::is_same<detail::elem_t<const F>, uint8_t>::value || std::is_same<detail::elem_t<F>, uint8_t>::value,
+                "d8_flow_distance: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<detail::elem_t<G>, double>::value, "d8_flow_distance: the distance raster must be double");
+  double cx, cy;
+  detail::cell_lengths(flowdirs, "d8_flow_distance", cx, cy);
+  const uint8_t *mask = detail::path_mask(flowdirs, channels, "d8_flow_distance");
+  dist.resize(flowdirs);
+  dist.setNoData(-1.0);
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  detail::check(rdgpu_d8_flow_path(flowdirs.data(), flowdirs.noData(), flowdirs.width(), flowdirs.height(), mask, cx, cy, nullptr,
+                                   nullptr, dist.data(), -1.0), "d8_flow_distance");
+}
+template <class F, class G>
+void d8_flow_distance(const F &flowdirs, G &dist) {
+  d8_flow_distance(flowdirs, dist, static_cast<const F *>(nullptr));
+}
+
+// hand <- dem[c] - dem[drainage cell of c] (height above the nearest drainage), NoData -9999 where there is no drainage
+// cell or one of the two elevations is the DEM's NoData; the output takes the directions' size, geotransform and projection
+template <class E, class F, class G, class C>
+void d8_hand(const E &dem, const F &flowdirs, G &hand, const C *channels) {
+  using T = detail::elem_t<E>;
+  static_assert(std::is_same<detail::elem_t<const F>, uint8_t>::value || std::is_same<detail::elem_t<F>, uint8_t>::value,
+                "d8_hand: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<detail::elem_t<G>, double>::value, "d8_hand: the HAND raster must be double");
+  if (dem.width() != flowdirs.width() || dem.height() != flowdirs.height())
+    throw std::runtime_error("d8_hand: the DEM must have the directions' size");
+  const uint8_t *mask = detail::path_mask(flowdirs, channels, "d8_hand");
+  hand.resize(flowdirs);
+  hand.setNoData(-9999.0);
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  detail::check(detail::c_hand(flowdirs.data(), flowdirs.noData(), (const T *)dem.data(), (T)dem.noData(), flowdirs.width(),
+                               flowdirs.height(), mask, hand.data(), -9999.0), "d8_hand");
+}
+template <class E, class F, class G>
+void d8_hand(const E &dem, const F &flowdirs, G &hand) {
+  d8_hand(dem, flowdirs, hand, static_cast<const F *>(nullptr));
+}
+
 }  // namespace rdgpu

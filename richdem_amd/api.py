@@ -1142,3 +1142,131 @@ def d8_stream_links_dev(dirs, order, out, dir_nodata: int = 255, channels=None) 
     check(lib().rdgpu_d8_stream_links_dev(ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata), w, h,
                                           _dev_mask(channels, (h, w), "d8_stream_links_dev"), ctypes.c_void_p(order.data_ptr()),
                                           ctypes.c_void_p(out.data_ptr()), _stream_ptr()), "rdgpu_d8_stream_links_dev")
+
+
+# ---- flow distance, drainage cell and HAND (csrc/flowpath.hip) --------------------------------
+_PATH_WANT = ("to_cell", "steps", "dist")
+_HAND_SUFFIX = {k: v for k, v in _SUFFIX.items() if v not in ("i64", "u64")}
+
+
+def _cell2(cell, who):
+    try:
+        cx, cy = float(cell[0]), float(cell[1])
+    except (TypeError, ValueError, IndexError):
+        raise RdgpuError(f"{who}: cell is a pair (cell_x, cell_y)") from None
+    return ctypes.c_double(cx), ctypes.c_double(cy)
+
+
+def _want(want, who):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in _PATH_WANT for k in want):
+        raise RdgpuError(f"{who}: want names at least one of {_PATH_WANT}")
+    return want
+
+
+def d8_flow_path(dirs: np.ndarray, dir_nodata: int = 255, channels: np.ndarray | None = None, cell=(1.0, 1.0),
+                 dist_nodata: float = -1.0, want=("to_cell", "dist")) -> dict:
+    """The drainage cell of every cell and the way to it (include/rdgpu.h states the definition): a dict with the planes
+    named in `want` -- "to_cell" (uint32 flat index, 0xFFFFFFFF for none), "steps" (uint32 [3, h, w]: along x, along y,
+    diagonal) and "dist" (float64, dist_nodata for none).  channels=None: the drainage cell is the outlet."""
+    dirs = _dirs2d(dirs, "d8_flow_path")
+    chan = _mask2d(channels, dirs.shape, "d8_flow_path")
+    want = _want(want, "d8_flow_path")
+    cx, cy = _cell2(cell, "d8_flow_path")
+    h, w = dirs.shape
+    out = {}
+    if "to_cell" in want:
+        out["to_cell"] = np.empty((h, w), np.uint32)
+    if "steps" in want:
+        out["steps"] = np.empty((3, h, w), np.uint32)
+    if "dist" in want:
+        out["dist"] = np.empty((h, w), np.float64)
+    check(lib().rdgpu_d8_flow_path(_ptr(dirs), ctypes.c_uint8(dir_nodata), w, h, _ptr(chan), cx, cy, _ptr(out.get("to_cell")),
+                                   _ptr(out.get("steps")), _ptr(out.get("dist")), ctypes.c_double(dist_nodata)),
+          "rdgpu_d8_flow_path")
+    return out
+
+
+def d8_flow_distance(dirs: np.ndarray, dir_nodata: int = 255, channels: np.ndarray | None = None, cell=(1.0, 1.0),
+                     dist_nodata: float = -1.0) -> np.ndarray:
+    """float64 raster: the length of every cell's flow path to its drainage cell -- the outlet, or with `channels` the
+    first channel cell -- in the units of `cell`; dist_nodata where there is none."""
+    return d8_flow_path(dirs, dir_nodata, channels, cell, dist_nodata, want=("dist",))["dist"]
+
+
+def d8_hand(dem: np.ndarray, dirs: np.ndarray, dem_nodata, dir_nodata: int = 255, channels: np.ndarray | None = None,
+            out_nodata: float = -9999.0) -> np.ndarray:
+    """float64 raster: height above the nearest drainage, dem[c] - dem[drainage cell of c]; out_nodata where there is no
+    drainage cell or one of the two elevations is dem_nodata.  Not clamped."""
+    dirs = _dirs2d(dirs, "d8_hand")
+    chan = _mask2d(channels, dirs.shape, "d8_hand")
+    if not isinstance(dem, np.ndarray) or dem.shape != dirs.shape or dem.dtype not in _HAND_SUFFIX:
+        raise RdgpuError("d8_hand: the DEM is an array of the directions' shape, element types int8 .. uint32, float32, float64")
+    dem = np.ascontiguousarray(dem)
+    s = _HAND_SUFFIX[dem.dtype]
+    h, w = dirs.shape
+    out = np.empty((h, w), np.float64)
+    check(getattr(lib(), f"rdgpu_d8_hand_{s}")(_ptr(dirs), ctypes.c_uint8(dir_nodata), _ptr(dem), _scalar(s, dem_nodata), w, h,
+                                               _ptr(chan), _ptr(out), ctypes.c_double(out_nodata)), "rdgpu_d8_hand")
+    return out
+
+
+def _dev_plane(t, shape, dtype, who):
+    if t is None:
+        return None
+    if tuple(_dev_nd(t, who, dtype)) != tuple(shape):
+        raise RdgpuError(f"{who}: shape mismatch")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _dev_nd(t, who, dtype):
+    if not (t.is_cuda and t.is_contiguous()):
+        raise RdgpuError(f"{who}: expected a contiguous tensor on the GPU")
+    if t.dtype != dtype:
+        raise RdgpuError(f"{who}: expected dtype {dtype}, got {t.dtype}")
+    return t.shape
+
+
+def d8_flow_path_dev(dirs, dir_nodata: int = 255, channels=None, cell=(1.0, 1.0), dist_nodata: float = -1.0, to_cell=None,
+                     steps=None, dist=None) -> None:
+    """The planes given (CUDA tensors: to_cell int32 [h, w] holding the uint32 indices bit for bit, -1 is "none"; steps
+    int32 [3, h, w] likewise; dist float64 [h, w]) <- d8_flow_path of dirs (uint8 CUDA tensor), on torch's current
+    stream and without synchronising it.  At least one plane must be given."""
+    import torch
+
+    h, w = _dev2d(dirs, "d8_flow_path_dev", torch.uint8)
+    if to_cell is None and steps is None and dist is None:
+        raise RdgpuError("d8_flow_path_dev: no output requested")
+    cx, cy = _cell2(cell, "d8_flow_path_dev")
+    check(lib().rdgpu_d8_flow_path_dev(ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata), w, h,
+                                       _dev_mask(channels, (h, w), "d8_flow_path_dev"), cx, cy,
+                                       _dev_plane(to_cell, (h, w), torch.int32, "d8_flow_path_dev"),
+                                       _dev_plane(steps, (3, h, w), torch.int32, "d8_flow_path_dev"),
+                                       _dev_plane(dist, (h, w), torch.float64, "d8_flow_path_dev"), ctypes.c_double(dist_nodata),
+                                       _stream_ptr()), "rdgpu_d8_flow_path_dev")
+
+
+def d8_flow_distance_dev(dirs, dist, dir_nodata: int = 255, channels=None, cell=(1.0, 1.0), dist_nodata: float = -1.0) -> None:
+    """dist (float64 CUDA tensor) <- d8_flow_distance of dirs (uint8 CUDA tensor), channels an optional uint8 CUDA mask."""
+    d8_flow_path_dev(dirs, dir_nodata, channels, cell, dist_nodata, dist=dist)
+
+
+def d8_hand_dev(dem, dirs, dem_nodata, out, dir_nodata: int = 255, channels=None, out_nodata: float = -9999.0) -> None:
+    """out (float64 CUDA tensor) <- d8_hand of dem (CUDA tensor, any element type torch has of int8 .. uint32, float32,
+    float64) and dirs (uint8 CUDA tensor)."""
+    import torch
+
+    h, w = _dev2d(dirs, "d8_hand_dev", torch.uint8)
+    m = {torch.int8: "i8", torch.uint8: "u8", torch.int16: "i16", torch.int32: "i32", torch.float32: "f32", torch.float64: "f64"}
+    for name, s in (("uint16", "u16"), ("uint32", "u32")):
+        if hasattr(torch, name):
+            m[getattr(torch, name)] = s
+    if dem.dtype not in m:
+        raise RdgpuError(f"d8_hand_dev: unsupported elevation dtype {dem.dtype}")
+    if _dev2d(dem, "d8_hand_dev") != (h, w) or _dev2d(out, "d8_hand_dev", torch.float64) != (h, w):
+        raise RdgpuError("d8_hand_dev: shape mismatch")
+    s = m[dem.dtype]
+    check(getattr(lib(), f"rdgpu_d8_hand_dev_{s}")(ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata),
+                                                   ctypes.c_void_p(dem.data_ptr()), _scalar(s, dem_nodata), w, h,
+                                                   _dev_mask(channels, (h, w), "d8_hand_dev"), ctypes.c_void_p(out.data_ptr()),
+                                                   ctypes.c_double(out_nodata), _stream_ptr()), "rdgpu_d8_hand_dev")

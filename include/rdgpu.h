@@ -454,22 +454,20 @@ RDGPU_DECL_ALTER(u64, uint64_t)
 #undef RDGPU_DECL_ALTER
 
 /* Environment switches of the directions-only flat resolution (read at every call; A/B timing and tests, results never change;
- * the stencil relaxation engine and its switch are gone: their record is in docs/HISTORY.md and profiles/):
+ * the stencil relaxation engine, the last pass over the DEM, the classification's own bitmaps and their switches are gone: their
+ * record is in docs/HISTORY.md and profiles/):
  *   RDGPU_FLAT_PLANES=0         the two level fields as one int per cell instead of 16 bit planes per 64 x 64 tile (the plane
  *                               engine also steps aside by itself when a level does not fit 16 bits: an open flat more than
  *                               65 000 cells across; flat_mask / labels, alter = true, ResolveFlatsEpsilon and the row-block
  *                               shards always use ints)
- *   RDGPU_FLAT_Q=0              the last pass over the two level fields and the DEM instead of 4 bits per cell (implies ints)
  *   RDGPU_FLAT_STATIC=0         the towards search in batches of rounds decided on the host instead of one enqueue
- *   RDGPU_FLAT_CLASS_BITMAPS=1  the classification writes the searches' bitmaps itself (no flag bytes)
  *   RDGPU_FLAT_ASYNC=<n>        a search's rounds hand over to resident wavefronts once a round visits fewer than n tiles
  *                               (default 20000; 0: rounds to the end), RDGPU_FLAT_ASYNC_BLOCKS / _STATS tune and report them,
  *                               RDGPU_FLAT_ASYNC_FAIL=1 declares a tail failed (tests: the recovery in rounds)
  *   RDGPU_FLAT_PLANES_MAX=<n>   lowers the level from which the plane engine steps aside (tests)
  *   RDGPU_FLAT_TRACE=1          per-round counts and visit statistics on stderr (ints, no side stream)
  *   RDGPU_FLAT_AWAY_BESIDE=0    the away search after the towards search instead of beside its tail
- * ResolveFlatsEpsilon: RDGPU_RFE_LEAN=0 (FindFlats as its own pass, labels / outlet marks / flat heights as the flat_mask path
- * makes them), RDGPU_RFE_OVERLAP=0 (the labels on the caller's stream), RDGPU_RFE_AWAY_BESIDE=1 (the away search on a third stream) */
+ * ResolveFlatsEpsilon: RDGPU_RFE_OVERLAP=0 (the labels on the caller's stream instead of beside the towards search's tail) */
 typedef struct rdgpu_flat_stats {
   uint64_t low_edges;      /* find_flat_edges: cells with flow next to an equal NO_FLOW cell */
   uint64_t high_edges;     /* NO_FLOW cells next to higher terrain                           */

@@ -100,39 +100,6 @@ __global__ __launch_bounds__(NTHR) void k_planes_prepare(const uint8_t *__restri
   }
 }
 
-// The same start from the classification's bitmaps (k_dirs_classify<BITMAPS>): `seeds` holds the field's seed rows; one
-// wavefront per tile, lane = row.
-template <bool TOWARDS>
-__global__ __launch_bounds__(NTHR) void k_planes_prepare_b(const unsigned long long *__restrict__ seeds, PlaneField pf, uint8_t *tile_active,
-                                                           int h, uint32_t tilesX, uint32_t tilesY,
-                                                           const unsigned long long *__restrict__ count_rows = nullptr,
-                                                           uint32_t *counts = nullptr, int count_slot = 0) {
-  constexpr int SEED = TOWARDS ? 2 : 1;
-  const uint32_t t = blockIdx.x * (NTHR / 64) + (threadIdx.x >> 6);
-  if (t >= tilesX * tilesY) return;
-  const int lane = threadIdx.x & 63;
-  const int tx = (int)(t % tilesX), ty = (int)(t / tilesX);
-  const unsigned long long srow = seeds[(size_t)t * BT + lane];
-  pf.R[(size_t)t * BT + lane] = srow;
-  const int brow = min(BT - 1, h - 1 - ty * BT);
-  const unsigned long long s0 = readlane64(srow, 0), sb = readlane64(srow, brow);
-  int32_t *const E = pf.E + (size_t)t * 256;
-  E[lane] = (s0 >> lane & 1ull) ? SEED : DINF;
-  E[64 + lane] = (sb >> lane & 1ull) ? SEED : DINF;
-  E[128 + lane] = (srow & 1ull) ? SEED : DINF;
-  E[192 + lane] = (srow >> 63 & 1ull) ? SEED : DINF;
-  if (__any(srow != 0) && lane < 9) {
-    const int ntx = tx + lane % 3 - 1, nty = ty + lane / 3 - 1;
-    if (ntx >= 0 && nty >= 0 && ntx < (int)tilesX && nty < (int)tilesY) tile_active[nty * tilesX + ntx] = 1;
-  }
-  if (counts) {   // the cells of a bitmap (the edge counts of rdgpu_flat_get_stats), striped like the classification's
-    uint32_t c = (uint32_t)__popcll(count_rows[(size_t)t * BT + lane]);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-    if (lane == 0 && c) atomicAdd(counts + 3 * (t & 255u) + count_slot, c);
-  }
-}
-
 // One visit of tile t by one wavefront, on the planes; returns the 9-bit mask of the neighbouring tiles to wake.
 template <int SEED_LEVEL, bool CO>
 __device__ __forceinline__ uint32_t relax_visit_p(const unsigned long long *__restrict__ mbits, uint8_t *expanded, const PlaneField pf,

@@ -13,7 +13,7 @@
 //                                                while the front is wide, then ONE resident launch that pulls tiles from
 //                                                queues -- k_relax_bits_async; the away search runs on a side stream
 //                                                beside the towards search's tail)
-//   d8_flow_flats / d8_masked_FlowDir :96-116, :42-65 -> k_flat_dirs (full mask), k_flat_dirs_levels (directions-only entry)
+//   d8_flow_flats / d8_masked_FlowDir :96-116, :42-65 -> k_flat_dirs (full mask), k_flat_dirs_q / k_flat_dirs_qp (directions-only entry)
 // ResolveFlatsEpsilon (flats/flats.hpp:21-28) runs the same searches over FindFlats' cells, with the labels (k_ccl_*) on a
 // side stream beside the searches' tail.
 //
@@ -186,7 +186,7 @@ __device__ __forceinline__ uint8_t d8_dir_cell(const T *sz, int zx, int zy, int 
 // are equal-elevation cells with a direction: the first of them in neighbour order, replaced by the first odd-numbered one
 // after it if it is a diagonal (the same tie rule as everywhere).  That is known here and nowhere later without the
 // elevations, so the pass after the searches (k_flat_dirs_q) reads no DEM at all.
-// FindFlats' pseudo direction of a staged cell (flats/find_flats.hpp:29-69; see k_find_flats): 0 = flat, 1 = not, 255 = NoData
+// FindFlats' pseudo direction of a staged cell (flats/find_flats.hpp:29-69): 0 = flat, 1 = not, 255 = NoData
 template <class T>
 __device__ __forceinline__ uint8_t find_flats_cell(const T *sz, int zx, int zy, int gx, int gy, int w, int h, T nodata) {
   if (gx < 0 || gy < 0 || gx >= w || gy >= h) return 255;
@@ -202,22 +202,13 @@ __device__ __forceinline__ uint8_t find_flats_cell(const T *sz, int zx, int zy, 
   return f;
 }
 
-// FINDFLATS (r05, ResolveFlatsEpsilon's lean path): the "directions" are FindFlats' pseudo raster and are NOT written -- nothing
-// but this classification reads them there: k_find_flats + k_flat_classify (two passes over the DEM, the pseudo raster
-// written and read back) in one.
-// BITMAPS (r06, the plane engine): instead of a flag byte per cell, the rows of three bitmaps per 64 x 64 search tile -- the
-// cells without a direction (M), those of them next to a low edge (the towards seeds), the high edges (the away seeds) --
-// and the edge counts: what k_bits_prepare would make of the flags, without writing and re-reading them (1 B -> 3 bits per
-// cell; the start kernels of the two searches read 1.5 KB per tile instead of 4 KB, without byte loads).
-struct ClassBitmaps {
-  unsigned long long *rows = nullptr;   // three bitmaps of nrows = search tiles x 64 row words each: M, near, high
-  uint32_t *counts = nullptr;           // 256 stripes of (low edges, high edges, NO_FLOW cells)
-  uint32_t nrows = 0, tilesXb = 0;
-};
-template <class T, bool NEARDIRS = false, bool FINDFLATS = false, bool BITMAPS = false>
+// FINDFLATS (r05, ResolveFlatsEpsilon): the "directions" are FindFlats' pseudo raster and are NOT written (dirs is null) --
+// nothing but this classification reads them there: a FindFlats pass + k_flat_classify (two passes over the DEM, the pseudo
+// raster written and read back) in one.
+// The two instantiations: <T, true> (the directions-only entry) and <T, false, true> (ResolveFlatsEpsilon).
+template <class T, bool NEARDIRS = false, bool FINDFLATS = false>
 __global__ __launch_bounds__(NTHR) void k_dirs_classify(const T *__restrict__ z, T nodata, uint8_t *__restrict__ dirs,
-                                                        uint8_t *__restrict__ flags, int w, int h, uint32_t tilesX, uint32_t ntiles,
-                                                        ClassBitmaps bm = ClassBitmaps{}) {
+                                                        uint8_t *__restrict__ flags, int w, int h, uint32_t tilesX, uint32_t ntiles) {
   __shared__ T sz[FZH * FZW];
   __shared__ uint8_t sdir[KLLH * SLW];
   const uint32_t t = xcd_tile(blockIdx.x, ntiles);
@@ -305,8 +296,6 @@ __global__ __launch_bounds__(NTHR) void k_dirs_classify(const T *__restrict__ z,
   T z0[3], z1[3], z2[3];
   uint8_t d0[3], d1[3], d2[3];
   bool v0[3], v1[3], v2[3], n0[3], n1[3], n2[3];
-  uint32_t nlow = 0;   // (BITMAPS: low edges, per lane)
-  unsigned long long keepM = 0, keepN = 0, keepH = 0;
 #pragma unroll
   for (int e = 0; e < 3; e++) {
     z0[e] = sz[(yb + 1) * FZW + lx + 1 + e]; z1[e] = sz[(yb + 2) * FZW + lx + 1 + e];
@@ -322,7 +311,6 @@ __global__ __launch_bounds__(NTHR) void k_dirs_classify(const T *__restrict__ z,
       v2[e] = d2[e] != 255; n2[e] = d2[e] == 0;
     }
     uint8_t f = 0;
-    bool b_noflow = false, b_high = false, b_near = false, b_low = false;   // (BITMAPS: the flags as lane masks, never a byte)
     const uint8_t d = d1[1];
     if (d != 255) {
       const bool noflow = d == 0;
@@ -343,7 +331,6 @@ __global__ __launch_bounds__(NTHR) void k_dirs_classify(const T *__restrict__ z,
       nb(z2[0], v2[0], n2[0]); nb(z2[1], v2[1], n2[1]); nb(z2[2], v2[2], n2[2]);
       if (noflow ? higher : eq_noflow) f |= noflow ? F_HIGH : F_LOW;
       if (noflow && eq_flow) f |= F_NEAR;
-      if (BITMAPS) { b_noflow = noflow; b_high = noflow & higher; b_near = noflow & eq_flow; b_low = !noflow & eq_noflow; }
       if (NEARDIRS && noflow && eq_flow) {
         // neighbours 1..8 in the 234/105/876 numbering; le: an equal-elevation cell with a direction (a low edge of this flat)
         auto lowedge = [&](T zn, bool valid, bool nf) -> bool { return valid && zn == e && !nf; };
@@ -360,31 +347,9 @@ __global__ __launch_bounds__(NTHR) void k_dirs_classify(const T *__restrict__ z,
         if (gx < w && gy < h) dirs[(size_t)gy * w + gx] = (uint8_t)nd;   // (a NO_FLOW cell is interior: its window is complete)
       }
     }
-    if (BITMAPS) {   // (a cell outside the raster has d == 255: f == 0)
-      const unsigned long long mb = __ballot(b_noflow), nb_ = __ballot(b_near), hb = __ballot(b_high);
-      // (the low edges are in no bitmap: counted here, per lane in a vector register -- as a wave-uniform sum it costs the kernel's
-      // scalar registers, 37 spilled; the high edges and NO_FLOW cells are counted from the bitmaps by k_planes_prepare_b)
-      nlow += b_low ? 1u : 0u;
-      if (lx == j) { keepM = mb; keepN = nb_; keepH = hb; }   // lane j keeps row j of the wavefront's band: one store of eight words per bitmap below
-    } else if (gx < w && gy < h) flags[(size_t)gy * w + gx] = f;
+    if (gx < w && gy < h) flags[(size_t)gy * w + gx] = f;
 #pragma unroll
     for (int e = 0; e < 3; e++) { z0[e] = z1[e]; z1[e] = z2[e]; d0[e] = d1[e]; d1[e] = d2[e]; v0[e] = v1[e]; v1[e] = v2[e]; n0[e] = n1[e]; n1[e] = n2[e]; }
-  }
-  if (BITMAPS) {
-    static_assert(SW == 64 && KLH / 4 == 8, "a classification tile is one search tile wide, a wavefront's band eight rows");
-    if (lx < KLH / 4) {   // rows y0 + yb .. + 7: consecutive words of one search tile
-      const int gy = y0 + yb + lx;
-      unsigned long long *const row = bm.rows + ((size_t)(gy >> 6) * bm.tilesXb + (size_t)(x0 >> 6)) * 64 + (size_t)(gy & 63);
-      row[0] = keepM; row[bm.nrows] = keepN; row[2 * (size_t)bm.nrows] = keepH;
-    }
-    // the counts, striped: same-address atomics serialise
-    const unsigned long long lowlanes = __ballot(nlow != 0);
-    if (lowlanes) {   // (rare: one wavefront in a few has a low edge)
-      uint32_t lo = nlow;
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) lo += __shfl_xor(lo, o, 64);
-      if (lx == 0) atomicAdd(bm.counts + 3 * ((t * 4 + (threadIdx.x >> 6)) & 255u), lo);
-    }
   }
 }
 
@@ -713,7 +678,7 @@ __global__ __launch_bounds__(NTHR) void k_ccl_border2(const T *__restrict__ z, u
 }
 
 // k_ccl_flatten four cells a thread, and flat_height's start: a component's deepest away level is collected at its root
-// (fh[root] = 0; the other entries of fh are never read by the lean path)
+// (fh[root] = 0; the other entries of fh are never read by ResolveFlatsEpsilon, its only user)
 __global__ __launch_bounds__(NTHR) void k_ccl_flatten4(uint32_t *L, int32_t *fh, uint64_t n) {
   const uint64_t n4 = n / 4, stride = (uint64_t)gridDim.x * NTHR;
   for (uint64_t q = (uint64_t)blockIdx.x * NTHR + threadIdx.x; q < n4 + (n & 3); q += stride) {
@@ -844,7 +809,7 @@ struct BitsScratch {
   uint32_t *tlist, *ctr, *counts;
   uint32_t tilesX, tilesY, ntiles;
   PlaneField pf;               // P != nullptr: the search runs on planes
-  unsigned long long *near = nullptr, *high = nullptr;   // (planes) the two fields' seed rows: the cells next to a low edge, the high edges
+  unsigned long long *near = nullptr;   // (planes) the cells next to a low edge: the towards seeds' rows, kept for the last pass
 };
 
 __device__ __forceinline__ uint32_t dpp_up(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }
@@ -1346,16 +1311,6 @@ __device__ __forceinline__ uint32_t relax_visit(const unsigned long long *__rest
 
 #include "flat_planes.inc"
 
-// the cells of a bitmap, into a stripe of the edge counts
-__global__ __launch_bounds__(NTHR) void k_rows_count(const unsigned long long *__restrict__ rows, uint32_t ntiles, uint32_t *counts, int slot) {
-  const uint32_t t = blockIdx.x * (NTHR / 64) + (threadIdx.x >> 6);
-  if (t >= ntiles) return;
-  uint32_t c = (uint32_t)__popcll(rows[(size_t)t * BT + (threadIdx.x & 63)]);
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(counts + 3 * (t & 255u) + slot, c);
-}
-
 template <int SEED_LEVEL, bool STATS = false>
 __global__ __launch_bounds__(NTHR, 5) void k_relax_bits(const unsigned long long *__restrict__ mbits, uint8_t *expanded, int32_t *D,
                                                      const uint32_t *__restrict__ tiles, const uint32_t *__restrict__ count,
@@ -1658,120 +1613,8 @@ __global__ __launch_bounds__(NTHR) void k_flat_dirs(const T *__restrict__ z, con
 // (towards level 1) hold mask 2 -- below every NO_FLOW cell of their flat, whose towards level is at least 2 -- and
 // d8_masked_FlowDir (:42-65) only COMPARES masks of cells of one flat.  So neither the flat heights nor the labels
 // behind them (k_ccl_*, k_flat_height, k_flat_combine: 45 ms of the stage at S3) are needed for the directions.
-template <class T>
-__global__ __launch_bounds__(NTHR) void k_flat_dirs_levels(const T *__restrict__ z, const int32_t *__restrict__ TW,
-                                                           const int32_t *__restrict__ AW, uint8_t *dirs, int w, int h,
-                                                           uint32_t tilesX, uint32_t ntiles) {
-  __shared__ T sz[KLLH * SLW];
-  __shared__ int32_t sm[KLLH * SLW];
-  constexpr int32_t LOWEDGE = INT32_MIN, NOTFLAT = INT32_MAX;
-  const uint32_t t = xcd_tile(blockIdx.x, ntiles);
-  if (t >= ntiles) return;
-  const int x0 = (int)(t % tilesX) * SW, y0 = (int)(t / tilesX) * KLH;
-  if (window_inside(x0, y0, w, h, SW, KLH, 1)) {
-    // the window lies inside the raster: four cells per load (see stage_window_inside), the two level fields combined on the way
-    stage_window_inside<T, SW, KLH, 1, SLW, NTHR>(z, w, x0, y0, sz);
-    constexpr int QPR = SW / 4, NQ = KLLH * QPR, QPT = (NQ + NTHR - 1) / NTHR, NHC = KLLH * 2;
-    struct Q4 { int32_t v[4]; };
-    const int32_t *const tb = TW + ((size_t)(y0 - 1) * w + (size_t)(x0 - 1)), *const ab = AW ? AW + ((size_t)(y0 - 1) * w + (size_t)(x0 - 1)) : nullptr;
-    Q4 tq[QPT], aq[QPT];
-    int32_t th = DINF, ah = DINF;
-#pragma unroll
-    for (int r = 0; r < QPT; r++) {
-      const int i = (int)threadIdx.x + r * NTHR;
-      const int ly = i / QPR, qq = i - ly * QPR;
-      if (i < NQ) {
-        __builtin_memcpy(&tq[r], tb + (uint32_t)(ly * w + 1 + 4 * qq), sizeof(Q4));
-        if (ab) __builtin_memcpy(&aq[r], ab + (uint32_t)(ly * w + 1 + 4 * qq), sizeof(Q4));
-      }
-    }
-    static_assert(NHC <= NTHR, "one halo cell per thread");
-    if ((int)threadIdx.x < NHC) {
-      const int ly = (int)threadIdx.x >> 1, c = (int)threadIdx.x & 1;
-      th = tb[(uint32_t)(ly * w + (c ? SW + 1 : 0))];
-      if (ab) ah = ab[(uint32_t)(ly * w + (c ? SW + 1 : 0))];
-    }
-    auto mask = [&](int32_t tv_, int32_t av_) -> int32_t { return tv_ >= DINF ? NOTFLAT : tv_ == 1 ? LOWEDGE : 2 * tv_ - (av_ < DINF ? av_ : 0); };
-#pragma unroll
-    for (int r = 0; r < QPT; r++) {
-      const int i = (int)threadIdx.x + r * NTHR;
-      const int ly = i / QPR, qq = i - ly * QPR;
-      if (i < NQ) {
-#pragma unroll
-        for (int e = 0; e < 4; e++) sm[ly * SLW + 1 + 4 * qq + e] = mask(tq[r].v[e], ab ? aq[r].v[e] : DINF);
-      }
-    }
-    if ((int)threadIdx.x < NHC) {
-      const int ly = (int)threadIdx.x >> 1, c = (int)threadIdx.x & 1;
-      sm[ly * SLW + (c ? SW + 1 : 0)] = mask(th, ah);
-    }
-  } else {
-    constexpr int IPT = (KLLH * SLW + NTHR - 1) / NTHR;
-    T zv[IPT];
-    int32_t tv[IPT], av[IPT];
-#pragma unroll
-    for (int r = 0; r < IPT; r++) {   // all loads of the thread in flight together (clamped addresses)
-      const int i = min((int)threadIdx.x + r * NTHR, KLLH * SLW - 1);
-      const int ly = i / SLW, lx = i - ly * SLW;
-      const int gx = min(max(x0 - 1 + lx, 0), w - 1), gy = min(max(y0 - 1 + ly, 0), h - 1);
-      const size_t g = (size_t)gy * w + gx;
-      zv[r] = z[g];
-      tv[r] = TW[g];
-      av[r] = AW ? AW[g] : DINF;
-    }
-#pragma unroll
-    for (int r = 0; r < IPT; r++) {
-      const int i = (int)threadIdx.x + r * NTHR;
-      if (i >= KLLH * SLW) continue;
-      const int ly = i / SLW, lx = i - ly * SLW;
-      const int gx = x0 - 1 + lx, gy = y0 - 1 + ly;
-      const bool in = gx >= 0 && gx < w && gy >= 0 && gy < h;
-      sz[i] = in ? zv[r] : T();
-      sm[i] = (!in || tv[r] >= DINF) ? NOTFLAT : tv[r] == 1 ? LOWEDGE : 2 * tv[r] - (av[r] < DINF ? av[r] : 0);
-    }
-  }
-  __syncthreads();
-  // a wavefront owns a band of 8 consecutive rows, a lane one column; the 3 x 3 windows slide down in registers
-  const int lx = threadIdx.x & (SW - 1), yb = (int)(threadIdx.x >> 6) * (KLH / 4);
-  const int gx = x0 + lx;
-  T z0[3], z1[3], z2[3];
-  int32_t m0[3], m1[3], m2[3];
-#pragma unroll
-  for (int e = 0; e < 3; e++) {
-    z0[e] = sz[yb * SLW + lx + e]; z1[e] = sz[(yb + 1) * SLW + lx + e];
-    m0[e] = sm[yb * SLW + lx + e]; m1[e] = sm[(yb + 1) * SLW + lx + e];
-  }
-#pragma unroll
-  for (int j = 0; j < KLH / 4; j++) {
-    const int gy = y0 + yb + j;
-#pragma unroll
-    for (int e = 0; e < 3; e++) { z2[e] = sz[(yb + j + 2) * SLW + lx + e]; m2[e] = sm[(yb + j + 2) * SLW + lx + e]; }
-    const int32_t mc = m1[1];
-    // interior only (:108-109); a NO_FLOW cell of a drainable flat (low edges keep their direction, :112)
-    if (gx > 0 && gy > 0 && gx < w - 1 && gy < h - 1 && mc != NOTFLAT && mc != LOWEDGE) {
-      // neighbours 1..8 in the 234/105/876 numbering
-      const T zn[9] = {z1[1], z1[0], z0[0], z0[1], z0[2], z1[2], z2[2], z2[1], z2[0]};
-      const int32_t mn[9] = {m1[1], m1[0], m0[0], m0[1], m0[2], m1[2], m2[2], m2[1], m2[0]};
-      const T e = z1[1];
-      int32_t m = mc;
-      int dir = 0;
-#pragma unroll
-      for (int k = 1; k <= 8; k++) {   // selects, no branches (see k_flat_classify)
-        const int32_t v = mn[k];
-        const bool same = (zn[k] == e) & (v != NOTFLAT);   // labels(n) == labels(c), :56-57 (an equal neighbour outside the flat cannot occur: kept safe)
-        const bool take = same & ((v < m) | ((v == m) & (dir > 0) & ((dir & 1) == 0) & ((k & 1) == 1)));
-        m = take ? v : m;
-        dir = take ? k : dir;
-      }
-      dirs[(size_t)gy * w + gx] = (uint8_t)dir;
-    }
-#pragma unroll
-    for (int e = 0; e < 3; e++) { z0[e] = z1[e]; z1[e] = z2[e]; m0[e] = m1[e]; m1[e] = m2[e]; }
-  }
-}
-
-// The same directions WITHOUT the DEM, from 4 bits per cell (r05; the default of the directions-only entry).  What
-// d8_masked_FlowDir compares are masks of adjacent cells of one flat, and
+// And not the DEM either: 4 bits per cell suffice (r05).  What d8_masked_FlowDir compares are masks of adjacent cells of one
+// flat, and
 //   * two adjacent NO_FLOW cells always lie in one flat (equal elevation: a higher one would have a direction), are reached
 //     by the towards search together or not at all, likewise by the away search, and their levels differ by at most one in
 //     either field (breadth-first levels of adjacent vertices): |mask(n) - mask(c)| = |2 dT - dA| <= 3, so the masks
@@ -1781,7 +1624,8 @@ __global__ __launch_bounds__(NTHR) void k_flat_dirs_levels(const T *__restrict__
 //   * a cell takes part iff its towards level lies in [2, DINF): low edges hold 1, everything else DINF.
 // So the window is staged as ONE BYTE per cell -- bits 0-2 the mask modulo 8, bit 3 "does not take part", bit 4 "has its
 // direction" -- four cells per LDS store, and a neighbour costs a subtraction, two ANDs, an OR and two compares: no
-// elevations read or compared (k_flat_dirs_levels: 20.4 GB fetched, 4.5 ms at S3).  Measured and dropped on the way
+// elevations read or compared (the r02-r04 pass over the two level fields and the DEM, retired: 20.4 GB fetched, 4.5 ms at S3,
+// against 14.7 GB and 3.1 ms here; docs/HISTORY.md).  Measured and dropped on the way
 // (profiles/r05b_flats_bytes_ab.json): byte planes written by the searches beside their 32-bit levels, so that this pass
 // reads 3 bytes per cell -- the stores slowed every visit and the start levels (36.1 against 32.6 ms for the stage): the
 // stage is bound by instruction issue and dependent visits, not by these bytes.
@@ -1987,7 +1831,7 @@ static BitsScratch bits_scratch(int w, int h, bool second = false, bool planes =
   Workspace &ws = Workspace::get();
   BitsScratch b;
   b.tilesX = (w + BT - 1) / BT; b.tilesY = (h + BT - 1) / BT; b.ntiles = b.tilesX * b.tilesY;
-  b.mbits = ws.buf<unsigned long long>("flats.mbits", (size_t)b.ntiles * BT * (planes ? 3 : 1));   // (planes: M | near | high)
+  b.mbits = ws.buf<unsigned long long>("flats.mbits", (size_t)b.ntiles * BT * (planes ? 2 : 1));   // (planes: M | near)
   b.expanded = ws.buf<uint8_t>(second ? "flats.bexp2" : "flats.bexp", b.ntiles);
   b.tflags = ws.buf<uint8_t>(second ? "flats.btflags2" : "flats.btflags", b.ntiles);
   b.tlist = ws.buf<uint32_t>(second ? "flats.btlist2" : "flats.btlist", b.ntiles);
@@ -2001,7 +1845,6 @@ static BitsScratch bits_scratch(int w, int h, bool second = false, bool planes =
     b.pf.expanded = b.expanded;
     if (const char *e = getenv("RDGPU_FLAT_PLANES_MAX")) b.pf.max_level = std::min(0xFFF0, std::max(8, atoi(e)));   // (tests: the overflow path)
     b.near = b.mbits + (size_t)b.ntiles * BT;
-    b.high = b.mbits + 2 * (size_t)b.ntiles * BT;
   }
   return b;
 }
@@ -2018,8 +1861,8 @@ static thread_local AsyncInfo g_async_info = {0, 0, 0, 0};
 
 // What relax_rounds_bits / the static search hand to the code around them when the search reaches its tail: mark() before
 // the resident launch is enqueued (the place for an event the side work waits on), go() after it (the resident
-// wavefronts have their places: now the work that is to run beside them).  Both are called exactly once, also when the
-// search ends in its rounds.
+// wavefronts have their places: now the work that is to run beside them).  Each, where set, is called exactly once, also
+// when the search ends in its rounds.
 struct Beside {
   std::function<void()> mark, go;
 };
@@ -2176,24 +2019,15 @@ static uint32_t relax_rounds_bits(const BitsScratch &b, int32_t *D, int w, int h
 }
 
 // The start of a field's search: the bitmap of the cells that take part, the seeds at their level, the tiles to visit first
-// (towards: with the edge counts in cnt, if given).  On planes (b.pf.P) from the bitmaps the classification made (no flags) or
-// from the flag bytes; else on ints (write_m: this field makes the bitmap; L / fh: only the high edges of flats with an outlet).
+// (towards: with the edge counts in cnt, if given), all from the flag bytes.  On planes (b.pf.P), or on ints (write_m: this
+// field makes the bitmap; L / fh: only the high edges of flats with an outlet).
 template <bool TOWARDS>
 static void launch_prepare(const BitsScratch &b, const uint8_t *flags, const uint32_t *L, const int32_t *fh, int32_t *D, bool write_m,
                            uint32_t *cnt, int w, int h, hipStream_t s) {
   // (b.pf.P is set exactly when bits_scratch was asked for planes: it stands for the callers' `planes`)
-  const dim3 per_tile(b.ntiles), per_wave((b.ntiles + 3) / 4), blk(NTHR);
+  const dim3 per_tile(b.ntiles), blk(NTHR);
   const RowWin win{0, h, nullptr, nullptr};
-  if (b.pf.P && !flags && TOWARDS) {
-    // (it also counts the NO_FLOW cells and the high edges from their bitmaps: the away search may start later, the counts
-    // are read with this search's)
-    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare_b<true>), per_wave, blk, 0, s, (const unsigned long long *)b.near, b.pf, b.tflags, h,
-              b.tilesX, b.tilesY, (const unsigned long long *)b.mbits, cnt, 2);
-    if (cnt) RD_LAUNCH("flats.bits_counts_high", k_rows_count, per_wave, blk, 0, s, (const unsigned long long *)b.high, b.ntiles, cnt, 1);
-  } else if (b.pf.P && !flags)
-    RD_LAUNCH("flats.bits_prepare", (k_planes_prepare_b<false>), per_wave, blk, 0, s, (const unsigned long long *)b.high, b.pf, b.tflags, h,
-              b.tilesX, b.tilesY);
-  else if (b.pf.P)
+  if (b.pf.P)
     RD_LAUNCH("flats.bits_prepare", (k_planes_prepare<TOWARDS, TOWARDS>), per_tile, blk, 0, s, flags, b.pf, b.mbits,
               TOWARDS ? b.near : (unsigned long long *)nullptr, b.tflags, cnt, w, h, b.tilesX, b.tilesY);
   else if (write_m)
@@ -2212,7 +2046,7 @@ static uint32_t run_bits_towards(const uint8_t *flags, int32_t *D, bool write_m,
   RD_HIP(hipMemsetAsync(b.tflags, 0, b.ntiles, s));
   RD_HIP(hipMemsetAsync(b.expanded, 0, b.ntiles, s));
   uint32_t *cnt = counts3 ? b.counts : nullptr;
-  if (cnt && flags) RD_HIP(hipMemsetAsync(cnt, 0, (3 * 256 + 8) * sizeof(uint32_t), s));   // (no flags: the classification counted)
+  if (cnt) RD_HIP(hipMemsetAsync(cnt, 0, (3 * 256 + 8) * sizeof(uint32_t), s));
   if (planes) RD_HIP(hipMemsetAsync(b.pf.overflow, 0, 2 * sizeof(uint32_t), s));   // (both fields' words)
   launch_prepare<true>(b, flags, nullptr, nullptr, D, write_m, cnt, w, h, s);
   if (cnt) {
@@ -2282,7 +2116,7 @@ static StaticAway enqueue_towards_static(const uint8_t *flags, unsigned long lon
   RD_HIP(hipMemsetAsync(b.tflags, 0, b.ntiles, s));
   RD_HIP(hipMemsetAsync(b.expanded, 0, b.ntiles, s));
   RD_HIP(hipMemsetAsync(b.pf.overflow, 0, 2 * sizeof(uint32_t), s));   // (both fields' words)
-  if (flags) RD_HIP(hipMemsetAsync(b.counts, 0, (3 * 256 + 8) * sizeof(uint32_t), s));   // (no flags: the classification counted the low edges)
+  RD_HIP(hipMemsetAsync(b.counts, 0, (3 * 256 + 8) * sizeof(uint32_t), s));
   launch_prepare<true>(b, flags, nullptr, nullptr, nullptr, true, b.counts, w, h, s);
   RD_LAUNCH("flats.bits_counts", k_bits_counts, dim3(1), dim3(NTHR), 0, s, (const uint32_t *)b.counts, d_counts3);
   st.run = enqueue_static_rounds<2>(b, nullptr, TOWARDS_STATIC_ROUNDS, w, h, "flats.relax_towards", s, false, beside);
@@ -2321,121 +2155,34 @@ static uint32_t finish_static(const StaticAway &st, int32_t *D, int nrounds, int
   return rounds;
 }
 
-// RDGPU_RFE_LEAN=0: labels, outlet marks and flat heights as the flat_mask path makes them: A/B and tests
-static bool lean_labels() { return !env_is("RDGPU_RFE_LEAN", '0'); }
-
 // Computes flat_mask (M) for the DEM; d_dirs must hold d8_flow_directions output.
-// Returns device pointers (workspace) to M, L, fh through the out parameters.
+// Returns device pointers (workspace) to M, L, fh through the out parameters (L, fh: null where no flat has an outlet).
 template <class T>
 static void resolve_flats_device(const T *d_z, const uint8_t *d_dirs, int w, int h, int32_t **outM, uint32_t **outL,
-                                 int32_t **outFh, hipStream_t s, const int32_t **outA = nullptr, T ff_nodata = T()) {
+                                 int32_t **outFh, hipStream_t s) {
   const uint64_t n = (uint64_t)w * h;
   Workspace &ws = Workspace::get();
   int32_t *M = ws.buf<int32_t>("flats.mask", n);
   *outM = M;
   *outL = nullptr;
   *outFh = nullptr;
-  const bool lean = outA && lean_labels();
-  if (!lean) RD_HIP(hipMemsetAsync(M, 0, n * sizeof(int32_t), s));  // flat_mask.setAll(0), :469 (lean: the towards search writes every cell)
+  RD_HIP(hipMemsetAsync(M, 0, n * sizeof(int32_t), s));  // flat_mask.setAll(0), :469
   g_fstats = rdgpu_flat_stats{0, 0, 0, 0, 0};
   g_async_info = AsyncInfo{0, 0, 0, 0};
 
   uint8_t *flags = ws.buf<uint8_t>("flats.flags", n);
-  if (d_dirs) {
-    launch_classify<T>(d_z, d_dirs, w, h, flags, s);
-  } else {   // (ResolveFlatsEpsilon's lean path: FindFlats and the classification in one pass; nodata travels in *outA's place)
-    if (!lean) throw Error(RDGPU_ERR_ARG, "resolve_flats_device: the fused FindFlats classification needs the lean path");
-    const uint32_t tilesX = (w + SW - 1) / SW, ntiles = tilesX * ((h + KLH - 1) / KLH);
-    RD_LAUNCH("flats.findflats_classify", (k_dirs_classify<T, false, true>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, ff_nodata,
-              (uint8_t *)nullptr, flags, w, h, tilesX, ntiles);
-  }
+  launch_classify<T>(d_z, d_dirs, w, h, flags, s);
   uint32_t nlow = 0, nhigh_all = 0, nnoflow = 0;
-  if (!lean) {
-    count_edges(flags, n, &nlow, &nhigh_all, &nnoflow, s);
-    g_fstats.low_edges = nlow;
-    g_fstats.noflow_cells = nnoflow;
-    g_fstats.high_edges = nhigh_all;
-    if (nlow == 0) return;   // no flats, or none with an outlet (:475-481)
-  }
+  count_edges(flags, n, &nlow, &nhigh_all, &nnoflow, s);
+  g_fstats.low_edges = nlow;
+  g_fstats.noflow_cells = nnoflow;
+  g_fstats.high_edges = nhigh_all;
+  if (nlow == 0) return;   // no flats, or none with an outlet (:475-481)
 
   uint32_t *L = ws.buf<uint32_t>("flats.L", n);
   int32_t *fh = ws.buf<int32_t>("flats.fh", n);
-  if (!lean) {
-    *outL = L;
-    *outFh = fh;
-  }
-  if (lean) {
-    // The caller wants the levels, the labels and the flat heights (ResolveFlatsEpsilon), nothing per flat beyond that: the
-    // labels do not depend on the searches here.  "The flat has an outlet" (:491-500) is what the towards levels say anyway
-    // (a flat without a low edge is never reached: its cells keep DINF and k_flat_epsilon4 skips them), so the away field
-    // starts from EVERY high edge and fh needs no "-1 = no outlet" marks: no k_flat_mark_low_flags pass, no fill of fh.
-    const uint32_t tilesX = (w + CW - 1) / CW, ntiles = tilesX * ((h + CH - 1) / CH);
-    T *colZ = ws.buf<T>("flats.colz", (size_t)ntiles * 2 * CH);
-    uint32_t *colL = ws.buf<uint32_t>("flats.coll", (size_t)ntiles * 2 * CH);
-    // ... and so they are made BESIDE the tail of the towards search (and the away search after it), on the device's side
-    // stream: the tail keeps two resident blocks per CU busy with dependent visits and leaves the memory system idle, the
-    // labelling is three streaming passes.  (Started with the search's first rounds, which are throughput-bound
-    // themselves, the labels only took their turn: 64.4 -> 63.0 ms at S3.)  RDGPU_RFE_OVERLAP=0: one stream.
-    const bool beside = !env_is("RDGPU_RFE_OVERLAP", '0');
-    hipStream_t ls = s;
-    Workspace::SideLane *lane = nullptr;   // (lane 0: the labels; lane 1: the away search)
-    if (beside) {
-      lane = &ws.side_lane(0);
-      ls = lane->stream;
-      RD_HIP(hipEventRecord(lane->fork, s));   // (the DEM and the workspace are as the caller's stream left them)
-    }
-    const auto labels = [&]() {
-      if (beside) RD_HIP(hipStreamWaitEvent(ls, lane->fork, 0));
-      RD_LAUNCH("flats.ccl_tile", (k_ccl_tile<T>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, ls, d_z, L, w, h, tilesX, ntiles, colZ, colL);
-      const uint64_t nthreads = (uint64_t)ntiles * (CW + CH);
-      RD_LAUNCH("flats.ccl_border", (k_ccl_border2<T>), dim3((uint32_t)((nthreads + NTHR - 1) / NTHR)), dim3(NTHR), 0, ls, d_z, L,
-                (const T *)colZ, (const uint32_t *)colL, w, h, tilesX, ntiles);
-      RD_LAUNCH("flats.ccl_flatten", k_ccl_flatten4, dim3(sgrid(n / 4 + 3)), dim3(NTHR), 0, ls, L, fh, n);
-      if (beside) RD_HIP(hipEventRecord(lane->join, ls));
-    };
-    if (!beside) labels();
-    // ... the away search too, on a second side stream (see enqueue_away_static), only on request: with the labels already
-    // beside the tail a third stream gains nothing (S3: 58.7 ms without, 59.5 with; RDGPU_RFE_AWAY_BESIDE=1)
-    // (the edge counts come with the towards search's start levels, as on the directions path: no counting pass)
-    unsigned long long c3[3] = {0, 0, 0};
-    const bool away_too = beside && env_is("RDGPU_RFE_AWAY_BESIDE", '1') && away_beside();
-    Workspace::SideLane *alane = away_too ? &ws.side_lane(1) : nullptr;
-    StaticAway sa;
-    int32_t *A = nullptr;
-    Beside bs;
-    bs.mark = [&]() {
-      if (away_too) RD_HIP(hipEventRecord(alane->fork, s));
-    };
-    bool away_started = false;
-    bs.go = [&]() {
-      if (beside) labels();
-      if (away_too && c3[0] > 0 && c3[1] > 0) {
-        away_started = true;
-        RD_HIP(hipStreamWaitEvent(alane->stream, alane->fork, 0));
-        A = ws.buf<int32_t>("flats.away", n);
-        sa = enqueue_away_static(flags, A, w, h, alane->stream);
-        RD_HIP(hipEventRecord(alane->join, alane->stream));
-      }
-    };
-    g_fstats.towards_levels = run_bits_towards(flags, M, true, c3, w, h, s, &bs);
-    g_fstats.low_edges = c3[0];
-    g_fstats.high_edges = c3[1];
-    g_fstats.noflow_cells = c3[2];
-    if (away_started) {
-      RD_HIP(hipStreamWaitEvent(s, alane->join, 0));
-      g_fstats.away_levels = finish_static<1>(sa, A, AWAY_STATIC_ROUNDS, w, h, "flats.relax_away", s);
-    } else if (c3[0] > 0 && c3[1] > 0) {
-      A = ws.buf<int32_t>("flats.away", n);
-      g_fstats.away_levels = run_bits_away(flags, nullptr, nullptr, A, false, w, h, s);
-    }
-    if (beside) RD_HIP(hipStreamWaitEvent(s, lane->join, 0));
-    if (c3[0] == 0) return;   // no flats, or none with an outlet (:475-481): *outL stays null, nothing is altered
-    *outL = L;
-    *outFh = fh;
-    if (A) RD_LAUNCH("flats.height", k_flat_height4, dim3(sgrid(n / 4 + 3)), dim3(NTHR), 0, s, (const int32_t *)A, (const uint32_t *)L, fh, n);
-    *outA = A;
-    return;
-  }
+  *outL = L;
+  *outFh = fh;
   {
     const uint32_t tilesX = (w + CW - 1) / CW, ntiles = tilesX * ((h + CH - 1) / CH);
     RD_LAUNCH("flats.ccl_tile", (k_ccl_tile<T>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, L, w, h, tilesX, ntiles, (T *)nullptr,
@@ -2457,12 +2204,85 @@ static void resolve_flats_device(const T *d_z, const uint8_t *d_dirs, int w, int
   }
   // towards gradient from every low edge, then the combined mask in place
   g_fstats.towards_levels = run_bits_towards(flags, M, nhigh_all == 0, nullptr, w, h, s);
-  if (outA) {   // the caller combines on the fly (k_flat_epsilon): M holds the towards levels
-    *outA = A;
-    return;
-  }
   RD_LAUNCH("flats.combine", k_flat_combine, dim3(sgrid(n)), dim3(NTHR), 0, s, M, (const int32_t *)A, (const uint32_t *)L,
             (const int32_t *)fh, n);
+}
+
+// ResolveFlatsEpsilon's levels: FindFlats and the classification in one pass over the DEM (nodata: FindFlats'), the towards
+// levels in M (every cell written: DINF where the search does not reach), the away levels in A (null without high edges),
+// the labels in L and the flat heights in fh.  The caller combines on the fly (k_flat_epsilon4).  L, fh, A: null where no
+// flat has an outlet.
+template <class T>
+static void epsilon_levels_device(const T *d_z, T nodata, int w, int h, int32_t **outM, const int32_t **outA, uint32_t **outL,
+                                  int32_t **outFh, hipStream_t s) {
+  const uint64_t n = (uint64_t)w * h;
+  Workspace &ws = Workspace::get();
+  int32_t *M = ws.buf<int32_t>("flats.mask", n);
+  *outM = M;
+  *outA = nullptr;
+  *outL = nullptr;
+  *outFh = nullptr;
+  g_fstats = rdgpu_flat_stats{0, 0, 0, 0, 0};
+  g_async_info = AsyncInfo{0, 0, 0, 0};
+
+  uint8_t *flags = ws.buf<uint8_t>("flats.flags", n);
+  {
+    const uint32_t tilesX = (w + SW - 1) / SW, ntiles = tilesX * ((h + KLH - 1) / KLH);
+    RD_LAUNCH("flats.findflats_classify", (k_dirs_classify<T, false, true>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, nodata,
+              (uint8_t *)nullptr, flags, w, h, tilesX, ntiles);
+  }
+  // The caller wants the levels, the labels and the flat heights, nothing per flat beyond that: the labels do not depend on
+  // the searches here.  "The flat has an outlet" (:491-500) is what the towards levels say anyway (a flat without a low edge
+  // is never reached: its cells keep DINF and k_flat_epsilon4 skips them), so the away field starts from EVERY high edge and
+  // fh needs no "-1 = no outlet" marks: no k_flat_mark_low_flags pass, no fill of fh.
+  uint32_t *L = ws.buf<uint32_t>("flats.L", n);
+  int32_t *fh = ws.buf<int32_t>("flats.fh", n);
+  const uint32_t tilesX = (w + CW - 1) / CW, ntiles = tilesX * ((h + CH - 1) / CH);
+  T *colZ = ws.buf<T>("flats.colz", (size_t)ntiles * 2 * CH);
+  uint32_t *colL = ws.buf<uint32_t>("flats.coll", (size_t)ntiles * 2 * CH);
+  // ... and so they are made BESIDE the tail of the towards search, on the device's side stream (lane 0): the tail keeps two
+  // resident blocks per CU busy with dependent visits and leaves the memory system idle, the labelling is three streaming
+  // passes.  (Started with the search's first rounds, which are throughput-bound themselves, the labels only took their
+  // turn: 64.4 -> 63.0 ms at S3.)  RDGPU_RFE_OVERLAP=0: one stream.
+  const bool beside = !env_is("RDGPU_RFE_OVERLAP", '0');
+  hipStream_t ls = s;
+  Workspace::SideLane *lane = nullptr;
+  if (beside) {
+    lane = &ws.side_lane(0);
+    ls = lane->stream;
+    RD_HIP(hipEventRecord(lane->fork, s));   // (the DEM and the workspace are as the caller's stream left them)
+  }
+  const auto labels = [&]() {
+    if (beside) RD_HIP(hipStreamWaitEvent(ls, lane->fork, 0));
+    RD_LAUNCH("flats.ccl_tile", (k_ccl_tile<T>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, ls, d_z, L, w, h, tilesX, ntiles, colZ, colL);
+    const uint64_t nthreads = (uint64_t)ntiles * (CW + CH);
+    RD_LAUNCH("flats.ccl_border", (k_ccl_border2<T>), dim3((uint32_t)((nthreads + NTHR - 1) / NTHR)), dim3(NTHR), 0, ls, d_z, L,
+              (const T *)colZ, (const uint32_t *)colL, w, h, tilesX, ntiles);
+    RD_LAUNCH("flats.ccl_flatten", k_ccl_flatten4, dim3(sgrid(n / 4 + 3)), dim3(NTHR), 0, ls, L, fh, n);
+    if (beside) RD_HIP(hipEventRecord(lane->join, ls));
+  };
+  Beside bs;
+  if (beside) bs.go = labels;   // (called once: when the towards search reaches its tail, or ends in its rounds)
+  else labels();
+  // (the edge counts come with the towards search's start levels, as on the directions path: no counting pass)
+  unsigned long long c3[3] = {0, 0, 0};
+  g_fstats.towards_levels = run_bits_towards(flags, M, true, c3, w, h, s, &bs);
+  g_fstats.low_edges = c3[0];
+  g_fstats.high_edges = c3[1];
+  g_fstats.noflow_cells = c3[2];
+  // the away search after it, on the caller's stream (on a third stream beside the tail it was measured slower: S3 58.7 ms
+  // without, 59.5 with; docs/HISTORY.md)
+  int32_t *A = nullptr;
+  if (c3[0] > 0 && c3[1] > 0) {
+    A = ws.buf<int32_t>("flats.away", n);
+    g_fstats.away_levels = run_bits_away(flags, nullptr, nullptr, A, false, w, h, s);
+  }
+  if (beside) RD_HIP(hipStreamWaitEvent(s, lane->join, 0));
+  if (c3[0] == 0) return;   // no flats, or none with an outlet (:475-481): *outL stays null, nothing is altered
+  *outL = L;
+  *outFh = fh;
+  if (A) RD_LAUNCH("flats.height", k_flat_height4, dim3(sgrid(n / 4 + 3)), dim3(NTHR), 0, s, (const int32_t *)A, (const uint32_t *)L, fh, n);
+  *outA = A;
 }
 
 static thread_local bool g_planes_overflowed = false;   // (flat_resolution_device: this call repeats a plane search that overflowed)
@@ -2494,36 +2314,15 @@ void flat_resolution_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dir
   Workspace &ws = Workspace::get();
   g_fstats = rdgpu_flat_stats{0, 0, 0, 0, 0};
   g_async_info = AsyncInfo{0, 0, 0, 0};
-  // r05: the last pass from 4 bits per cell, without the DEM (k_flat_dirs_q; the cells next to a low edge get their direction
-  // in the classification); RDGPU_FLAT_Q=0: k_flat_dirs_levels over the level planes and the DEM (r02-r04): A/B and tests
-  const bool qpass = !env_is("RDGPU_FLAT_Q", '0');
   // r06: the level fields as bit planes per tile (flat_planes.inc); RDGPU_FLAT_PLANES=0, a level beyond 16 bits (an open flat
-  // wider than 65 000 cells), RDGPU_FLAT_Q=0 or RDGPU_FLAT_TRACE: one int per cell (r02-r05).  The plane engine takes its
-  // bitmaps and counts from the flag bytes, or straight from the classification (RDGPU_FLAT_CLASS_BITMAPS=1).
-  const bool planes = qpass && !env_is("RDGPU_FLAT_PLANES", '0') && !g_planes_overflowed && !getenv("RDGPU_FLAT_TRACE");
-  // (measured r06: the start kernels drop from 2.9 to 0.4 ms and 4.8 GB of flag traffic go away, but the classification itself
-  // goes from 4.9 to 6.6 ms with the ballots and row words in it -- 22.7 ms either way at S3; so the flags stay the default and
-  // RDGPU_FLAT_CLASS_BITMAPS=1 selects the bitmaps: profiles/r06f_flats_class_bitmaps_ab.json)
-  const bool class_bitmaps = planes && env_is("RDGPU_FLAT_CLASS_BITMAPS", '1');
-  uint8_t *flags = class_bitmaps ? nullptr : ws.buf<uint8_t>("flats.flags", n);
-  if (class_bitmaps) {
-    const BitsScratch bt = bits_scratch(w, h, false, true);
-    ClassBitmaps bm;
-    bm.rows = bt.mbits; bm.nrows = bt.ntiles * BT;
-    bm.counts = bt.counts; bm.tilesXb = bt.tilesX;
-    RD_HIP(hipMemsetAsync(bt.counts, 0, (3 * 256 + 8) * sizeof(uint32_t), s));
-    const uint32_t tilesX = (w + SW - 1) / SW, ntiles = tilesX * 2u * (uint32_t)((h + BT - 1) / BT);   // whole search tiles: their rows past the raster read as empty
-    RD_LAUNCH("flats.dirs_classify", (k_dirs_classify<T, true, false, true>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, nodata,
-              d_dirs, (uint8_t *)nullptr, w, h, tilesX, ntiles, bm);
-  } else {
-    const uint32_t tilesX = (w + SW - 1) / SW, ntiles = tilesX * ((h + KLH - 1) / KLH);
-    if (qpass)
-      RD_LAUNCH("flats.dirs_classify", (k_dirs_classify<T, true>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, nodata, d_dirs, flags,
-                w, h, tilesX, ntiles);
-    else
-      RD_LAUNCH("flats.dirs_classify", (k_dirs_classify<T>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, nodata, d_dirs, flags, w, h,
-                tilesX, ntiles);
-  }
+  // wider than 65 000 cells) or RDGPU_FLAT_TRACE: one int per cell (r02-r05).  Either engine takes its bitmaps and counts from
+  // the classification's flag bytes, and either last pass (r05) works from 4 bits per cell, without the DEM: the cells next to
+  // a low edge get their direction in the classification.
+  const bool planes = !env_is("RDGPU_FLAT_PLANES", '0') && !g_planes_overflowed && !getenv("RDGPU_FLAT_TRACE");
+  uint8_t *flags = ws.buf<uint8_t>("flats.flags", n);
+  const uint32_t tilesX = (w + SW - 1) / SW, ntiles = tilesX * ((h + KLH - 1) / KLH);
+  RD_LAUNCH("flats.dirs_classify", (k_dirs_classify<T, true>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, nodata, d_dirs, flags, w,
+            h, tilesX, ntiles);
   int32_t *TWd = planes ? nullptr : ws.buf<int32_t>("flats.mask", n), *A = nullptr;
   // RDGPU_FLAT_STATIC=0: the towards search in batches of rounds decided on the host (r02-r05): A/B and tests
   if (planes && away_beside() && !env_is("RDGPU_FLAT_STATIC", '0')) {
@@ -2602,13 +2401,8 @@ void flat_resolution_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dir
     launch_dirs_qp(bt, ba, have_away ? 1 : 0, d_dirs, w, h, s);
     return;
   }
-  const uint32_t tilesX = (w + SW - 1) / SW, ntiles = tilesX * ((h + KLH - 1) / KLH);
-  if (qpass)
-    RD_LAUNCH("flats.dirs_q", k_flat_dirs_q, dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, (const int32_t *)TWd, (const int32_t *)A, d_dirs,
-              w, h, tilesX, ntiles);
-  else
-    RD_LAUNCH("flats.dirs_levels", (k_flat_dirs_levels<T>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, (const int32_t *)TWd,
-              (const int32_t *)A, d_dirs, w, h, tilesX, ntiles);
+  RD_LAUNCH("flats.dirs_q", k_flat_dirs_q, dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, (const int32_t *)TWd, (const int32_t *)A, d_dirs, w,
+            h, tilesX, ntiles);
 }
 
 template <class T>
@@ -3053,50 +2847,14 @@ static void fs_heights(rdgpu_flat_shard *f, int32_t *d_out) {
 // ResolveFlatsEpsilon (flats/flats.hpp:21-28) = FindFlats (flats/find_flats.hpp:29-69) + GetFlatMask
 // (flats/Barnes2014.hpp:398-467) + ResolveFlatsEpsilon_Barnes2014 (:496-550): what rd.ResolveFlats calls.
 // GetFlatMask is the same BFS construction as resolve_flats_barnes, applied to FindFlats' notion of a flat
-// cell (interior, no lower neighbour AND no NoData neighbour).  So FindFlats is written as a pseudo direction
-// raster (0 = flat, 1 = not, 255 = NoData) and the engine above runs unchanged -- the two facts it leans on
-// (adjacent flat cells have equal elevation; drainable <=> reached by the towards gradient) hold for this
-// definition too.  Then every interior cell with flat_mask > 0 is raised by flat_mask increments of
+// cell (interior, no lower neighbour AND no NoData neighbour).  So FindFlats is a pseudo direction raster (0 = flat,
+// 1 = not, 255 = NoData; k_dirs_classify<FINDFLATS> forms it in LDS) and the engine above runs unchanged -- the two
+// facts it leans on (adjacent flat cells have equal elevation; drainable <=> reached by the towards gradient) hold for
+// this definition too.  Then every interior cell with flat_mask > 0 is raised by flat_mask increments of
 // std::nextafter(e, numeric_limits<T>::infinity()) in ITS OWN type: float and double in closed form on the bit
 // pattern; for integer T that "infinity" is 0 and the arguments promote to double, so one step moves the value
 // by one towards zero -- reproduced as is (it is what the reference returns).
 // ------------------------------------------------------------------------------------------
-template <class T>
-__global__ __launch_bounds__(NTHR) void k_find_flats(const T *__restrict__ z, T nodata, uint8_t *__restrict__ flats, int w,
-                                                     int h, uint32_t tilesX, uint32_t ntiles) {
-  __shared__ T sz[SLH * SLW];
-  const uint32_t t = xcd_tile(blockIdx.x, ntiles);
-  if (t >= ntiles) return;
-  const int x0 = (int)(t % tilesX) * SW, y0 = (int)(t / tilesX) * SH;
-  for (int i = threadIdx.x; i < SLH * SLW; i += NTHR) {
-    const int ly = i / SLW, lx = i - ly * SLW;
-    const int gx = min(max(x0 - 1 + lx, 0), w - 1), gy = min(max(y0 - 1 + ly, 0), h - 1);   // clamped: edge cells are decided by position
-    sz[i] = z[(size_t)gy * w + gx];
-  }
-  __syncthreads();
-  const int lx = threadIdx.x & (SW - 1), ly0 = threadIdx.x >> 6;
-  const int off[9] = {0, -1, -SLW - 1, -SLW, -SLW + 1, 1, SLW + 1, SLW, SLW - 1};
-#pragma unroll
-  for (int j = 0; j < SH / 4; j++) {
-    const int ly = ly0 + 4 * j, gx = x0 + lx, gy = y0 + ly;
-    if (gx >= w || gy >= h) continue;
-    const int o = (ly + 1) * SLW + lx + 1;
-    const T e = sz[o];
-    uint8_t f;
-    if (e == nodata) f = 255;                                                  // find_flats.hpp:43-46
-    else if (gx == 0 || gy == 0 || gx == w - 1 || gy == h - 1) f = 1;          // :48-51
-    else {
-      f = 0;
-#pragma unroll
-      for (int k = 1; k <= 8; k++) {
-        const T zn = sz[o + off[k]];
-        if (zn < e || zn == nodata) f = 1;                                     // :56-63
-      }
-    }
-    flats[(size_t)gy * w + gx] = f;
-  }
-}
-
 __device__ __forceinline__ double next_up_n64(double v, uint32_t m) {   // nextafter(v, +inf) applied m times
   uint64_t b = __builtin_bit_cast(uint64_t, v);
   if ((b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) return v;    // NaN
@@ -3206,20 +2964,10 @@ void resolve_flats_epsilon_device(T *d_z, T nodata, int w, int h, hipStream_t s)
   if (!d_z) throw Error(RDGPU_ERR_ARG, "rdgpu_resolve_flats_epsilon: null pointer");
   if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_resolve_flats_epsilon: width and height must be positive");
   if ((uint64_t)w * (uint64_t)h > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, "rdgpu_resolve_flats_epsilon: raster too large");
-  // r05: on the lean path (the default) FindFlats is part of the classification pass; RDGPU_RFE_LEAN=0: k_find_flats
-  // writes the pseudo direction raster first
-  uint8_t *flats = nullptr;
-  if (!lean_labels()) {
-    flats = Workspace::get().buf<uint8_t>("flats.findflats", (size_t)w * h);
-    uint32_t tilesX;
-    const uint32_t ntiles = stencil_tiles(w, h, &tilesX);
-    RD_LAUNCH("flats.find_flats", (k_find_flats<T>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, (const T *)d_z, nodata, flats, w, h,
-              tilesX, ntiles);
-  }
   int32_t *M, *fh;
   uint32_t *L;
-  const int32_t *A = nullptr;
-  resolve_flats_device<T>(d_z, flats, w, h, &M, &L, &fh, s, &A, nodata);
+  const int32_t *A;
+  epsilon_levels_device<T>(d_z, nodata, w, h, &M, &A, &L, &fh, s);
   if (L) {
     if (reinterpret_cast<uintptr_t>(d_z) % 16 == 0)
       RD_LAUNCH("flats.epsilon", (k_flat_epsilon4<T>), dim3(sgrid((uint64_t)w * h / 4 + 3)), dim3(NTHR), 0, s, d_z, (const int32_t *)M, A,

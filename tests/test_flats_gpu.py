@@ -138,13 +138,14 @@ def test_single_device_and_row_block_shards_agree(rd, orc):
 
 
 @pytest.mark.parametrize("switch", ["RDGPU_FLAT_ASYNC=0", "RDGPU_FLAT_ASYNC=100000", "RDGPU_FLAT_AWAY_BESIDE=0", "RDGPU_FLAT_ASYNC_BLOCKS=3",
-                                    "RDGPU_RFE_LEAN=0", "RDGPU_RFE_OVERLAP=0", "RDGPU_RFE_AWAY_BESIDE=1", "RDGPU_FLAT_ASYNC_FAIL=1",
-                                    "RDGPU_FLAT_Q=0", "RDGPU_FLAT_PLANES=0", "RDGPU_FLAT_PLANES_MAX=40", "RDGPU_FLAT_CLASS_BITMAPS=1", "RDGPU_FLAT_STATIC=0"])
+                                    "RDGPU_RFE_OVERLAP=0", "RDGPU_FLAT_ASYNC_FAIL=1",
+                                    "RDGPU_FLAT_PLANES=0", "RDGPU_FLAT_PLANES_MAX=40", "RDGPU_FLAT_STATIC=0"])
 def test_search_schedules_give_the_same_levels(rd, orc, monkeypatch, switch):
     """The bitmap search in rounds to the end, with its asynchronous tail from the first batch on (k_relax_bits_async),
-    with the away search after instead of beside the towards tail, on three resident blocks; ResolveFlatsEpsilon with the
-    older label path, on one stream, on three; a tail that is declared failed and finished in rounds from every tile
-    (RDGPU_FLAT_ASYNC_FAIL): the fixed point does not depend on the schedule -- directions and
+    with the away search after instead of beside the towards tail, on three resident blocks; ResolveFlatsEpsilon with its
+    labels on one stream; a tail that is declared failed and finished in rounds from every tile (RDGPU_FLAT_ASYNC_FAIL); the
+    int engine, a plane search that overflows, the towards search in batches of rounds decided on the host: the fixed point
+    does not depend on the schedule -- directions and
     epsilon-resolved elevations equal the oracle's under every switch, on lakes that span many 64 x 64 tiles."""
     k, v = switch.split("=")
     dem = orc.port.fill(fractal_dem_int(1300, 900, 73, 0.01))
@@ -196,8 +197,8 @@ def test_level_planes_long_channels_and_overflow(rd, orc, monkeypatch):
 def test_directions_from_masks_modulo_8(rd, orc, monkeypatch):
     """r05: the directions-only entry derives the directions from the two level planes alone, as masks modulo 8 (adjacent
     cells of a flat differ by at most one level in either field), cells next to a low edge getting theirs in the
-    classification pass; RDGPU_FLAT_Q=0 is the r02-r04 pass that also reads and compares the DEM.
-    Both equal the oracle: plateaus whose levels run far past 4 and past 256, a flat with an island of higher ground (high
+    classification pass.
+    They equal the oracle's: plateaus whose levels run far past 4 and past 256, a flat with an island of higher ground (high
     edges inside), flats without an outlet (no direction), NoData beside flats, flats wider than a tile and crossing the tile
     borders at every offset, under both search schedules."""
     rng = np.random.default_rng(91)
@@ -225,7 +226,7 @@ def test_directions_from_masks_modulo_8(rd, orc, monkeypatch):
     for name, dem in cases.items():
         nd = dem.dtype.type(-9999)
         exp = orc.port.flat_resolution(dem, nd)
-        for sw in (None, "RDGPU_FLAT_Q=0", "RDGPU_FLAT_ASYNC=0", "RDGPU_FLAT_ASYNC=100000"):
+        for sw in (None, "RDGPU_FLAT_ASYNC=0", "RDGPU_FLAT_ASYNC=100000"):
             if sw:
                 monkeypatch.setenv(*sw.split("="))
             got = rd.barnes_flat_resolution_d8(dem, nd)

@@ -917,6 +917,53 @@ RDGPU_DECL_HAND(f32, float)
 RDGPU_DECL_HAND(f64, double)
 #undef RDGPU_DECL_HAND
 
+/* ---- depression inventory: labels and one record per depression of the fill --------------------
+ * No reference counterpart (the flat inventory of the lakes FillDepressions produces; the depression hierarchy is not
+ * built).  Let W = FillDepressions<topology>(dem) exactly as rdgpu_fill_<T> computes it; NoData is an elevation like any
+ * other, as in that entry.  A cell is RAISED iff W > dem.  A DEPRESSION is a connected component of the raised cells
+ * under `topology` (8 or 4, the one used for the fill).  Adjacent raised cells share one W: the depression's level.
+ *   labels  int32 per cell (nullable): 0 on un-raised cells, 1..N on depressions, numbered by ascending lowest raster
+ *           index (y * width + x) of their cells -- independent of any execution order.  Always complete.
+ *   table   (nullable) record i describes label i + 1; at most `capacity` records are written, the first ones by label.
+ *   count   N, always the true number whatever the capacity.  table == NULL with capacity == 0 is the sizing call.
+ * Integer element types sum `volume` in 64-bit integers and convert once (exact below 2^53).  f32 / f64 sum it in
+ * double in no fixed order: its last bits are NOT reproducible from run to run; every term is non-negative, so
+ * |volume - exact sum| <= cells * 2^-52 * (exact sum).  Every other field is exact and reproducible.
+ * f64 runs on the dense value ranks of the raster (structure) and gathers level, pit_elevation and volume from the
+ * original values.  The i64 / u64 entries exist and return RDGPU_ERR_UNSUPPORTED: a double cannot carry their
+ * elevations or volumes exactly.  Argument checks and size limits are those of rdgpu_fill_<T>; a null count, or a null
+ * table with a non-zero capacity, is RDGPU_ERR_ARG.  A DEM with nothing to raise gives all-zero labels and count 0.
+ * The _dev forms take device pointers (d_count one device word) and are ordered on hip_stream; like
+ * rdgpu_fill_max_dep_dev_<T> they add no wait of their own to those of the fill's local phase.  Scratch comes from the
+ * workspace pool under names starting with "depr.". */
+typedef struct rdgpu_depression {
+  uint32_t first_cell;    /* lowest raster index in the depression */
+  uint32_t pit_cell;      /* index of its lowest dem value; the lowest index among equal values */
+  uint32_t outlet_cell;   /* lowest raster index among the UN-raised cells adjacent (by topology) to the depression
+                             with dem == level: where the flood enters it */
+  uint32_t cells;         /* number of cells */
+  double level;           /* (double)dem[outlet_cell] = W on every cell of the depression */
+  double pit_elevation;   /* (double)dem[pit_cell] */
+  double volume;          /* sum over the cells of (level - dem), in elevation units x cells */
+} rdgpu_depression;
+#define RDGPU_DECL_DEPR(SUF, T)                                                                                        \
+  int rdgpu_depressions_##SUF(const T *dem, int width, int height, int topology, int32_t *labels /* nullable */,      \
+                              rdgpu_depression *table /* nullable */, uint32_t capacity, uint32_t *count);            \
+  int rdgpu_depressions_dev_##SUF(const T *d_dem, int width, int height, int topology, int32_t *d_labels /* nullable */, \
+                                  rdgpu_depression *d_table /* nullable */, uint32_t capacity, uint32_t *d_count,     \
+                                  void *hip_stream);
+RDGPU_DECL_DEPR(u8, uint8_t)
+RDGPU_DECL_DEPR(i8, int8_t)
+RDGPU_DECL_DEPR(i16, int16_t)
+RDGPU_DECL_DEPR(u16, uint16_t)
+RDGPU_DECL_DEPR(i32, int32_t)
+RDGPU_DECL_DEPR(u32, uint32_t)
+RDGPU_DECL_DEPR(f32, float)
+RDGPU_DECL_DEPR(f64, double)
+RDGPU_DECL_DEPR(i64, int64_t)   /* RDGPU_ERR_UNSUPPORTED */
+RDGPU_DECL_DEPR(u64, uint64_t)  /* RDGPU_ERR_UNSUPPORTED */
+#undef RDGPU_DECL_DEPR
+
 /* ---- synthetic input (test/bench input generator) ----------- */
 int rdgpu_synth_dem_dev_f32(float *d_dem, int width, int height, int seed, int x0, int y0,
                             float tilt, void *hip_stream);

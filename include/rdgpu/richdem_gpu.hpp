@@ -836,4 +836,38 @@ void d8_hand(const E &dem, const F &flowdirs, G &hand) {
   d8_hand(dem, flowdirs, hand, static_cast<const F *>(nullptr));
 }
 
+// ---- depression inventory (no reference counterpart; the definition is in rdgpu.h) ----------------------------------
+namespace detail {
+#define RDGPU_SHIM_DEPR(SUF, T)                                                                                            \
+  inline int c_depressions(const T *z, int w, int h, int t, int32_t *l, rdgpu_depression *tab, uint32_t cap, uint32_t *n) { \
+    return rdgpu_depressions_##SUF(z, w, h, t, l, tab, cap, n);                                                            \
+  }
+RDGPU_SHIM_DEPR(u8, uint8_t) RDGPU_SHIM_DEPR(i8, int8_t) RDGPU_SHIM_DEPR(u16, uint16_t) RDGPU_SHIM_DEPR(i16, int16_t)
+RDGPU_SHIM_DEPR(u32, uint32_t) RDGPU_SHIM_DEPR(i32, int32_t) RDGPU_SHIM_DEPR(f32, float) RDGPU_SHIM_DEPR(f64, double)
+#undef RDGPU_SHIM_DEPR
+template <class T>
+int c_depressions(const T *, int, int, int, int32_t *, rdgpu_depression *, uint32_t, uint32_t *) { unsupported("Depressions"); }
+}  // namespace detail
+
+// labels <- 0 on the cells FillDepressions<topo> leaves alone, 1..N on the lakes it fills (numbered by their lowest raster
+// index); table[i] describes label i + 1.  NoData is an elevation like any other, as in FillDepressions.  labels takes the
+// DEM's size, geotransform and projection, NoData 0.  Two calls of the engine: the sizing call, then the full one.
+template <auto topo, class A, class L>
+void Depressions(const A &dem, L &labels, std::vector<rdgpu_depression> &table) {
+  using T = detail::elem_t<const A>;
+  static_assert(std::is_same<detail::elem_t<L>, int32_t>::value, "Depressions: the label raster must be int32_t");
+  labels.resize(dem, 0);
+  labels.setNoData(0);
+  table.clear();
+  if (dem.width() == 0 || dem.height() == 0) return;
+  uint32_t n = 0;
+  detail::check(detail::c_depressions((const T *)dem.data(), dem.width(), dem.height(), detail::topology_code<topo>(), nullptr,
+                                      nullptr, 0, &n), "Depressions");
+  table.resize(n);
+  uint32_t got = 0;
+  detail::check(detail::c_depressions((const T *)dem.data(), dem.width(), dem.height(), detail::topology_code<topo>(),
+                                      labels.data(), n ? table.data() : nullptr, n, &got), "Depressions");
+  if (got != n) throw std::runtime_error("Depressions: the count changed between the sizing call and the full call");
+}
+
 }  // namespace rdgpu

@@ -1270,3 +1270,76 @@ def d8_hand_dev(dem, dirs, dem_nodata, out, dir_nodata: int = 255, channels=None
                                                    ctypes.c_void_p(dem.data_ptr()), _scalar(s, dem_nodata), w, h,
                                                    _dev_mask(channels, (h, w), "d8_hand_dev"), ctypes.c_void_p(out.data_ptr()),
                                                    ctypes.c_double(out_nodata), _stream_ptr()), "rdgpu_d8_hand_dev")
+
+
+# ---- depression inventory: labels and one record per depression of the fill -------------------------------------
+DEPRESSION_DTYPE = np.dtype([("first_cell", np.uint32), ("pit_cell", np.uint32), ("outlet_cell", np.uint32), ("cells", np.uint32),
+                             ("level", np.float64), ("pit_elevation", np.float64), ("volume", np.float64)])   # rdgpu_depression
+
+
+def depressions_into(dem: np.ndarray, labels: np.ndarray | None, table: np.ndarray | None, topology="D8") -> int:
+    """One call of ``rdgpu_depressions_<T>``: ``labels`` (int32, the DEM's shape) and the first ``len(table)`` records of
+    ``table`` (``DEPRESSION_DTYPE``) are written where given; returns the number of depressions, whatever the capacity."""
+    if not isinstance(dem, np.ndarray) or dem.ndim != 2:
+        raise RdgpuError("depressions: expected a 2-D numpy array")
+    dem = np.ascontiguousarray(dem)
+    s = _suffix(dem.dtype)
+    h, w = dem.shape
+    if labels is not None and not (isinstance(labels, np.ndarray) and labels.dtype == np.int32 and labels.shape == (h, w)
+                                   and labels.flags["C_CONTIGUOUS"]):
+        raise RdgpuError("depressions: labels must be a C-contiguous int32 array of the DEM's shape")
+    if table is not None and not (isinstance(table, np.ndarray) and table.dtype == DEPRESSION_DTYPE and table.ndim == 1
+                                  and table.flags["C_CONTIGUOUS"]):
+        raise RdgpuError("depressions: table must be a C-contiguous 1-D array of DEPRESSION_DTYPE")
+    count = ctypes.c_uint32(0)
+    check(getattr(lib(), f"rdgpu_depressions_{s}")(dem.ctypes.data_as(ctypes.c_void_p), w, h, _topo(topology),
+                                                   None if labels is None else labels.ctypes.data_as(ctypes.c_void_p),
+                                                   None if table is None or len(table) == 0 else table.ctypes.data_as(ctypes.c_void_p),
+                                                   ctypes.c_uint32(0 if table is None else len(table)), ctypes.byref(count)),
+          "rdgpu_depressions")
+    return int(count.value)
+
+
+def depressions(dem: np.ndarray, topology="D8", labels: bool = True):
+    """The depressions ``FillDepressions(dem, topology=...)`` fills: ``(labels, table)``.  ``labels`` (int32; ``None`` when
+    not asked for) is 0 on cells the fill leaves alone and 1..N on its lakes, numbered by their lowest raster index;
+    ``table[i]`` (``DEPRESSION_DTYPE``) describes label ``i + 1``: first, pit and outlet cell (raster indices), cells,
+    level, pit elevation and volume (elevation units x cells).  NoData is an elevation like any other.  Two calls: the
+    sizing call, then the one that fills the table."""
+    n = depressions_into(dem, None, None, topology)
+    lab = np.empty(dem.shape, np.int32) if labels else None
+    table = np.zeros(n, DEPRESSION_DTYPE)
+    got = depressions_into(dem, lab, table, topology)
+    if got != n:
+        raise RdgpuError(f"depressions: the count changed between the two calls ({n} -> {got})")
+    return lab, table
+
+
+def depressions_dev(dem, labels, table, topology="D8"):
+    """The same on HBM-resident tensors, on torch's current stream: ``labels`` an int32 CUDA tensor of the DEM's shape or
+    ``None``; ``table`` a contiguous CUDA tensor of any element type holding 40 bytes per record (its capacity is its size
+    in bytes // 40; ``.cpu().numpy().view(DEPRESSION_DTYPE)`` reads it) or ``None``.  Returns a one-element int32 CUDA
+    tensor that holds the number of depressions once the stream gets there."""
+    import torch
+
+    h, w = _dev2d(dem, "depressions_dev")
+    m = {torch.int8: "i8", torch.uint8: "u8", torch.int16: "i16", torch.int32: "i32", torch.float32: "f32", torch.float64: "f64",
+         torch.int64: "i64"}
+    for name, s in (("uint16", "u16"), ("uint32", "u32"), ("uint64", "u64")):
+        if hasattr(torch, name):
+            m[getattr(torch, name)] = s
+    if dem.dtype not in m:
+        raise RdgpuError(f"depressions_dev: unsupported elevation dtype {dem.dtype}")
+    if labels is not None and tuple(_dev2d(labels, "depressions_dev", torch.int32)) != (h, w):
+        raise RdgpuError("depressions_dev: shape mismatch")
+    cap = 0
+    if table is not None:
+        if not (table.is_cuda and table.is_contiguous()):
+            raise RdgpuError("depressions_dev: expected a contiguous table tensor on the GPU")
+        cap = table.numel() * table.element_size() // DEPRESSION_DTYPE.itemsize
+    count = torch.zeros(1, dtype=torch.int32, device=dem.device)
+    check(getattr(lib(), f"rdgpu_depressions_dev_{m[dem.dtype]}")(
+        ctypes.c_void_p(dem.data_ptr()), w, h, _topo(topology), None if labels is None else ctypes.c_void_p(labels.data_ptr()),
+        None if cap == 0 else ctypes.c_void_p(table.data_ptr()), ctypes.c_uint32(cap), ctypes.c_void_p(count.data_ptr()),
+        _stream_ptr()), "rdgpu_depressions_dev")
+    return count

@@ -27,6 +27,7 @@
 // All elevation work is on order-preserving 32-bit keys (common.hpp Key32), so it is exact for
 // u8/i16/u16/i32/u32/f32.  HBM-bound integer/compare work: no MFMA anywhere.
 #include "common.hpp"
+#include "fill_shared.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -40,7 +41,6 @@ constexpr int TW = 64;        // tile width  (cells)  = one wavefront per tile r
 constexpr int TH = 32;        // tile height (cells)
 constexpr int LW = TW + 2;    // LDS row stride incl. 1-cell halo (66 words: conflict-free rows)
 constexpr int LH = TH + 2;
-constexpr int NTHR = 256;     // 4 wavefronts
 constexpr uint32_t OUTP = 0xFFFFFFFFu;  // descent pointer of a border cell: drains off the raster
 // Component ids carry CLOSED in the top bit when the component never hooks again: the outside (B) and,
 // in a row-block shard, the frozen terminal basins of the cut rows (Barnes 2016 tile protocol).
@@ -1437,37 +1437,6 @@ __global__ __launch_bounds__(NTHR) void k_shard_apply(const uint32_t *__restrict
 // ------------------------------------------------------------------------------------------
 // host driver
 // ------------------------------------------------------------------------------------------
-static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
-
-// Device buffers that outlive the local phase.
-struct FillBuffers {
-  uint32_t *lab = nullptr, *cur = nullptr, *acc = nullptr, *tid = nullptr;
-  uint32_t B = 0;
-  bool trivial = false;   // nothing to raise (no interior, or no pits)
-  // the compact-label local phase of a row-block shard (r04): no 32-bit label per cell, but the 16-bit slots, the tiles'
-  // node bases and counts, node -> basin (curN), and per node its level (lvl) and watershed terminal (nodeW)
-  bool compact = false;
-  uint16_t *lab16 = nullptr;
-  uint32_t *tile_base = nullptr, *tile_count = nullptr, *curN = nullptr, *lvl = nullptr, *nodeW = nullptr;
-  unsigned long long *counters = nullptr;
-  uint32_t rcap = 0, nstripes = 0, nnmax = 0;
-};
-
-struct BufAlloc {   // where persistent buffers come from: the shared workspace, or owned hipMalloc
-  bool owned;
-  std::vector<void *> *owned_list;
-  bool shard_ws = false;   // workspace buffers under their own names ("shard." + name): the one cached shard
-  template <class U>
-  U *get(const char *name, size_t count) {
-    if (!owned && shard_ws) return Workspace::get().buf<U>((std::string("shard.") + name).c_str(), count);
-    if (!owned) return Workspace::get().buf<U>(name, count);
-    void *p = nullptr;
-    RD_HIP(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(U)));
-    owned_list->push_back(p);
-    return static_cast<U *>(p);
-  }
-};
-
 // Phases 1-4: descent forest, basins, Boruvka rounds.  With open_top/open_bottom the first/last row is
 // a cut row of a row-block shard whose cells are frozen terminals.
 template <class T, int TOPO>
@@ -1647,6 +1616,21 @@ static void fill_local_phase(const T *d_z, int w, int h, int open_top, int open_
   }
 }
 
+// The local phase of a whole raster on workspace buffers, for the other files of the library (fill_shared.hpp).
+template <class T>
+void fill_local_phase_plain(const T *d_z, int w, int h, int topology, FillBuffers &fb, hipStream_t s) {
+  BufAlloc ws_alloc{false, nullptr};
+  if (topology == 8) fill_local_phase<T, 8>(d_z, w, h, 0, 0, ws_alloc, fb, s);
+  else fill_local_phase<T, 4>(d_z, w, h, 0, 0, ws_alloc, fb, s);
+}
+template void fill_local_phase_plain<uint8_t>(const uint8_t *, int, int, int, FillBuffers &, hipStream_t);
+template void fill_local_phase_plain<int8_t>(const int8_t *, int, int, int, FillBuffers &, hipStream_t);
+template void fill_local_phase_plain<int16_t>(const int16_t *, int, int, int, FillBuffers &, hipStream_t);
+template void fill_local_phase_plain<uint16_t>(const uint16_t *, int, int, int, FillBuffers &, hipStream_t);
+template void fill_local_phase_plain<int32_t>(const int32_t *, int, int, int, FillBuffers &, hipStream_t);
+template void fill_local_phase_plain<uint32_t>(const uint32_t *, int, int, int, FillBuffers &, hipStream_t);
+template void fill_local_phase_plain<float>(const float *, int, int, int, FillBuffers &, hipStream_t);
+
 // The same in tile order (64 x 32 tiles, XCD-banded, aligned quads): the cells of a tile share a few dozen basins, so
 // the acc[] lines stay in the XCD's L2 while the tile is worked on -- in row order every row segment of a basin
 // fetched its line again (5.5 GB of gathers on top of 12.8 GB of rows at S3).  A quad is written back only when one of
@@ -1707,12 +1691,6 @@ static void fill_finalize(T *d_z, int w, int h, const FillBuffers &fb, hipStream
 // a shard's finish on compact labels: the nodes' levels from the (raised) basin levels, then the raster pass
 template <class T>
 static void fill_finalize16(T *d_z, int w, int h, const FillBuffers &fb, hipStream_t s);
-
-static void check_fill_args(const void *p, int w, int h, int topology) {
-  if (!p) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: null DEM pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: width and height must be positive");
-  if (topology != 8 && topology != 4) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: topology must be 8 or 4");  // depressions.hpp:19-20
-}
 
 // pit_mask<topo>(elevations, pit_mask) (reference depressions/Barnes2014.hpp:593-676; apps/rd_depressions_mask.cpp):
 // the same flood, recording which cells it would raise instead of raising them.  1 = the cell lies strictly below the
@@ -1785,26 +1763,6 @@ static void pit_mask_host(const T *dem, T nodata, int w, int h, int topology, ui
 // On a DEM without equal elevations that cell, the highest un-raised one, cannot have started a run: a pocket has more
 // than one rim cell and all of them would have to be the highest cell.)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t md_find(uint32_t *par, uint32_t x) {
-  uint32_t p = __hip_atomic_load(&par[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  while (p != x) {
-    x = p;
-    p = __hip_atomic_load(&par[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  return x;
-}
-__device__ __forceinline__ void md_unite(uint32_t *par, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = md_find(par, a);
-    b = md_find(par, b);
-    if (a == b) return;
-    if (a < b) { const uint32_t t = a; a = b; b = t; }   // hook the larger root under the smaller: acyclic under any interleaving
-    const uint32_t old = atomicMin(&par[a], b);
-    if (old == a) return;
-    a = old;
-  }
-}
-
 __global__ __launch_bounds__(NTHR) void k_md_init(uint32_t *par, uint32_t *cnt, uint32_t *spawn, uint32_t *size, uint32_t B) {
   const uint32_t b = blockIdx.x * NTHR + threadIdx.x;
   if (b >= B) return;
@@ -1852,39 +1810,6 @@ __global__ __launch_bounds__(NTHR) void k_md_pockets(const T *__restrict__ z, co
       const int stop = notr ? lane + __ffsll((long long)notr) : 64;
       const int end = next < stop ? next : stop;
       atomicAdd(&cnt[b], (uint32_t)(end - lane));
-    }
-  }
-}
-
-template <class T, int TOPO, int PASS>
-__global__ __launch_bounds__(NTHR) void k_md_spawn(const T *__restrict__ z, const uint32_t *__restrict__ lab,
-                                                   const uint32_t *__restrict__ acc, uint32_t *par, uint32_t *spawn, int w,
-                                                   int h, uint32_t B) {
-  const uint64_t n = (uint64_t)w * h, stride = (uint64_t)gridDim.x * NTHR;
-  for (uint64_t c = (uint64_t)blockIdx.x * NTHR + threadIdx.x; c < n; c += stride) {
-    const uint32_t b = lab[c];
-    const uint32_t kz = Key32<T>::to(z[c]);
-    if (b != B && acc[b] > kz) continue;   // raised cells are flooded, they do not flood
-    const int x = (int)(c % (uint64_t)w), y = (int)(c / (uint64_t)w);
-    uint32_t first = 0xFFFFFFFFu;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      if (TOPO == 4 && (k & 1)) continue;
-      const int dx[8] = {-1, -1, 0, 1, 1, 1, 0, -1}, dy[8] = {0, -1, -1, -1, 0, 1, 1, 1};
-      const int xx = x + dx[k], yy = y + dy[k];
-      if (xx < 0 || xx >= w || yy < 0 || yy >= h) continue;
-      const size_t q = (size_t)yy * w + xx;
-      const uint32_t bq = lab[q];
-      if (bq == B) continue;
-      const uint32_t L = acc[bq];
-      if (L != kz || !(L > Key32<T>::to(z[q]))) continue;   // a raised neighbour filled to exactly this cell's elevation
-      const uint32_t r = md_find(par, bq);
-      if (PASS == 0) {
-        if ((uint32_t)c < __hip_atomic_load(&spawn[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&spawn[r], (uint32_t)c);
-      } else if (__hip_atomic_load(&spawn[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)c) {
-        if (first == 0xFFFFFFFFu) first = r;
-        else md_unite(par, first, r);        // the pockets this cell floods are one run
-      }
     }
   }
 }

@@ -10,6 +10,7 @@
 //     filled ranks back through the table of distinct keys.
 // A cell is rewritten only when its level changed, so untouched cells keep their input bits.
 #include "common.hpp"
+#include "fill_shared.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -22,8 +23,6 @@ extern "C" int rdgpu_pit_mask_dev_u32(const uint32_t *, uint32_t, int, int, int,
 extern "C" int rdgpu_watersheds_dev_u32(uint32_t *, uint32_t, int, int, int, int, int32_t *, void *);
 
 namespace rdgpu {
-
-constexpr int NTHR = 256;
 
 template <class T>
 struct Key64;
@@ -222,6 +221,14 @@ static void pf_flowdirs64_device(const T *d_z, T nodata, int w, int h, uint8_t *
   const Ranks r = dense_ranks<T>(d_z, (uint64_t)w * h, s);
   const int rc = rdgpu_pf_flowdirs_dev_u32(r.rk, nodata_rank<T>(r, nodata, s), w, h, d_dirs, s);
   if (rc) throw Error(rc, rdgpu_last_error());
+}
+
+// The depression inventory (depressions.hip): structure from the rank raster, values gathered from the original raster.
+void depressions_f64_device(const double *d_z, int w, int h, int topology, int32_t *d_labels, rdgpu_depression *d_table,
+                            uint32_t capacity, uint32_t *d_count, hipStream_t s) {
+  check64(d_z, w, h, topology, "rdgpu_depressions");
+  const Ranks r = dense_ranks<double>(d_z, (uint64_t)w * h, s);
+  depressions_on_ranks(r.rk, r.uniq, d_z, w, h, topology, d_labels, d_table, capacity, d_count, s);
 }
 
 // PriorityFlood_Wei2018 (depressions/Wei2018.hpp:154-202) compares and copies elevations and tests cells against NoData:

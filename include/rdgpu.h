@@ -818,6 +818,46 @@ int rdgpu_d8_upslope_cells_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int wi
                                uint8_t *d_out, void *hip_stream);
 int rdgpu_d8_upslope_line(int width, int height, int x0, int y0, int x1, int y1, uint32_t *cells, uint32_t capacity, uint32_t *n);
 
+/* ---- upslope extremes: the largest or smallest value over each cell's drainage area ------------
+ * No reference counterpart (TauDEM ships it as "D8 Extreme Upslope Value").  Directions are uint8 D8 codes (0 NO_FLOW,
+ * 1..8 index the neighbour in the reference's dx / dy tables, dir_nodata); values is a raster of T of the same size.
+ *   A cell PARTICIPATES iff dirs != dir_nodata.  A participating cell CONTRIBUTES iff its value is not value_nodata
+ *   (compared with == in T: -0.0f equals a NoData of 0.0f) and, for f32, is not a NaN (a NaN never contributes, whatever
+ *   value_nodata is).
+ *   The LINK of a participating cell c exists iff its code is 1..8, its target lies in the raster and the target
+ *   participates; otherwise c's tree ends at c.
+ *   U(v), the upslope set of a participating cell v, is the set of participating cells whose chain of links reaches v,
+ *   v included.  On a direction loop every loop cell has the same U: the loop and everything that drains into it.
+ *   Nothing is special-cased for loops and no loop sentinel is written.
+ *   ORDER: integers in their numeric order; f32 in the IEEE total order restricted to the non-NaN values,
+ *   -inf < ... < -0 < +0 < ... < +inf: -0 and +0 are DISTINCT here and ordered, although == does not tell them apart.
+ * Per-cell outputs, each a nullable pointer (a call must request at least one):
+ *   at_cell  uint32  the lowest flat index y * width + x among the contributing cells of U(v) whose value is the maximum
+ *                    (which == RDGPU_EXTREME_MAX) or the minimum (RDGPU_EXTREME_MIN) under that order; 0xFFFFFFFF where
+ *                    v does not participate or U(v) has no contributing cell.
+ *   extreme  T       values[at_cell[v]], bit for bit; value_nodata with its bits unchanged where at_cell is 0xFFFFFFFF.
+ * Every cell of every requested plane is written exactly once, the inputs are not modified, and the result is exact and
+ * identical from run to run.  T: i8 u8 i16 u16 i32 u32 f32.  f64, i64 and u64 are NOT declared: the engine carries value
+ * and cell index in one 64-bit word, which 64-bit values do not fit.
+ * A null dirs or values, both outputs null, a which other than 0 or 1, a non-positive size or more than 0xFFFF0000
+ * cells returns RDGPU_ERR_ARG before any device work; nothing is written then.  The _dev forms take device pointers and
+ * are ordered on hip_stream without synchronising it.  Scratch (1 byte per cell) comes from the workspace pool. */
+enum { RDGPU_EXTREME_MAX = 0, RDGPU_EXTREME_MIN = 1 };
+#define RDGPU_DECL_EXTREME(SUF, T)                                                                                          \
+  int rdgpu_d8_upslope_extreme_##SUF(const uint8_t *dirs, uint8_t dir_nodata, const T *values, T value_nodata, int width,  \
+                                     int height, int which, T *extreme /* nullable */, uint32_t *at_cell /* nullable */);  \
+  int rdgpu_d8_upslope_extreme_dev_##SUF(const uint8_t *d_dirs, uint8_t dir_nodata, const T *d_values, T value_nodata,     \
+                                         int width, int height, int which, T *d_extreme /* nullable */,                    \
+                                         uint32_t *d_at_cell /* nullable */, void *hip_stream);
+RDGPU_DECL_EXTREME(i8, int8_t)
+RDGPU_DECL_EXTREME(u8, uint8_t)
+RDGPU_DECL_EXTREME(i16, int16_t)
+RDGPU_DECL_EXTREME(u16, uint16_t)
+RDGPU_DECL_EXTREME(i32, int32_t)
+RDGPU_DECL_EXTREME(u32, uint32_t)
+RDGPU_DECL_EXTREME(f32, float)
+#undef RDGPU_DECL_EXTREME
+
 /* ---- channel network and Strahler stream order on the D8 direction forest ---------------------
  * No reference counterpart (include/richdem/methods/strahler.hpp is a commented-out draft).  Directions are uint8 D8
  * codes (0 NO_FLOW, 1..8, dir_nodata); chan is an optional channel mask (uint8, non-zero = channel), and chan == NULL

@@ -836,6 +836,62 @@ void d8_hand(const E &dem, const F &flowdirs, G &hand) {
   d8_hand(dem, flowdirs, hand, static_cast<const F *>(nullptr));
 }
 
+// ---- upslope extremes on the D8 forest (no reference counterpart; the definition is in rdgpu.h) ----------------------
+namespace detail {
+#define RDGPU_SHIM_EXTREME(SUF, T)                                                                                      \
+  inline int c_extreme(const uint8_t *d, uint8_t dnd, const T *v, T vnd, int w, int h, int which, T *e, uint32_t *at) { \
+    return rdgpu_d8_upslope_extreme_##SUF(d, dnd, v, vnd, w, h, which, e, at);                                          \
+  }
+RDGPU_SHIM_EXTREME(u8, uint8_t) RDGPU_SHIM_EXTREME(i8, int8_t) RDGPU_SHIM_EXTREME(u16, uint16_t) RDGPU_SHIM_EXTREME(i16, int16_t)
+RDGPU_SHIM_EXTREME(u32, uint32_t) RDGPU_SHIM_EXTREME(i32, int32_t) RDGPU_SHIM_EXTREME(f32, float)
+#undef RDGPU_SHIM_EXTREME
+template <class T>
+int c_extreme(const uint8_t *, uint8_t, const T *, T, int, int, int, T *, uint32_t *) { unsupported("d8_upslope_extreme"); }
+}  // namespace detail
+
+// extreme <- the largest (which == RDGPU_EXTREME_MAX) or smallest (RDGPU_EXTREME_MIN) value of `values` over everything that
+// drains through each cell, the cell included; *at_cell (optional, uint32_t) <- the flat index of the cell it sits at, the
+// lowest such index on a tie, NoData 0xFFFFFFFF.  Cells whose value is the values' NoData (or a NaN) contribute nothing;
+// where nothing contributes, or the direction is NoData, extreme is the values' NoData.  Both outputs take the directions'
+// size, geotransform and projection.  Element types: int8 .. uint32 and float; 64-bit values throw.
+namespace detail {
+template <class F, class V, class E>
+void extreme_prepare(const F &flowdirs, const V &values, E &extreme, int which) {
+  using T = elem_t<const V>;
+  static_assert(std::is_same<elem_t<const F>, uint8_t>::value || std::is_same<elem_t<F>, uint8_t>::value,
+                "d8_upslope_extreme: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<elem_t<E>, T>::value, "d8_upslope_extreme: the extreme raster has the values' element type");
+  if (values.width() != flowdirs.width() || values.height() != flowdirs.height())
+    throw std::runtime_error("d8_upslope_extreme: the values must have the directions' size");
+  if (which != RDGPU_EXTREME_MAX && which != RDGPU_EXTREME_MIN)
+    throw std::runtime_error("d8_upslope_extreme: which must be RDGPU_EXTREME_MAX or RDGPU_EXTREME_MIN");
+  extreme.resize(flowdirs);
+  extreme.setNoData(values.noData());
+}
+template <class F, class V, class E>
+void extreme_run(const F &flowdirs, const V &values, E &extreme, uint32_t *at, int which) {
+  using T = elem_t<const V>;
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  check(c_extreme(flowdirs.data(), flowdirs.noData(), (const T *)values.data(), (T)values.noData(), flowdirs.width(),
+                  flowdirs.height(), which, (T *)extreme.data(), at), "d8_upslope_extreme");
+}
+}  // namespace detail
+template <class F, class V, class E, class C>
+void d8_upslope_extreme(const F &flowdirs, const V &values, E &extreme, C *at_cell, int which = RDGPU_EXTREME_MAX) {
+  static_assert(std::is_same<detail::elem_t<C>, uint32_t>::value, "d8_upslope_extreme: the cell raster must be uint32_t");
+  detail::extreme_prepare(flowdirs, values, extreme, which);
+  if (at_cell) {
+    at_cell->resize(flowdirs);
+    at_cell->setNoData(0xFFFFFFFFu);
+  }
+  detail::extreme_run(flowdirs, values, extreme, at_cell ? at_cell->data() : nullptr, which);
+}
+template <class F, class V, class E>
+void d8_upslope_extreme(const F &flowdirs, const V &values, E &extreme, int which = RDGPU_EXTREME_MAX) {
+  detail::extreme_prepare(flowdirs, values, extreme, which);
+  detail::extreme_run(flowdirs, values, extreme, nullptr, which);
+}
+
 // ---- depression inventory (no reference counterpart; the definition is in rdgpu.h) ----------------------------------
 namespace detail {
 #define RDGPU_SHIM_DEPR(SUF, T)                                                                                            \

@@ -1343,3 +1343,75 @@ def depressions_dev(dem, labels, table, topology="D8"):
         None if cap == 0 else ctypes.c_void_p(table.data_ptr()), ctypes.c_uint32(cap), ctypes.c_void_p(count.data_ptr()),
         _stream_ptr()), "rdgpu_depressions_dev")
     return count
+
+
+# ---- upslope extremes (csrc/extreme.hip) -------------------------------------------------------
+_EXTREME_WANT = ("extreme", "at_cell")
+_EXTREME_SUFFIX = {k: v for k, v in _SUFFIX.items() if v not in ("f64", "i64", "u64")}
+
+
+def _which(which, who) -> int:
+    m = {"max": 0, "min": 1, 0: 0, 1: 1}
+    if isinstance(which, bool) or which not in m:
+        raise RdgpuError(f"{who}: which is 'max' or 'min'")
+    return m[which]
+
+
+def d8_upslope_extreme(dirs: np.ndarray, values: np.ndarray, which="max", value_nodata=None, dir_nodata: int = 255,
+                       want=("extreme", "at_cell")) -> dict:
+    """The largest (which="max") or smallest ("min") value over everything that drains through each cell, the cell
+    included, and where it sits (include/rdgpu.h states the definition): a dict with the planes named in `want` --
+    "extreme" (the values' element type; value_nodata where nothing contributes) and "at_cell" (uint32 flat index, the
+    lowest on a tie, 0xFFFFFFFF for none).  values: int8 .. uint32 or float32; cells equal to value_nodata and NaNs
+    contribute nothing.  value_nodata=None: the array's own no_data (an rdarray), else an error."""
+    who = "d8_upslope_extreme"
+    dirs = _dirs2d(dirs, who)
+    if not isinstance(values, np.ndarray) or values.shape != dirs.shape or values.dtype not in _EXTREME_SUFFIX:
+        raise RdgpuError(f"{who}: the values are an array of the directions' shape, element types int8 .. uint32 or float32")
+    w_ = _which(which, who)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in _EXTREME_WANT for k in want):
+        raise RdgpuError(f"{who}: want names at least one of {_EXTREME_WANT}")
+    if value_nodata is None:
+        value_nodata = getattr(values, "no_data", None)
+        if value_nodata is None:
+            raise RdgpuError(f"{who}: value_nodata is not given and the values carry no no_data of their own")
+    s = _EXTREME_SUFFIX[values.dtype]
+    nd = _scalar(s, value_nodata)
+    vals = np.ascontiguousarray(values)
+    h, w = dirs.shape
+    out = {}
+    if "extreme" in want:
+        out["extreme"] = np.empty((h, w), vals.dtype)
+    if "at_cell" in want:
+        out["at_cell"] = np.empty((h, w), np.uint32)
+    check(getattr(lib(), f"rdgpu_d8_upslope_extreme_{s}")(_ptr(dirs), ctypes.c_uint8(dir_nodata), _ptr(vals), nd, w, h, w_,
+                                                          _ptr(out.get("extreme")), _ptr(out.get("at_cell"))),
+          "rdgpu_d8_upslope_extreme")
+    return out
+
+
+def d8_upslope_extreme_dev(dirs, values, which, value_nodata, extreme=None, at_cell=None, dir_nodata: int = 255) -> None:
+    """The planes given (CUDA tensors: extreme of the values' dtype, at_cell int32 holding the uint32 indices bit for bit,
+    -1 is "none") <- d8_upslope_extreme of dirs (uint8 CUDA tensor) and values (CUDA tensor of int8 .. uint32 as far as
+    torch has them, or float32), on torch's current stream and without synchronising it.  At least one plane must be
+    given."""
+    import torch
+
+    who = "d8_upslope_extreme_dev"
+    h, w = _dev2d(dirs, who, torch.uint8)
+    m = {torch.int8: "i8", torch.uint8: "u8", torch.int16: "i16", torch.int32: "i32", torch.float32: "f32"}
+    for name, s in (("uint16", "u16"), ("uint32", "u32")):
+        if hasattr(torch, name):
+            m[getattr(torch, name)] = s
+    if values.dtype not in m:
+        raise RdgpuError(f"{who}: unsupported value dtype {values.dtype}")
+    if _dev2d(values, who) != (h, w):
+        raise RdgpuError(f"{who}: shape mismatch")
+    if extreme is None and at_cell is None:
+        raise RdgpuError(f"{who}: no output requested")
+    s = m[values.dtype]
+    check(getattr(lib(), f"rdgpu_d8_upslope_extreme_dev_{s}")(
+        ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata), ctypes.c_void_p(values.data_ptr()), _scalar(s, value_nodata),
+        w, h, _which(which, who), _dev_plane(extreme, (h, w), values.dtype, who), _dev_plane(at_cell, (h, w), torch.int32, who),
+        _stream_ptr()), "rdgpu_d8_upslope_extreme_dev")

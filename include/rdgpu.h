@@ -957,6 +957,45 @@ RDGPU_DECL_HAND(f32, float)
 RDGPU_DECL_HAND(f64, double)
 #undef RDGPU_DECL_HAND
 
+/* ---- longest upstream flow path on the D8 direction forest -------------------------------------
+ * No reference counterpart (TauDEM's plen, WhiteboxTools' MaxUpslopeFlowpathLength and LongestFlowpath).  Directions are
+ * uint8 D8 codes (0 NO_FLOW, 1..8, dir_nodata).
+ *   D(c), steps(c), outlet(c) are dist, steps and to_cell of rdgpu_d8_flow_path with chan == NULL, bit for bit.  A cell
+ *   HAS A PATH iff that to_cell is not 0xFFFFFFFF: NoData cells have none, nor do cells whose path runs into a direction
+ *   loop.
+ *   U(v), for a cell v with a path, is v and every cell whose path passes through v; all of them have a path.
+ *   head(v) is the cell of U(v) with the greatest D, compared as doubles (all finite and >= 0); among equal D the lowest
+ *   flat index y * width + x.  For u in U(v) the steps from u to v are steps(u) - steps(v) plane by plane, so head(v) is
+ *   the cell upstream of v that is farthest from v.  D is a ROUNDED function of three integers: two different step
+ *   triples whose real lengths lie within a rounding of each other are ordered by their rounded D, and by index where
+ *   the rounded values are equal.
+ * Per-cell outputs, each a nullable pointer (a call must request at least one):
+ *   from_cell      uint32                    head(v); 0xFFFFFFFF where v has no path.
+ *   steps          uint32 [3][height][width] steps(head(v)) - steps(v) per plane (along x, along y, diagonal).  All 0
+ *                                            where v is its own head, all 0xFFFFFFFF where v has no path.
+ *   length         float64                   (double)nx * cell_x + (double)ny * cell_y + (double)nd * diag of those three
+ *                                            counts, evaluated as rdgpu_d8_flow_path's dist is (a rounding after every
+ *                                            product and every sum, no fused multiply-add, diag computed once on the
+ *                                            host); length_nodata where v has no path.
+ *   on_basin_path  uint8                     1 iff head(v) == head(outlet(v)), else 0; 0 where v has no path.  These are
+ *                                            exactly the cells of the longest flow path of v's basin, from its head down
+ *                                            to the outlet: head(v) lies in U(v), so the head's path passes through v,
+ *                                            and a cell on head(outlet)'s path has that cell as the maximum of its own,
+ *                                            smaller upslope set.
+ * Every cell of every requested plane is written exactly once, the inputs are not modified, and the result is exact and
+ * identical from run to run.  cell_x and cell_y: their sign is ignored; zero or not finite is RDGPU_ERR_ARG.  A null
+ * dirs, no output requested, a non-positive size or more than 0xFFFF0000 cells returns RDGPU_ERR_ARG before any device
+ * work; nothing is written then.  The _dev form takes device pointers and is ordered on hip_stream without
+ * synchronising it.  Scratch (16 bytes per cell, the flow-path engine's 2.5 among them; on_basin_path 4 more, 8 without
+ * from_cell) comes from the workspace pool. */
+int rdgpu_d8_longest_flow_path(const uint8_t *dirs, uint8_t dir_nodata, int width, int height, double cell_x, double cell_y,
+                               uint32_t *from_cell /* nullable */, uint32_t *steps /* nullable */, double *length /* nullable */,
+                               double length_nodata, uint8_t *on_basin_path /* nullable */);
+int rdgpu_d8_longest_flow_path_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int width, int height, double cell_x, double cell_y,
+                                   uint32_t *d_from_cell /* nullable */, uint32_t *d_steps /* nullable */,
+                                   double *d_length /* nullable */, double length_nodata, uint8_t *d_on_basin_path /* nullable */,
+                                   void *hip_stream);
+
 /* ---- depression inventory: labels and one record per depression of the fill --------------------
  * No reference counterpart (the flat inventory of the lakes FillDepressions produces; the depression hierarchy is not
  * built).  Let W = FillDepressions<topology>(dem) exactly as rdgpu_fill_<T> computes it; NoData is an elevation like any

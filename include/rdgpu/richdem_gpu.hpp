@@ -836,6 +836,60 @@ void d8_hand(const E &dem, const F &flowdirs, G &hand) {
   d8_hand(dem, flowdirs, hand, static_cast<const F *>(nullptr));
 }
 
+// ---- longest upstream flow path on the D8 forest (no reference counterpart; the definition is in rdgpu.h) -----------
+// length <- the length of the longest flow path that ends at each cell; *from_cell (optional, uint32_t) <- the flat index
+// of that path's head, the lowest on a tie; *on_basin_path (optional, uint8_t) <- 1 on the longest path of every basin,
+// from its head down to the outlet.  The cell lengths are the directions' |geotransform[1]|, |geotransform[5]|; the
+// outputs take the directions' size, geotransform and projection, NoData -1, 0xFFFFFFFF and 0 (NoData cells and cells
+// that drain into a direction loop have no path).
+namespace detail {
+template <class F, class G>
+void longest_prepare(const F &flowdirs, G &length, double &cx, double &cy) {
+  static_assert(std::is_same<elem_t<const F>, uint8_t>::value || std::is_same<elem_t<F>, uint8_t>::value,
+                "d8_longest_flow_path: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<elem_t<G>, double>::value, "d8_longest_flow_path: the length raster must be double");
+  cell_lengths(flowdirs, "d8_longest_flow_path", cx, cy);
+  length.resize(flowdirs);
+  length.setNoData(-1.0);
+}
+template <class F, class G>
+void longest_run(const F &flowdirs, G &length, double cx, double cy, uint32_t *from, uint8_t *on_path) {
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  check(rdgpu_d8_longest_flow_path(flowdirs.data(), flowdirs.noData(), flowdirs.width(), flowdirs.height(), cx, cy, from, nullptr,
+                                   length.data(), -1.0, on_path), "d8_longest_flow_path");
+}
+template <class F, class A, class V>
+elem_t<A> *longest_plane(const F &flowdirs, A *plane, V nodata) {
+  if (!plane) return nullptr;
+  plane->resize(flowdirs);
+  plane->setNoData(nodata);
+  return plane->data();
+}
+}  // namespace detail
+template <class F, class G, class C, class B>
+void d8_longest_flow_path(const F &flowdirs, G &length, C *from_cell, B *on_basin_path) {
+  static_assert(std::is_same<detail::elem_t<C>, uint32_t>::value, "d8_longest_flow_path: the cell raster must be uint32_t");
+  static_assert(std::is_same<detail::elem_t<B>, uint8_t>::value, "d8_longest_flow_path: the path mask must be uint8_t");
+  double cx, cy;
+  detail::longest_prepare(flowdirs, length, cx, cy);
+  uint32_t *from = detail::longest_plane(flowdirs, from_cell, 0xFFFFFFFFu);
+  uint8_t *on_path = detail::longest_plane(flowdirs, on_basin_path, (uint8_t)0);
+  detail::longest_run(flowdirs, length, cx, cy, from, on_path);
+}
+template <class F, class G, class C>
+void d8_longest_flow_path(const F &flowdirs, G &length, C *from_cell) {
+  static_assert(std::is_same<detail::elem_t<C>, uint32_t>::value, "d8_longest_flow_path: the cell raster must be uint32_t");
+  double cx, cy;
+  detail::longest_prepare(flowdirs, length, cx, cy);
+  detail::longest_run(flowdirs, length, cx, cy, detail::longest_plane(flowdirs, from_cell, 0xFFFFFFFFu), nullptr);
+}
+template <class F, class G>
+void d8_longest_flow_path(const F &flowdirs, G &length) {
+  double cx, cy;
+  detail::longest_prepare(flowdirs, length, cx, cy);
+  detail::longest_run(flowdirs, length, cx, cy, nullptr, nullptr);
+}
+
 // ---- upslope extremes on the D8 forest (no reference counterpart; the definition is in rdgpu.h) ----------------------
 namespace detail {
 #define RDGPU_SHIM_EXTREME(SUF, T)                                                                                      \

@@ -1415,3 +1415,55 @@ def d8_upslope_extreme_dev(dirs, values, which, value_nodata, extreme=None, at_c
         ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata), ctypes.c_void_p(values.data_ptr()), _scalar(s, value_nodata),
         w, h, _which(which, who), _dev_plane(extreme, (h, w), values.dtype, who), _dev_plane(at_cell, (h, w), torch.int32, who),
         _stream_ptr()), "rdgpu_d8_upslope_extreme_dev")
+
+
+# ---- longest upstream flow path (csrc/longest.hip) ---------------------------------------------
+_LONGEST_WANT = ("from_cell", "steps", "length", "on_basin_path")
+
+
+def d8_longest_flow_path(dirs: np.ndarray, dir_nodata: int = 255, cell=(1.0, 1.0), length_nodata: float = -1.0,
+                         want=("from_cell", "length")) -> dict:
+    """The longest flow path that ends at every cell (include/rdgpu.h states the definition): a dict with the planes named
+    in `want` -- "from_cell" (uint32 flat index of the path's head, the lowest on a tie, 0xFFFFFFFF for none), "steps"
+    (uint32 [3, h, w]: along x, along y, diagonal), "length" (float64, length_nodata for none) and "on_basin_path" (uint8:
+    1 on the longest path of every basin, from its head to the outlet)."""
+    who = "d8_longest_flow_path"
+    dirs = _dirs2d(dirs, who)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in _LONGEST_WANT for k in want):
+        raise RdgpuError(f"{who}: want names at least one of {_LONGEST_WANT}")
+    cx, cy = _cell2(cell, who)
+    h, w = dirs.shape
+    out = {}
+    if "from_cell" in want:
+        out["from_cell"] = np.empty((h, w), np.uint32)
+    if "steps" in want:
+        out["steps"] = np.empty((3, h, w), np.uint32)
+    if "length" in want:
+        out["length"] = np.empty((h, w), np.float64)
+    if "on_basin_path" in want:
+        out["on_basin_path"] = np.empty((h, w), np.uint8)
+    check(lib().rdgpu_d8_longest_flow_path(_ptr(dirs), ctypes.c_uint8(dir_nodata), w, h, cx, cy, _ptr(out.get("from_cell")),
+                                           _ptr(out.get("steps")), _ptr(out.get("length")), ctypes.c_double(length_nodata),
+                                           _ptr(out.get("on_basin_path"))), "rdgpu_d8_longest_flow_path")
+    return out
+
+
+def d8_longest_flow_path_dev(dirs, dir_nodata: int = 255, cell=(1.0, 1.0), length_nodata: float = -1.0, from_cell=None, steps=None,
+                             length=None, on_basin_path=None) -> None:
+    """The planes given (CUDA tensors: from_cell int32 [h, w] holding the uint32 indices bit for bit, -1 is "none"; steps
+    int32 [3, h, w] likewise; length float64 [h, w]; on_basin_path uint8 [h, w]) <- d8_longest_flow_path of dirs (uint8
+    CUDA tensor), on torch's current stream and without synchronising it.  At least one plane must be given."""
+    import torch
+
+    who = "d8_longest_flow_path_dev"
+    h, w = _dev2d(dirs, who, torch.uint8)
+    if from_cell is None and steps is None and length is None and on_basin_path is None:
+        raise RdgpuError(f"{who}: no output requested")
+    cx, cy = _cell2(cell, who)
+    check(lib().rdgpu_d8_longest_flow_path_dev(ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata), w, h, cx, cy,
+                                               _dev_plane(from_cell, (h, w), torch.int32, who),
+                                               _dev_plane(steps, (3, h, w), torch.int32, who),
+                                               _dev_plane(length, (h, w), torch.float64, who), ctypes.c_double(length_nodata),
+                                               _dev_plane(on_basin_path, (h, w), torch.uint8, who), _stream_ptr()),
+          "rdgpu_d8_longest_flow_path_dev")

@@ -457,9 +457,9 @@ RDGPU_DECL_ALTER(u64, uint64_t)
  * the stencil relaxation engine, the last pass over the DEM, the classification's own bitmaps and their switches are gone: their
  * record is in docs/HISTORY.md and profiles/):
  *   RDGPU_FLAT_PLANES=0         the two level fields as one int per cell instead of 16 bit planes per 64 x 64 tile (the plane
- *                               engine also steps aside by itself when a level does not fit 16 bits: an open flat more than
- *                               65 000 cells across; flat_mask / labels, alter = true, ResolveFlatsEpsilon and the row-block
- *                               shards always use ints)
+ *                               engine also steps aside by itself when a level may not fit 16 bits: a flat more than
+ *                               65 279 levels deep, e.g. open water that far across; flat_mask / labels, alter = true,
+ *                               ResolveFlatsEpsilon and the row-block shards always use ints)
  *   RDGPU_FLAT_STATIC=0         the towards search in batches of rounds decided on the host instead of one enqueue
  *   RDGPU_FLAT_ASYNC=<n>        a search's rounds hand over to resident wavefronts once a round visits fewer than n tiles
  *                               (default 20000; 0: rounds to the end), RDGPU_FLAT_ASYNC_BLOCKS / _STATS tune and report them,
@@ -479,13 +479,14 @@ int rdgpu_flat_get_stats(rdgpu_flat_stats *out);
 /* The asynchronous tails of the two level searches of the last flat resolution on this thread (csrc/flats.hip,
  * k_relax_bits_async; no reference counterpart -- the reference's searches are serial queues, flats/flat_resolution.hpp:152-298):
  * tile visits by the resident wavefronts, tiles that were live when the rounds handed over (summed over the launches),
- * launches, launches that gave up and were finished in rounds. */
+ * launches, launches that gave up and were finished in rounds.  plane_repeats: 1 when this thread's last directions-only call
+ * found a level beyond the planes' range and was repeated on the int engine, else 0. */
 typedef struct rdgpu_flat_async_stats {
   uint64_t visits;
   uint32_t launches;
   uint32_t failures;
   uint32_t live_tiles;
-  uint32_t reserved;
+  uint32_t plane_repeats;
 } rdgpu_flat_async_stats;
 int rdgpu_flat_get_async_stats(rdgpu_flat_async_stats *out);
 

@@ -580,7 +580,7 @@ class _FlatStats(ctypes.Structure):
 
 class _FlatAsyncStats(ctypes.Structure):
     _fields_ = [("visits", ctypes.c_uint64), ("launches", ctypes.c_uint32), ("failures", ctypes.c_uint32),
-                ("live_tiles", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+                ("live_tiles", ctypes.c_uint32), ("plane_repeats", ctypes.c_uint32)]
 
 
 def flat_stats() -> dict:
@@ -590,7 +590,8 @@ def flat_stats() -> dict:
     a = _FlatAsyncStats()
     check(lib().rdgpu_flat_get_async_stats(ctypes.byref(a)), "rdgpu_flat_get_async_stats")
     return {"low_edges": st.low, "high_edges": st.high, "noflow": st.noflow, "away": st.away, "towards": st.towards,
-            "tail_visits": a.visits, "tail_live_tiles": a.live_tiles, "tail_launches": a.launches, "tail_failures": a.failures}
+            "tail_visits": a.visits, "tail_live_tiles": a.live_tiles, "tail_launches": a.launches, "tail_failures": a.failures,
+            "plane_repeats": a.plane_repeats}
 
 
 def release_workspace() -> None:

@@ -10,8 +10,8 @@
 //
 // So the levels stay in the layout the search works in:
 //   P[tile][plane][row]   16 planes of 64-bit row words: bit c of plane j of row r = bit j of the level of cell (r, c);
-//                         levels 1 .. 65534, all ones = not reached / does not take part.  8 KB per tile and field (the int
-//                         raster: 16 KB), read and written by the tile's own visits only.
+//                         levels 1 .. 65533 (PL_MAX + 254), all ones = not reached / does not take part.  8 KB per tile and
+//                         field (the int raster: 16 KB), read and written by the tile's own visits only.
 //   E[tile][4][64]        the levels of the tile's top and bottom row (lane = column) and left and right column (lane =
 //                         row) as ints (DINF = not reached): what the NEIGHBOURS' visits read as their ring -- four
 //                         coalesced loads instead of two row loads and two column gathers.
@@ -22,8 +22,14 @@
 // (k_flat_dirs_qp) does d8_masked_FlowDir's comparison bit-sliced as well, 64 cells per operation, and only its output --
 // one byte per cell that gets a direction -- is turned into the raster's layout.
 // A level that does not fit 16 bits raises `overflow`; the caller then runs the int engine (nothing was written to dirs).
+// The limit is looked at where a visit starts and where a 256-level segment starts, not per level (the level loop is the
+// hottest code of the search): a segment that starts at base < PL_MAX assigns levels up to base + 255, also after a jump to
+// the next ring level (a jump of 256 or more ends the segment first).  So PL_MAX leaves one whole segment below 0xFFFF:
+// no level the planes are given reaches the all-ones pattern or wraps, and the edge ints the neighbours read are true.
 constexpr int NPL = 16;
-constexpr int32_t PL_MAX = 0xFFF0;   // levels from here on: overflow (PlaneField::max_level; RDGPU_FLAT_PLANES_MAX lowers it: tests)
+// segments starting here or later: overflow (PlaneField::max_level; RDGPU_FLAT_PLANES_MAX lowers it: tests)
+constexpr int32_t PL_MAX = 0xFFFF - (1 << BPLANES);
+static_assert(PL_MAX - 1 + (1 << BPLANES) - 1 < 0xFFFF, "a segment's last level must stay below the not-reached pattern");
 // (struct PlaneField: flats.hip, beside BitsScratch)
 
 template <bool CO>

@@ -801,7 +801,7 @@ struct PlaneField {
   unsigned long long *R = nullptr;   // [tile][64]
   uint32_t *overflow = nullptr;
   uint8_t *expanded = nullptr;       // per tile: has been visited (its planes exist)
-  int32_t max_level = 0xFFF0;        // a level from here on raises `overflow` (the planes hold 16 bits)
+  int32_t max_level = 0xFFFF - (1 << BPLANES);   // a visit or segment starting from here on raises `overflow` (PL_MAX)
 };
 struct BitsScratch {
   unsigned long long *mbits;   // per tile and row: the cells that take part
@@ -1843,7 +1843,7 @@ static BitsScratch bits_scratch(int w, int h, bool second = false, bool planes =
     b.pf.R = ws.buf<unsigned long long>(second ? "flats.preached2" : "flats.preached", (size_t)b.ntiles * BT);
     b.pf.overflow = ws.buf<uint32_t>("flats.poverflow", 4) + (second ? 1 : 0);
     b.pf.expanded = b.expanded;
-    if (const char *e = getenv("RDGPU_FLAT_PLANES_MAX")) b.pf.max_level = std::min(0xFFF0, std::max(8, atoi(e)));   // (tests: the overflow path)
+    if (const char *e = getenv("RDGPU_FLAT_PLANES_MAX")) b.pf.max_level = std::min(PL_MAX, std::max(8, atoi(e)));   // (tests: the overflow path)
     b.near = b.mbits + (size_t)b.ntiles * BT;
   }
   return b;
@@ -2286,6 +2286,7 @@ static void epsilon_levels_device(const T *d_z, T nodata, int w, int h, int32_t 
 }
 
 static thread_local bool g_planes_overflowed = false;   // (flat_resolution_device: this call repeats a plane search that overflowed)
+static thread_local uint32_t g_plane_repeats = 0;       // (rdgpu_flat_get_async_stats: the last directions-only call did)
 // A level beyond 16 bits: once more, on ints (the last pass has not run, or left dirs alone: it holds what the classification
 // wrote, nothing is lost).
 template <class T>
@@ -2293,6 +2294,7 @@ void flat_resolution_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dir
 template <class T>
 static void repeat_on_ints(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, hipStream_t s) {
   g_planes_overflowed = true;
+  g_plane_repeats = 1;
   struct Reset { ~Reset() { g_planes_overflowed = false; } } reset;
   flat_resolution_device<T>(d_z, nodata, w, h, d_dirs, s);
 }
@@ -2314,8 +2316,10 @@ void flat_resolution_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dir
   Workspace &ws = Workspace::get();
   g_fstats = rdgpu_flat_stats{0, 0, 0, 0, 0};
   g_async_info = AsyncInfo{0, 0, 0, 0};
-  // r06: the level fields as bit planes per tile (flat_planes.inc); RDGPU_FLAT_PLANES=0, a level beyond 16 bits (an open flat
-  // wider than 65 000 cells) or RDGPU_FLAT_TRACE: one int per cell (r02-r05).  Either engine takes its bitmaps and counts from
+  if (!g_planes_overflowed) g_plane_repeats = 0;
+  // r06: the level fields as bit planes per tile (flat_planes.inc); RDGPU_FLAT_PLANES=0, a level beyond the planes' range (a
+  // flat more than PL_MAX = 65 279 levels deep) or RDGPU_FLAT_TRACE: one int per cell (r02-r05).  Either engine takes its
+  // bitmaps and counts from
   // the classification's flag bytes, and either last pass (r05) works from 4 bits per cell, without the DEM: the cells next to
   // a low edge get their direction in the classification.
   const bool planes = !env_is("RDGPU_FLAT_PLANES", '0') && !g_planes_overflowed && !getenv("RDGPU_FLAT_TRACE");
@@ -3117,6 +3121,6 @@ extern "C" int rdgpu_flat_get_stats(rdgpu_flat_stats *out) {
 }
 extern "C" int rdgpu_flat_get_async_stats(rdgpu_flat_async_stats *out) {
   if (!out) return RDGPU_ERR_ARG;
-  *out = rdgpu_flat_async_stats{g_async_info.visits, g_async_info.launches, g_async_info.failures, g_async_info.live_tiles, 0};
+  *out = rdgpu_flat_async_stats{g_async_info.visits, g_async_info.launches, g_async_info.failures, g_async_info.live_tiles, g_plane_repeats};
   return RDGPU_OK;
 }

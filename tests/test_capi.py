@@ -38,6 +38,26 @@ def test_argument_errors_do_not_need_a_gpu(rd):
         rd.FillDepressions(np.zeros(4, np.float32))
 
 
+def test_flat_async_stats_mirror_matches_the_header(rd):
+    """rdgpu_flat_async_stats: the ctypes mirror has the header's fields in the header's order, the size the struct has had
+    since it was introduced (the former `reserved` word is `plane_repeats`), and the call fills every word."""
+    import ctypes
+
+    from richdem_amd.api import _FlatAsyncStats
+
+    src = open(os.path.join(ROOT, "include", "rdgpu.h")).read()
+    body = re.search(r"typedef struct rdgpu_flat_async_stats \{(.*?)\} rdgpu_flat_async_stats;", src, flags=re.S).group(1)
+    fields = re.findall(r"\b(uint64_t|uint32_t)\s+(\w+);", body)
+    ct = {"uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32}
+    assert [(n, ct[t]) for t, n in fields] == list(_FlatAsyncStats._fields_)
+    assert [n for _, n in fields] == ["visits", "launches", "failures", "live_tiles", "plane_repeats"]
+    assert ctypes.sizeof(_FlatAsyncStats) == 24 and _FlatAsyncStats.plane_repeats.offset == 20
+    a = _FlatAsyncStats(1, 2, 3, 4, 5)
+    assert rd.lib().rdgpu_flat_get_async_stats(ctypes.byref(a)) == 0
+    assert a.plane_repeats in (0, 1)                      # (whatever ran before in this process: never the 5 put there)
+    assert rd.flat_stats()["plane_repeats"] == a.plane_repeats
+
+
 def test_no_cpu_fallback_without_gpu(rd):
     """Without a GPU the product must fail loudly, never compute on the CPU."""
     import torch

@@ -184,14 +184,17 @@ def test_level_planes_long_channels_and_overflow(rd, orc, monkeypatch):
     exp = orc.port.flat_resolution(dem, nd)
     assert (exp[dem == 10] != 0).all()
     assert np.array_equal(rd.barnes_flat_resolution_d8(dem, nd), exp)
+    assert rd.flat_stats()["plane_repeats"] == 0       # ~33 000 levels: the planes hold them
     for shape in ((70, 9), (9, 70), (64, 64), (65, 129), (1, 200), (200, 1), (3, 3)):
         rng = np.random.default_rng(shape[0] * 7 + shape[1])
         small = orc.port.fill(rng.integers(0, 4, shape).astype(np.int32))
         assert np.array_equal(rd.barnes_flat_resolution_d8(small, nd), orc.port.flat_resolution(small, nd)), shape
     monkeypatch.setenv("RDGPU_FLAT_PLANES_MAX", "300")
     assert np.array_equal(rd.barnes_flat_resolution_d8(dem, nd), exp)
+    assert rd.flat_stats()["plane_repeats"] == 1       # the call was repeated on ints
     monkeypatch.setenv("RDGPU_FLAT_ASYNC", "100000")   # ... and when the overflow happens in the asynchronous tail
     assert np.array_equal(rd.barnes_flat_resolution_d8(dem, nd), exp)
+    assert rd.flat_stats()["plane_repeats"] == 1
 
 
 def test_directions_from_masks_modulo_8(rd, orc, monkeypatch):

@@ -15,7 +15,7 @@
 //      one atomicAdd(word, area - (1<<56)) per step; integer, exact, order independent.
 //  f64 weights (FA_D8): f64 atomicAdd on the total + release/acquire decrement of a separate counter.
 #include "common.hpp"
-#include "tile_front.hpp"
+#include "d8_forest.hpp"
 
 #include <string>
 #include <type_traits>
@@ -378,13 +378,13 @@ __global__ __launch_bounds__(NTHR, 6) void k_acc_link_tile(const uint8_t *__rest
   // what the border cells publish, one per thread (252 of the tile's 256 slots; the four spare ones are marked unused)
   {
     const int slot = (int)threadIdx.x;
-    const size_t node = (size_t)t * 256 + slot;
+    const size_t node = (size_t)t * TILE_SLOTS + slot;
     unsigned long long word = NOT_A_NODE << LK_SHIFT;
     uint32_t tn = NO_NODE;
     uint8_t rs = 255;
-    if (slot < 4 * LT - 4) {
-      const int bx = slot < LT ? slot : slot < 2 * LT ? slot - LT : slot < 3 * LT - 2 ? 0 : LT - 1;
-      const int by = slot < LT ? 0 : slot < 2 * LT ? LT - 1 : slot < 3 * LT - 2 ? slot - 2 * LT + 1 : slot - (3 * LT - 2) + 1;
+    if (slot < BORDER_SLOTS) {
+      int bx, by;
+      border_cell(slot, bx, by);
       const uint32_t c2 = (uint32_t)((by * LPS + bx) * 2);
       const uint32_t root = *reinterpret_cast<const uint16_t *>(lpb + c2);
       const uint32_t back = *reinterpret_cast<const uint16_t *>(lpb + root);
@@ -397,6 +397,8 @@ __global__ __launch_bounds__(NTHR, 6) void k_acc_link_tile(const uint8_t *__rest
         word = (unsigned long long)(cw & 0xFFFFFFu);   // complete by construction: every cell counted has a path to it
         const int d = (int)(cw >> 24);
         const int gx = x0 + bx + d8dx(d), gy = y0 + by + d8dy(d);
+        // tile_front.hpp's tile_node(gx, gy, tilesX), written out: through the call this kernel comes out of the compiler
+        // with two registers exchanged, and its code is to stay as it was measured
         tn = ((uint32_t)(gy / LT) * tilesX + (uint32_t)(gx / LT)) * 256u + (uint32_t)border_slot(gx % LT, gy % LT);
       }
     }
@@ -480,9 +482,9 @@ __device__ __forceinline__ void link_final_walk_tile(const uint32_t t, const uin
     const int slot = (int)threadIdx.x;
     unsigned long long inflow = 0;
     uint32_t blocked = 0;
-    if (slot < 4 * LT - 4) {
-      const int bx = slot < LT ? slot : slot < 2 * LT ? slot - LT : slot < 3 * LT - 2 ? 0 : LT - 1;
-      const int by = slot < LT ? 0 : slot < 2 * LT ? LT - 1 : slot < 3 * LT - 2 ? slot - 2 * LT + 1 : slot - (3 * LT - 2) + 1;
+    if (slot < BORDER_SLOTS) {
+      int bx, by;
+      border_cell(slot, bx, by);
       const int o = (by + 1) * LLW + bx + 1;
       if (sd[o] != nodata) {
         unsigned long long wv[8];
@@ -495,7 +497,7 @@ __device__ __forceinline__ void link_final_walk_tile(const uint32_t t, const uin
           wv[m - 1] = 0;
           if (use[m - 1]) {
             const int gx = x0 + nx, gy = y0 + ny;
-            wv[m - 1] = nw[((size_t)(gy / LT) * tilesX + (size_t)(gx / LT)) * 256 + (size_t)border_slot(gx % LT, gy % LT)];
+            wv[m - 1] = nw[((size_t)(gy / LT) * tilesX + (size_t)(gx / LT)) * TILE_SLOTS + (size_t)border_slot(gx % LT, gy % LT)];
           }
         }
 #pragma unroll
@@ -527,10 +529,10 @@ __device__ __forceinline__ void link_final_walk_tile(const uint32_t t, const uin
     lw[ly * LT + lx] = data ? (((unsigned long long)tgs[j] << 43) | 1ull) : 0ull;
   }
   __syncthreads();
-  if (threadIdx.x < 4 * LT - 4) {   // one border cell per thread: what it receives from outside, and what blocks it
+  if (threadIdx.x < BORDER_SLOTS) {   // one border cell per thread: what it receives from outside, and what blocks it
     const int slot = (int)threadIdx.x;
-    const int bx = slot < LT ? slot : slot < 2 * LT ? slot - LT : slot < 3 * LT - 2 ? 0 : LT - 1;
-    const int by = slot < LT ? 0 : slot < 2 * LT ? LT - 1 : slot < 3 * LT - 2 ? slot - 2 * LT + 1 : slot - (3 * LT - 2) + 1;
+    int bx, by;
+    border_cell(slot, bx, by);
     const unsigned long long add = ((unsigned long long)ext_blk[slot] << 56) | ext_in[slot];
     if (add && lw[by * LT + bx] != 0) lw[by * LT + bx] += add;   // (a NoData border cell receives nothing: its gather found no donor)
   }
@@ -638,9 +640,9 @@ __global__ __launch_bounds__(NTHR, 5) void k_acc_link_final_sums(const uint8_t *
   int bcell = -1;
   {
     const int slot = (int)threadIdx.x;
-    if (slot < 4 * LT - 4) {
-      const int bx = slot < LT ? slot : slot < 2 * LT ? slot - LT : slot < 3 * LT - 2 ? 0 : LT - 1;
-      const int by = slot < LT ? 0 : slot < 2 * LT ? LT - 1 : slot < 3 * LT - 2 ? slot - 2 * LT + 1 : slot - (3 * LT - 2) + 1;
+    if (slot < BORDER_SLOTS) {
+      int bx, by;
+      border_cell(slot, bx, by);
       const int o = (by + 1) * SDW + SDO + bx;
       if (sd[o] != nodata) {
         bcell = by * LPS + bx;
@@ -655,7 +657,7 @@ __global__ __launch_bounds__(NTHR, 5) void k_acc_link_final_sums(const uint8_t *
           if (use[m - 1]) {
             const uint32_t gx = (uint32_t)(x0 + nx), gy = (uint32_t)(y0 + ny);   // (a cell with data: inside the raster)
             static_assert(LT == 64, "shifts and masks below");
-            wv[m - 1] = nw[((size_t)(gy >> 6) * tilesX + (size_t)(gx >> 6)) * 256 + (size_t)border_slot((int)(gx & 63u), (int)(gy & 63u))];
+            wv[m - 1] = nw[((size_t)(gy >> 6) * tilesX + (size_t)(gx >> 6)) * TILE_SLOTS + (size_t)border_slot((int)(gx & 63u), (int)(gy & 63u))];
           }
         }
 #pragma unroll
@@ -903,20 +905,15 @@ __global__ __launch_bounds__(NTHR) void k_acc_nodata_f64(const uint8_t *__restri
 // ---- drivers --------------------------------------------------------------------------------
 static inline uint32_t sgrid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + NTHR - 1) / NTHR, 256u * 32u); }
 
-static void check_dims(int w, int h, const char *who) {
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, std::string(who) + ": width and height must be positive");
-  if ((uint64_t)w * (uint64_t)h > 0xFFFF0000ull) throw Error(RDGPU_ERR_ARG, std::string(who) + ": raster too large");
-}
-
 template <class A>
 void d8_flow_accum_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, A *d_area, hipStream_t s) {
   if (!d_dirs || !d_area) throw Error(RDGPU_ERR_ARG, "rdgpu_d8_flow_accum: null pointer");
-  check_dims(w, h, "rdgpu_d8_flow_accum");
+  check_forest_dims(w, h, "rdgpu_d8_flow_accum");
   const uint64_t n = (uint64_t)w * h;
   const char *env = getenv("RDGPU_ACCUM_LINKS");   // =0: the raster-wide walk (what the row-block shards run); A/B and tests
   if (!(env && env[0] == '0')) {
     const uint32_t tilesX = (w + LT - 1) / LT, ntiles = tilesX * ((h + LT - 1) / LT);
-    const uint64_t nnodes = (uint64_t)ntiles * 256;
+    const uint64_t nnodes = (uint64_t)ntiles * TILE_SLOTS;
     if (nnodes < 0xFFFFFF00ull) {
       Workspace &ws = Workspace::get();
       unsigned long long *nw = ws.buf<unsigned long long>("accum.link_word", nnodes);
@@ -1030,7 +1027,7 @@ void flow_accum_f64_device(const uint8_t *d_dirs, int w, int h, double *d_acc, h
 template <class T>
 void fa_d8_device(const T *d_z, T nodata, int w, int h, double *d_acc, hipStream_t s, bool unit_weights = false) {
   if (!d_z || !d_acc) throw Error(RDGPU_ERR_ARG, "rdgpu_fa_d8: null pointer");
-  check_dims(w, h, "rdgpu_fa_d8");
+  check_forest_dims(w, h, "rdgpu_fa_d8");
   Workspace &ws = Workspace::get();
   uint8_t *dirs = ws.buf<uint8_t>("accum.fmdirs", (size_t)w * h);
   // the one read of the weights runs on the side stream while the directions are made on the caller's
@@ -1058,7 +1055,7 @@ void fa_d8_device(const T *d_z, T nodata, int w, int h, double *d_acc, hipStream
 template <class A>
 static void d8_flow_accum_host(const uint8_t *dirs, uint8_t nodata, int w, int h, A *area) {
   if (!dirs || !area) throw Error(RDGPU_ERR_ARG, "rdgpu_d8_flow_accum: null pointer");
-  check_dims(w, h, "rdgpu_d8_flow_accum");
+  check_forest_dims(w, h, "rdgpu_d8_flow_accum");
   const size_t n = (size_t)w * h;
   uint8_t *dd = Workspace::get().buf<uint8_t>("host.dirs", n);
   A *da = Workspace::get().buf<A>("host.area", n);
@@ -1071,7 +1068,7 @@ static void d8_flow_accum_host(const uint8_t *dirs, uint8_t nodata, int w, int h
 template <class T>
 static void fa_d8_host(const T *dem, T nodata, int w, int h, double *accum, bool unit_weights = false) {
   if (!dem || !accum) throw Error(RDGPU_ERR_ARG, "rdgpu_fa_d8: null pointer");
-  check_dims(w, h, "rdgpu_fa_d8");
+  check_forest_dims(w, h, "rdgpu_fa_d8");
   const size_t n = (size_t)w * h;
   T *d = Workspace::get().buf<T>("host.dem", n);
   double *da = Workspace::get().buf<double>("host.area", n);
@@ -1351,7 +1348,7 @@ static void accs_free(rdgpu_accum_shard *a) {
 static rdgpu_accum_shard *accs_begin(const uint8_t *d_dirs, uint8_t nodata, int w, int h, const uint8_t *d_above,
                                      const uint8_t *d_below, hipStream_t st, bool local = false) {
   if (!d_dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_accum_shard_begin: null pointer");
-  check_dims(w, h, "rdgpu_accum_shard_begin");
+  check_forest_dims(w, h, "rdgpu_accum_shard_begin");
   rdgpu_accum_shard *a = new rdgpu_accum_shard();
   try {
     a->stream = st;
@@ -1517,7 +1514,7 @@ __global__ __launch_bounds__(256) void k_fm_props(const uint8_t *__restrict__ di
 template <class T>
 static void fm_d8_host(const T *dem, T nodata, int w, int h, float *props9) {
   if (!dem || !props9) throw rdgpu::Error(RDGPU_ERR_ARG, "rdgpu_fm_d8: null pointer");
-  rdgpu::check_dims(w, h, "rdgpu_fm_d8");
+  rdgpu::check_forest_dims(w, h, "rdgpu_fm_d8");
   const size_t n = (size_t)w * h;
   T *d = rdgpu::Workspace::get().buf<T>("host.dem", n);
   uint8_t *dirs = rdgpu::Workspace::get().buf<uint8_t>("accum.fmdirs", n);

@@ -29,8 +29,7 @@
 // LDS per block: 4752 B staged directions (later the 4096 B exit table) + 33792 B words = 38544 B (38800 with the
 // block-wide OR's scratch): four blocks per CU.  58 VGPRs in both tile kernels, 20 in the rounds.
 // Scratch: two buffers of 20 B per node, 256 nodes per 4096 cells: 2.5 B per cell (+ 4 B per cell for HAND's to_cell).
-#include "common.hpp"
-#include "tile_front.hpp"
+#include "d8_forest.hpp"
 
 #include <cmath>
 #include <string>
@@ -46,13 +45,12 @@ constexpr int FP_SX = 16, FP_SY = 28, FP_SD = 40, FP_SK = 52;
 enum { FP_K_NONE = 0, FP_K_SELF = 1, FP_K_EXIT = 2 };   // the end has no drainage cell | is the drainage cell | leaves the tile
 // a node's link: the node it points to, or
 constexpr uint32_t FP_DONE = 0xFFFFFFFFu, FP_FRESH = 0xFFFFFFFEu;   // resolved in both buffers | in this buffer only
-constexpr int FP_RPT = LT / 4;                                       // rows (cells) per thread of a tile pass
 
 struct FpTile {   // a tile's LDS state
   uint8_t sd[SDH * SDW] __attribute__((aligned(16)));   // staged directions (tile_front.hpp); k_fp_final: the exits' answers
   unsigned long long lw[LT * LPS];                      // per cell: its word
 };
-static_assert(sizeof(uint4) * 256 <= SDH * SDW, "the exit table overlays the staged directions");
+static_assert(sizeof(uint4) * TILE_SLOTS <= SDH * SDW, "the exit table overlays the staged directions");
 
 // one step in direction d (1..8) as a tile word's counts: 1, 5 along x; 3, 7 along y; the even codes diagonal
 __device__ __forceinline__ int fp_plane(uint32_t d) { return (d & 1u) ? ((d & 2u) ? 1 : 0) : 2; }
@@ -69,33 +67,24 @@ __device__ __forceinline__ unsigned long long fp_hop(unsigned long long a, unsig
   return (q & FP_PTR) | ((a & ~FP_PTR) + (q & ~FP_PTR));
 }
 
-// the node of the raster cell (gx, gy), a border cell of its tile
-__device__ __forceinline__ uint32_t fp_node(int gx, int gy, uint32_t tilesX) {
-  return ((uint32_t)(gy / LT) * tilesX + (uint32_t)(gx / LT)) * 256u + (uint32_t)border_slot(gx % LT, gy % LT);
-}
-__device__ __forceinline__ void fp_border_cell(int slot, int &bx, int &by) {
-  bx = slot < LT ? slot : slot < 2 * LT ? slot - LT : slot < 3 * LT - 2 ? 0 : LT - 1;
-  by = slot < LT ? 0 : slot < 2 * LT ? LT - 1 : slot < 3 * LT - 2 ? slot - 2 * LT + 1 : slot - (3 * LT - 2) + 1;
-}
-
 // Stages the tile and pointer-jumps every cell to the in-tile end of its path: p[j] is the word of the thread's cell
 // (lx, ly0 + 4 j); with FP_END it names the end, the steps to it and its kind; without, the path runs into a direction
-// loop inside the tile (the flag, not "points to itself", marks an end: see upslope.hip).
+// loop inside the tile (the flag, not "points to itself", marks an end: d8_forest.hpp).
 __device__ __forceinline__ void fp_tile_ends(FpTile &T, const uint8_t *__restrict__ dirs, const uint8_t *__restrict__ chan,
-                                             uint8_t nodata, int w, int h, int x0, int y0, unsigned long long (&p)[FP_RPT]) {
+                                             uint8_t nodata, int w, int h, int x0, int y0, unsigned long long (&p)[FOREST_RPT]) {
   stage_dirs_rows(dirs, w, h, x0, y0, nodata, T.sd);
   const int lx = threadIdx.x & (LT - 1), ly0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   uint32_t stopmask = 0;   // the mask is read once per cell, by the cell's own thread: no LDS copy
   if (chan) {
 #pragma unroll
-    for (int j = 0; j < FP_RPT; j++) {
+    for (int j = 0; j < FOREST_RPT; j++) {
       const int gx = x0 + lx, gy = y0 + ly0 + 4 * j;
       if (gx < w && gy < h && chan[(size_t)gy * w + gx] != 0) stopmask |= 1u << j;
     }
   }
   __syncthreads();
 #pragma unroll
-  for (int j = 0; j < FP_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int ly = ly0 + 4 * j;
     const unsigned long long self = (unsigned long long)(ly * LPS + lx);
     const uint32_t d = T.sd[(ly + 1) * SDW + SDO + lx];
@@ -124,7 +113,7 @@ __device__ __forceinline__ void fp_tile_ends(FpTile &T, const uint8_t *__restric
   for (int it = 0; it < 12; it++) {
     bool moving = false;
 #pragma unroll
-    for (int j = 0; j < FP_RPT; j++) {
+    for (int j = 0; j < FOREST_RPT; j++) {
       unsigned long long a = p[j];
       if (!(a & FP_END)) {
         a = fp_hop(a, fp_load(&T.lw[a & FP_CELL]));
@@ -146,15 +135,15 @@ __global__ __launch_bounds__(NTHR, 4) void k_fp_tile(const uint8_t *__restrict__
   const uint32_t t = xcd_tile(blockIdx.x, ntiles);
   if (t >= ntiles) return;
   const int x0 = (int)(t % tilesX) * LT, y0 = (int)(t / tilesX) * LT;
-  unsigned long long p[FP_RPT];
+  unsigned long long p[FOREST_RPT];
   fp_tile_ends(T, dirs, chan, nodata, w, h, x0, y0, p);
   // what a path that ENTERS the tile at a border cell comes to, one border cell per thread
   const int slot = (int)threadIdx.x;
   uint32_t l = FP_FRESH;
   uint4 v = make_uint4(FP_NONE, 0u, 0u, 0u);   // (the four spare slots; a path into an in-tile loop; an end without a drainage cell)
-  if (slot < 4 * LT - 4) {
+  if (slot < BORDER_SLOTS) {
     int bx, by;
-    fp_border_cell(slot, bx, by);
+    border_cell(slot, bx, by);
     const unsigned long long a = T.lw[by * LPS + bx];
     const int kind = (int)(a >> FP_SK) & 3;
     if ((a & FP_END) && kind != FP_K_NONE) {
@@ -169,12 +158,12 @@ __global__ __launch_bounds__(NTHR, 4) void k_fp_tile(const uint8_t *__restrict__
         const int pl = fp_plane(d);
         v.y += pl == 0; v.z += pl == 1; v.w += pl == 2;
         v.x = 0u;
-        l = fp_node(x0 + ex + d8dx((int)d), y0 + ey + d8dy((int)d), tilesX);
+        l = tile_node(x0 + ex + d8dx((int)d), y0 + ey + d8dy((int)d), tilesX);
       }
     }
   }
-  link[(size_t)t * 256 + slot] = l;
-  val[(size_t)t * 256 + slot] = v;
+  link[(size_t)t * TILE_SLOTS + slot] = l;
+  val[(size_t)t * TILE_SLOTS + slot] = v;
 }
 
 // One doubling round from (ls, vs) into (ld, vd).  flags[r]: round r left a node open.
@@ -211,19 +200,19 @@ __global__ __launch_bounds__(NTHR, 4) void k_fp_final(const uint8_t *__restrict_
   const uint32_t t = xcd_tile(blockIdx.x, ntiles);
   if (t >= ntiles) return;
   const int x0 = (int)(t % tilesX) * LT, y0 = (int)(t / tilesX) * LT;
-  unsigned long long p[FP_RPT];
+  unsigned long long p[FOREST_RPT];
   fp_tile_ends(T, dirs, chan, nodata, w, h, x0, y0, p);
   // the exits' answers, one border cell per thread: a node is resolved in at least one of the two buffers, or not at all
   const int slot = (int)threadIdx.x;
   uint4 ans = make_uint4(FP_NONE, 0u, 0u, 0u);
-  if (slot < 4 * LT - 4) {
+  if (slot < BORDER_SLOTS) {
     int bx, by;
-    fp_border_cell(slot, bx, by);
+    border_cell(slot, bx, by);
     const unsigned long long self = (unsigned long long)(by * LPS + bx);
     const unsigned long long a = T.lw[self];
     if ((a & FP_PTR) == (self | FP_END) && ((int)(a >> FP_SK) & 3) == FP_K_EXIT) {
       const uint32_t d = T.sd[(by + 1) * SDW + SDO + bx];
-      const uint32_t nid = fp_node(x0 + bx + d8dx((int)d), y0 + by + d8dy((int)d), tilesX);
+      const uint32_t nid = tile_node(x0 + bx + d8dx((int)d), y0 + by + d8dy((int)d), tilesX);
       const uint4 *src = val_a;
       uint32_t l = link_a[nid];
       if (l < FP_FRESH) { l = link_b[nid]; src = val_b; }
@@ -241,7 +230,7 @@ __global__ __launch_bounds__(NTHR, 4) void k_fp_final(const uint8_t *__restrict_
   const int lx = threadIdx.x & (LT - 1), ly0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const size_t plane = (size_t)w * h;
 #pragma unroll
-  for (int j = 0; j < FP_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int gx = x0 + lx, gy = y0 + ly0 + 4 * j;
     if (gx >= w || gy >= h) continue;
     const unsigned long long a = p[j];
@@ -261,9 +250,7 @@ __global__ __launch_bounds__(NTHR, 4) void k_fp_final(const uint8_t *__restrict_
     const size_t g = (size_t)gy * w + gx;
     if (to_cell) to_cell[g] = tc;
     if (steps) { steps[g] = nx; steps[plane + g] = ny; steps[2 * plane + g] = nd; }
-    if (dist)   // two roundings per term, never a fused multiply-add: a numpy model reproduces it bit for bit
-      dist[g] = tc == FP_NONE ? dist_nodata
-                              : __dadd_rn(__dadd_rn(__dmul_rn((double)nx, cx), __dmul_rn((double)ny, cy)), __dmul_rn((double)nd, diag));
+    if (dist) dist[g] = tc == FP_NONE ? dist_nodata : d8_path_length(nx, ny, nd, cx, cy, diag);
   }
 }
 
@@ -284,30 +271,28 @@ __global__ __launch_bounds__(NTHR) void k_fp_hand(const T *__restrict__ dem, T d
 // ---- drivers ----------------------------------------------------------------------------------------------------------
 static void fp_check_dims(const void *dirs, int w, int h, const char *who) {
   if (!dirs) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, std::string(who) + ": width and height must be positive");
-  if ((uint64_t)w * (uint64_t)h > 0xFFFF0000ull) throw Error(RDGPU_ERR_ARG, std::string(who) + ": raster too large");
+  check_forest_dims(w, h, who);
 }
 static void fp_check_path_args(const void *dirs, int w, int h, double cx, double cy, const void *to_cell, const void *steps,
                                const void *dist, const char *who) {
   fp_check_dims(dirs, w, h, who);
   if (!to_cell && !steps && !dist) throw Error(RDGPU_ERR_ARG, std::string(who) + ": no output requested");
-  if (!std::isfinite(cx) || !std::isfinite(cy) || cx == 0 || cy == 0)
-    throw Error(RDGPU_ERR_ARG, std::string(who) + ": the cell lengths must be finite and non-zero");
+  check_cell_lengths(cx, cy, who);
 }
 
-// arguments checked by the caller
-static void flow_path_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, const uint8_t *d_chan, double cx, double cy,
-                             uint32_t *d_to_cell, uint32_t *d_steps, double *d_dist, double dist_nodata, hipStream_t s) {
+// arguments checked by the caller (declared in d8_forest.hpp: longest.hip runs it too)
+void flow_path_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, const uint8_t *d_chan, double cx, double cy,
+                      uint32_t *d_to_cell, uint32_t *d_steps, double *d_dist, double dist_nodata, hipStream_t s) {
   cx = std::fabs(cx);
   cy = std::fabs(cy);
   const double diag = std::sqrt(cx * cx + cy * cy);
-  const uint32_t tilesX = (w + LT - 1) / LT, ntiles = tilesX * ((h + LT - 1) / LT);
-  const uint64_t nnodes = (uint64_t)ntiles * 256;
+  const ForestDims fd(w, h);
+  const uint32_t tilesX = fd.tilesX, ntiles = fd.ntiles;
+  const uint64_t nnodes = fd.nnodes;
   Workspace &ws = Workspace::get();
   uint32_t *link[2] = {ws.buf<uint32_t>("flowpath.link_a", nnodes), ws.buf<uint32_t>("flowpath.link_b", nnodes)};
   uint4 *val[2] = {ws.buf<uint4>("flowpath.val_a", nnodes), ws.buf<uint4>("flowpath.val_b", nnodes)};
-  int rounds = 1;
-  while ((1ull << (rounds - 1)) < nnodes) rounds++;   // ceil(log2(nodes)) + 1
+  const int rounds = forest_rounds(nnodes);
   uint32_t *flags = ws.buf<uint32_t>("flowpath.flags", (size_t)rounds);
   RD_HIP(hipMemsetAsync(flags, 0, (size_t)rounds * sizeof(uint32_t), s));
   RD_LAUNCH("flowpath.tile", k_fp_tile, dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_dirs, d_chan, nodata, w, h, tilesX, ntiles, link[0],

@@ -6,15 +6,15 @@
 // greatest distance D to the OUTLET: an upslope maximum of a fixed per-cell value, closed downstream as extreme.hip closes
 // its keys.  D is a double, so value and cell index no longer fit the one 64-bit word extreme.hip pushes; they are closed
 // one after the other.
-//   flow-path engine   the three step planes of every cell (rdgpu_d8_flow_path_dev without a mask) into scratch; D is
-//                      evaluated from them where it is needed, with the engine's own expression: the same bits.
-//   k_lp_links         extreme.hip's k_ex_links: the node a path that enters a tile at a border cell leaves it to.  This
-//                      buffer is only read afterwards: both closures start their doubling from it.
+//   flow-path engine   the three step planes of every cell (flow_path_device without a mask) into scratch; D is evaluated
+//                      from them where it is needed, with the engine's own d8_path_length: the same bits.
+//   k_forest_links     the node links (d8_forest.hpp).  This buffer is only read afterwards: both closures start their
+//                      doubling from it.
 //   CLOSURE 1, the value.  key = bits(D) + 1, monotone as an unsigned integer because D is finite and >= 0; 0 is "no
 //   contribution", which D == 0.0 at an outlet must not be.  Cells without a path have no key.
 //   k_lp_tile<KEYS>    own keys closed in the tile (ds_max_rtn_u64 over doubled pointers), exits raise their node.
-//   k_lp_round<u64>    ceil(log2(nodes)) + 1 gated rounds, pointers doubled between two buffers.  nkey[i] is then the
-//                      greatest key that ENTERS the tile at border cell i.
+//   k_forest_round     ceil(log2(nodes)) + 1 gated rounds over the 64-bit keys, pointers doubled between two buffers.
+//                      nkey[i] is then the greatest key that ENTERS the tile at border cell i.
 //   CLOSURE 2, the index.  M(c), the closed key of cell c, never falls downstream.  A link c -> t is KEPT iff
 //   M(t) == M(c) != 0 and CUT otherwise; a pointer doubled over kept links only has equal M all the way along it, so a
 //   push over it carries a cell of U(target) that holds the target's maximum, and nothing else ever arrives.  A cell starts
@@ -23,7 +23,7 @@
 //   k_lp_tile<HEADS>   M rebuilt in the tile (own keys + nkey of the tile's border slots, closed), kept links, indices
 //                      closed in LDS (ds_max_rtn_u32); an exit raises nidx of its node iff nkey there equals its own M.
 //   k_lp_cut           the kept node links: i -> n iff nkey[n] == nkey[i] != 0.
-//   k_lp_round<u32>    the same gated rounds over the kept links.
+//   k_forest_round     the same gated rounds over the kept links and the 32-bit indices.
 //   k_lp_tile<WRITE>   as HEADS, with nidx of a border slot joining its cell's start iff nkey there equals the cell's M;
 //                      every cell decoded: the head's steps gathered, the cell's own subtracted, the planes written.
 //   k_lp_basin         on_basin_path = from_cell[v] == from_cell[to_cell[v]] in a pass of its own: the outlet's head is
@@ -31,15 +31,11 @@
 //                      scratch) and gathers one word.  The alternative, a third closure that brings head(outlet) back UP
 //                      the forest, would have cost a pull-style node table and one more tile pass.
 //
-// Races.  Every shared word that changes is changed by ONE atomic maximum (64-bit keys, 32-bit indices, in LDS and in
-// global memory), keys and indices only grow, and a push is idempotent: what arrives early is what arrives anyway.  The
-// only words too wide for that are the doubled pointers: in LDS they double synchronously (read, barrier, store), over
-// the nodes from one buffer into the other (DESIGN 6d's discipline).  M is final before closure 2 reads it (kernel order
-// on the stream; a barrier in the tile), so which links are kept does not depend on timing.
-// Termination.  extreme.hip's argument for both closures (kept links form a sub-forest): 12 rounds in a tile,
-// ceil(log2(nodes)) + 1 over the nodes, a round that raises nothing ends them early.  Cells on or draining into a
-// direction loop have no path, hence no key and no index; nothing with a key lies upstream of them, so they raise nothing
-// and receive nothing, their links are cut (M == 0), and the rounds over them end on the flag.
+// Races and termination: d8_forest.hpp's argument, for both closures (kept links form a sub-forest; the words are 64-bit
+// keys, then 32-bit indices).  M is final before closure 2 reads it (kernel order on the stream; a barrier in the tile), so
+// which links are kept does not depend on timing.  Cells on or draining into a direction loop have no path, hence no key
+// and no index; nothing with a key lies upstream of them, so they raise nothing and receive nothing, their links are cut
+// (M == 0), and the rounds over them end on the flag.
 //
 // No host synchronisation in the device driver; the flow-path engine's launches + 3 memsets + 5 + 2 rounds launches (+ 1
 // for on_basin_path), fixed by the raster's size.
@@ -48,8 +44,7 @@
 // Scratch: 12 B per cell for the step planes, the flow-path engine's 2.5, and per node three pointer buffers, a key and an
 // index (24 B; 256 nodes per 4096 cells: 1.5 B per cell); on_basin_path keeps to_cell (4 B per cell) and, where from_cell
 // is not requested, from_cell (4 more).
-#include "common.hpp"
-#include "tile_front.hpp"
+#include "d8_forest.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -60,16 +55,9 @@ namespace rdgpu {
 
 typedef unsigned long long lpkey_t;
 
-constexpr uint32_t LP_NONE = 0xFFFFFFFFu;
-constexpr uint32_t LP_END = 0x8000u, LP_CELL = 0x7FFFu;   // k_lp_links' tile pointers: | LP_END when the cell is the END of the path
-constexpr int LP_RPT = LT / 4;                            // rows (cells) per thread of a tile pass
-constexpr int LP_JUMPS = 12;                              // 2^12 = 4096 cells: any path or loop inside a tile
+constexpr uint32_t LP_NONE = 0xFFFFFFFFu;   // no path (the flow-path engine's steps), no head, no kept link
 enum { LP_KEYS = 0, LP_HEADS = 1, LP_WRITE = 2 };
 
-struct LpLinkTile {
-  uint8_t sd[SDH * SDW] __attribute__((aligned(4)));   // staged directions (tile_front.hpp)
-  uint16_t lp[LT * LPS];                               // per cell: a cell further down its in-tile path
-};
 struct LpTile {
   uint8_t sd[SDH * SDW] __attribute__((aligned(8)));
   uint16_t lp[LT * LPS];
@@ -78,102 +66,6 @@ struct LpTile {
     uint32_t idx[LT * LPS];   // closure 2, per cell: the best index known to reach it (after the keys have been read)
   } __attribute__((aligned(8)));
 };
-
-// the link of the cell (lx, ly) of the staged tile, as extreme.hip's ex_link: -1 the cell is NoData (or outside the raster:
-// staged as NoData), 0 none (its path ends here), 1 to (tx, ty) inside the tile, 2 to (tx, ty) in another tile.  These are
-// the links of the flow-path engine without a mask.
-__device__ __forceinline__ int lp_link(const uint8_t *sd, uint8_t nodata, int lx, int ly, int &tx, int &ty) {
-  const uint32_t d = sd[(ly + 1) * SDW + SDO + lx];
-  tx = lx; ty = ly;
-  if (d == nodata) return -1;
-  if (d - 1u >= 8u) return 0;
-  tx = lx + d8dx((int)d); ty = ly + d8dy((int)d);
-  if (sd[(ty + 1) * SDW + SDO + tx] == nodata) return 0;
-  return (tx >= 0 && tx < LT && ty >= 0 && ty < LT) ? 1 : 2;
-}
-__device__ __forceinline__ uint32_t lp_node(int gx, int gy, uint32_t tilesX) {
-  return ((uint32_t)(gy / LT) * tilesX + (uint32_t)(gx / LT)) * 256u + (uint32_t)border_slot(gx % LT, gy % LT);
-}
-__device__ __forceinline__ void lp_border_cell(int slot, int &bx, int &by) {
-  bx = slot < LT ? slot : slot < 2 * LT ? slot - LT : slot < 3 * LT - 2 ? 0 : LT - 1;
-  by = slot < LT ? 0 : slot < 2 * LT ? LT - 1 : slot < 3 * LT - 2 ? slot - 2 * LT + 1 : slot - (3 * LT - 2) + 1;
-}
-// the flow-path engine's dist of three step counts: two roundings per term, never a fused multiply-add
-__device__ __forceinline__ double lp_length(uint32_t nx, uint32_t ny, uint32_t nd, double cx, double cy, double diag) {
-  return __dadd_rn(__dadd_rn(__dmul_rn((double)nx, cx), __dmul_rn((double)ny, cy)), __dmul_rn((double)nd, diag));
-}
-
-// ---- the link forest of the border cells (extreme.hip's k_ex_links) ----------------------------------------------------------
-__global__ __launch_bounds__(NTHR, 5) void k_lp_links(const uint8_t *__restrict__ dirs, uint8_t nodata, int w, int h, uint32_t tilesX,
-                                                      uint32_t ntiles, uint32_t *__restrict__ nxt0) {
-  __shared__ LpLinkTile T;
-  const uint32_t t = xcd_tile(blockIdx.x, ntiles);
-  if (t >= ntiles) return;
-  const int x0 = (int)(t % tilesX) * LT, y0 = (int)(t / tilesX) * LT;
-  stage_dirs_rows(dirs, w, h, x0, y0, nodata, T.sd);
-  __syncthreads();
-  const int lx = threadIdx.x & (LT - 1), ly0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  uint32_t p[LP_RPT], q[LP_RPT];
-#pragma unroll
-  for (int j = 0; j < LP_RPT; j++) {
-    const int ly = ly0 + 4 * j;
-    const uint32_t self = (uint32_t)(ly * LPS + lx);
-    int tx, ty;
-    const int kind = lp_link(T.sd, nodata, lx, ly, tx, ty);
-    p[j] = kind == 1 ? (uint32_t)(ty * LPS + tx) : (self | LP_END);
-    T.lp[self] = (uint16_t)p[j];
-  }
-  __syncthreads();
-  // synchronous doubling: after round r a pointer without LP_END covers exactly 2^(r+1) cells
-#pragma unroll 1
-  for (int it = 0; it < LP_JUMPS; it++) {
-    bool moving = false;
-#pragma unroll
-    for (int j = 0; j < LP_RPT; j++) q[j] = (p[j] & LP_END) ? p[j] : T.lp[p[j]];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < LP_RPT; j++) {
-      p[j] = q[j];
-      moving |= !(q[j] & LP_END);
-      T.lp[(ly0 + 4 * j) * LPS + lx] = (uint16_t)q[j];
-    }
-    if (!__syncthreads_or(moving)) break;
-  }
-  // one border cell per thread (a pointer without LP_END after the last round: into a loop inside the tile)
-  const int slot = (int)threadIdx.x;
-  uint32_t word = LP_NONE;
-  if (slot < 4 * LT - 4) {
-    int bx, by, tx, ty;
-    lp_border_cell(slot, bx, by);
-    const uint32_t rp = T.lp[by * LPS + bx], root = rp & LP_CELL;
-    if (rp & LP_END) {
-      const int ry = (int)root / LPS, rx = (int)root - ry * LPS;
-      if (lp_link(T.sd, nodata, rx, ry, tx, ty) == 2) word = lp_node(x0 + tx, y0 + ty, tilesX);
-    }
-  }
-  nxt0[(size_t)t * 256 + slot] = word;
-}
-
-// ---- one doubling round over the nodes (extreme.hip's k_ex_round; K: the 64-bit keys or the 32-bit indices) ------------------
-// From src into dst (never in place: every node covers the same distance); a node raises the word of the node it points to
-// (one global_atomic_umax[_x2]).  flag_out: a word was raised.
-template <class K>
-__global__ __launch_bounds__(NTHR) void k_lp_round(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, K *nval, uint32_t nnodes,
-                                                   const uint32_t *__restrict__ gate, uint32_t *flag_out) {
-  if (*gate == 0) return;
-  bool flag = false;
-  for (uint32_t i = blockIdx.x * NTHR + threadIdx.x; i < nnodes; i += gridDim.x * NTHR) {   // (nnodes: a multiple of NTHR)
-    const uint32_t n = src[i];
-    uint32_t n2 = LP_NONE;
-    if (n < nnodes) {
-      n2 = src[n];
-      const K k = __hip_atomic_load(&nval[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (k != 0) flag |= atomicMax(&nval[n], k) < k;
-    }
-    dst[i] = n2;
-  }
-  if (__any(flag) && (threadIdx.x & 63) == 0) *flag_out = 1;
-}
 
 // the node links closure 2 keeps, from the un-doubled links and the closed node keys
 __global__ __launch_bounds__(NTHR) void k_lp_cut(const uint32_t *__restrict__ nxt0, const lpkey_t *__restrict__ nkey,
@@ -190,33 +82,6 @@ __global__ __launch_bounds__(NTHR) void k_lp_cut(const uint32_t *__restrict__ nx
 }
 
 // ---- the two closures inside a tile ------------------------------------------------------------------------------------------
-// Pushes the words of W (S.key or S.idx) down the pointers in S.lp, which every thread holds in p[] for its own cells:
-// round r pushes by 2^r; a round that raises nothing has closed them.  Ends behind a barrier.
-template <class K>
-__device__ __forceinline__ void lp_close(LpTile &S, K *W, uint32_t (&p)[LP_RPT], bool any, int lx, int ly0) {
-  if (!__syncthreads_or(any)) return;
-  uint32_t q[LP_RPT];
-#pragma unroll 1
-  for (int it = 0; it < LP_JUMPS; it++) {
-    bool fresh = false;
-#pragma unroll
-    for (int j = 0; j < LP_RPT; j++) q[j] = S.lp[p[j]];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < LP_RPT; j++) {
-      const uint32_t self = (uint32_t)((ly0 + 4 * j) * LPS + lx);
-      if (p[j] != self) {
-        const K k = __hip_atomic_load(&W[self], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (k != 0) fresh |= atomicMax(&W[p[j]], k) < k;
-      }
-      S.lp[self] = (uint16_t)q[j];
-    }
-    if (!__syncthreads_or(fresh)) break;
-#pragma unroll
-    for (int j = 0; j < LP_RPT; j++) p[j] = q[j];
-  }
-}
-
 // LP_KEYS:  keys = the cells' own; closed in the tile; a cell whose link leaves the tile raises the key of its node.
 // LP_HEADS: keys = own and the node keys of the tile's border slots, closed: M.  Indices over the kept links, closed; a
 //           cell whose link leaves the tile raises the index of its node iff the node's key is its M.
@@ -236,33 +101,33 @@ __global__ __launch_bounds__(NTHR, 3) void k_lp_tile(const uint8_t *__restrict__
   stage_dirs_rows(dirs, w, h, x0, y0, nodata, S.sd);
   const int lx = threadIdx.x & (LT - 1), ly0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   // the steps to the outlet are read once per cell by the cell's own thread; no path: no key
-  lpkey_t own[LP_RPT];
+  lpkey_t own[FOREST_RPT];
 #pragma unroll
-  for (int j = 0; j < LP_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int gx = x0 + lx, gy = y0 + ly0 + 4 * j;
     own[j] = 0;
     if (gx < w && gy < h) {
       const size_t g = (size_t)gy * w + gx;
       const uint32_t nx = sfp[g];
       if (nx != LP_NONE)
-        own[j] = (lpkey_t)__double_as_longlong(lp_length(nx, sfp[plane + g], sfp[2 * plane + g], cx, cy, diag)) + 1ull;
+        own[j] = (lpkey_t)__double_as_longlong(d8_path_length(nx, sfp[plane + g], sfp[2 * plane + g], cx, cy, diag)) + 1ull;
     }
   }
   __syncthreads();
-  uint32_t p[LP_RPT];
+  uint32_t p[FOREST_RPT];
   uint32_t exitmask = 0;
   bool keyed = false;
 #pragma unroll
-  for (int j = 0; j < LP_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int ly = ly0 + 4 * j;
     const uint32_t self = (uint32_t)(ly * LPS + lx);
     int tx, ty;
-    const int kind = lp_link(S.sd, nodata, lx, ly, tx, ty);
+    const int kind = forest_link(S.sd, nodata, lx, ly, tx, ty);
     lpkey_t k = own[j];   // (0 on NoData cells: they have no path)
     if (MODE != LP_KEYS && kind >= 0) {
       const int slot = border_slot(lx, ly);
       if (slot >= 0) {
-        const lpkey_t nk = nkey[(size_t)t * 256 + slot];
+        const lpkey_t nk = nkey[(size_t)t * TILE_SLOTS + slot];
         k = nk > k ? nk : k;
       }
     }
@@ -272,34 +137,22 @@ __global__ __launch_bounds__(NTHR, 3) void k_lp_tile(const uint8_t *__restrict__
     S.key[self] = k;
     keyed |= k != 0;
   }
-  lp_close<lpkey_t>(S, S.key, p, keyed, lx, ly0);
+  forest_close(S.lp, p, keyed, lx, ly0, [&](uint32_t self, uint32_t to) { return forest_push_max(S.key, self, to); });
   if (MODE == LP_KEYS) {
-    bool pushed = false;
-#pragma unroll
-    for (int j = 0; j < LP_RPT; j++) {
-      if (!(exitmask >> j & 1u)) continue;
-      const int ly = ly0 + 4 * j;
-      const lpkey_t k = S.key[ly * LPS + lx];
-      if (k == 0) continue;
-      int tx, ty;
-      lp_link(S.sd, nodata, lx, ly, tx, ty);
-      atomicMax(&nkey[lp_node(x0 + tx, y0 + ty, tilesX)], k);   // (the target is not NoData: inside the raster)
-      pushed = true;
-    }
-    if (__any(pushed) && (threadIdx.x & 63) == 0) *flag_out = 1;
+    forest_push_exits(S.sd, nodata, S.key, exitmask, lx, ly0, x0, y0, tilesX, nkey, flag_out);
     return;
   }
   // closure 2.  M of the cell and of its target, the kept link and the cell's start, all read before the indices
   // overwrite the keys
-  lpkey_t m[LP_RPT];
-  uint32_t start[LP_RPT];
+  lpkey_t m[FOREST_RPT];
+  uint32_t start[FOREST_RPT];
   bool headed = false;
 #pragma unroll
-  for (int j = 0; j < LP_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int ly = ly0 + 4 * j;
     const uint32_t self = (uint32_t)(ly * LPS + lx);
     int tx, ty;
-    const int kind = lp_link(S.sd, nodata, lx, ly, tx, ty);
+    const int kind = forest_link(S.sd, nodata, lx, ly, tx, ty);
     m[j] = S.key[self];
     p[j] = (kind == 1 && m[j] != 0 && S.key[ty * LPS + tx] == m[j]) ? (uint32_t)(ty * LPS + tx) : self;
     uint32_t k = 0;
@@ -307,8 +160,8 @@ __global__ __launch_bounds__(NTHR, 3) void k_lp_tile(const uint8_t *__restrict__
       if (own[j] == m[j]) k = LP_NONE - ((uint32_t)(y0 + ly) * (uint32_t)w + (uint32_t)(x0 + lx));
       if (MODE == LP_WRITE) {
         const int slot = border_slot(lx, ly);
-        if (slot >= 0 && nkey[(size_t)t * 256 + slot] == m[j]) {
-          const uint32_t nk = nidx[(size_t)t * 256 + slot];
+        if (slot >= 0 && nkey[(size_t)t * TILE_SLOTS + slot] == m[j]) {
+          const uint32_t nk = nidx[(size_t)t * TILE_SLOTS + slot];
           k = nk > k ? nk : k;
         }
       }
@@ -318,23 +171,23 @@ __global__ __launch_bounds__(NTHR, 3) void k_lp_tile(const uint8_t *__restrict__
   }
   __syncthreads();   // the keys have been read for the last time
 #pragma unroll
-  for (int j = 0; j < LP_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const uint32_t self = (uint32_t)((ly0 + 4 * j) * LPS + lx);
     S.lp[self] = (uint16_t)p[j];
     S.idx[self] = start[j];
   }
-  lp_close<uint32_t>(S, S.idx, p, headed, lx, ly0);
+  forest_close(S.lp, p, headed, lx, ly0, [&](uint32_t self, uint32_t to) { return forest_push_max(S.idx, self, to); });
   if (MODE == LP_HEADS) {
     bool pushed = false;
 #pragma unroll
-    for (int j = 0; j < LP_RPT; j++) {
+    for (int j = 0; j < FOREST_RPT; j++) {
       if (!(exitmask >> j & 1u)) continue;
       const int ly = ly0 + 4 * j;
       const uint32_t k = S.idx[ly * LPS + lx];
       if (k == 0) continue;
       int tx, ty;
-      lp_link(S.sd, nodata, lx, ly, tx, ty);
-      const uint32_t n = lp_node(x0 + tx, y0 + ty, tilesX);
+      forest_link(S.sd, nodata, lx, ly, tx, ty);
+      const uint32_t n = tile_node(x0 + tx, y0 + ty, tilesX);
       if (nkey[n] != m[j]) continue;   // the link is cut: something farther away enters that cell from elsewhere
       atomicMax(&nidx[n], k);
       pushed = true;
@@ -342,7 +195,7 @@ __global__ __launch_bounds__(NTHR, 3) void k_lp_tile(const uint8_t *__restrict__
     if (__any(pushed) && (threadIdx.x & 63) == 0) *flag_out = 1;
   } else {
 #pragma unroll
-    for (int j = 0; j < LP_RPT; j++) {
+    for (int j = 0; j < FOREST_RPT; j++) {
       const int ly = ly0 + 4 * j, gx = x0 + lx, gy = y0 + ly;
       if (gx >= w || gy >= h) continue;
       const uint32_t k = S.idx[ly * LPS + lx];
@@ -358,7 +211,7 @@ __global__ __launch_bounds__(NTHR, 3) void k_lp_tile(const uint8_t *__restrict__
       }
       if (from_cell) from_cell[g] = fc;
       if (steps) { steps[g] = nx; steps[plane + g] = ny; steps[2 * plane + g] = nd; }
-      if (length) length[g] = fc == LP_NONE ? length_nodata : lp_length(nx, ny, nd, cx, cy, diag);
+      if (length) length[g] = fc == LP_NONE ? length_nodata : d8_path_length(nx, ny, nd, cx, cy, diag);
     }
   }
 }
@@ -376,10 +229,8 @@ static void lp_check_args(const void *dirs, int w, int h, double cx, double cy, 
                           const void *length, const void *on_basin_path, const char *who) {
   if (!dirs) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
   if (!from_cell && !steps && !length && !on_basin_path) throw Error(RDGPU_ERR_ARG, std::string(who) + ": no output requested");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, std::string(who) + ": width and height must be positive");
-  if ((uint64_t)w * (uint64_t)h > 0xFFFF0000ull) throw Error(RDGPU_ERR_ARG, std::string(who) + ": raster too large");
-  if (!std::isfinite(cx) || !std::isfinite(cy) || cx == 0 || cy == 0)
-    throw Error(RDGPU_ERR_ARG, std::string(who) + ": the cell lengths must be finite and non-zero");
+  check_forest_dims(w, h, who);
+  check_cell_lengths(cx, cy, who);
 }
 
 // arguments checked by the caller
@@ -389,10 +240,9 @@ static void longest_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, 
   cy = std::fabs(cy);
   const double diag = std::sqrt(cx * cx + cy * cy);   // (the flow-path engine's expression)
   const uint64_t n = (uint64_t)w * h;
-  const uint32_t tilesX = (w + LT - 1) / LT, ntiles = tilesX * ((h + LT - 1) / LT);
-  const uint32_t nnodes = ntiles * 256u;   // (at most 0xFFFF0000 cells: below 2^29 nodes)
-  int rounds = 1;
-  while ((1ull << (rounds - 1)) < nnodes) rounds++;   // ceil(log2(nodes)) + 1
+  const ForestDims fd(w, h);
+  const uint32_t tilesX = fd.tilesX, ntiles = fd.ntiles, nnodes = (uint32_t)fd.nnodes;
+  const int rounds = forest_rounds(nnodes);
   Workspace &ws = Workspace::get();
   uint32_t *sfp = ws.buf<uint32_t>("longest.steps", 3 * n);
   uint32_t *tc = d_on_basin_path ? ws.buf<uint32_t>("longest.to_cell", n) : nullptr;
@@ -403,25 +253,23 @@ static void longest_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, 
   uint32_t *nidx = ws.buf<uint32_t>("longest.nidx", nnodes);
   // flags, per closure c = 0, 1 at c * (rounds + 1): [0] the tile pass raised a node word | [1 + r] round r raised one
   uint32_t *flags = ws.buf<uint32_t>("longest.flags", 2 * ((size_t)rounds + 1));
-  // the recursive device lock is held: the engine's own entry runs inside this one
-  const int rc = rdgpu_d8_flow_path_dev(d_dirs, nodata, w, h, nullptr, cx, cy, tc, sfp, nullptr, 0.0, (void *)s);
-  if (rc != RDGPU_OK) throw Error(rc, rdgpu_last_error());
+  flow_path_device(d_dirs, nodata, w, h, nullptr, cx, cy, tc, sfp, nullptr, 0.0, s);   // (lp_check_args covers its checks)
   RD_HIP(hipMemsetAsync(flags, 0, 2 * ((size_t)rounds + 1) * sizeof(uint32_t), s));
   RD_HIP(hipMemsetAsync(nkey, 0, (size_t)nnodes * sizeof(lpkey_t), s));
   RD_HIP(hipMemsetAsync(nidx, 0, (size_t)nnodes * sizeof(uint32_t), s));
   const uint32_t rgrid = std::min<uint32_t>(ntiles, 2048u);
   uint32_t *const f1 = flags, *const f2 = flags + rounds + 1;
-  RD_LAUNCH("longest.links", k_lp_links, dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_dirs, nodata, w, h, tilesX, ntiles, nxt0);
+  RD_LAUNCH("longest.links", k_forest_links, dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_dirs, nodata, w, h, tilesX, ntiles, nxt0);
   RD_LAUNCH("longest.keys", (k_lp_tile<LP_KEYS>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_dirs, nodata, (const uint32_t *)sfp, w, h,
             tilesX, ntiles, cx, cy, diag, nkey, nidx, f1, (uint32_t *)nullptr, (uint32_t *)nullptr, (double *)nullptr, 0.0);
   for (int r = 0; r < rounds; r++)   // (round 0 reads the kept buffer; every round writes every word of its target)
-    RD_LAUNCH("longest.key_round", (k_lp_round<lpkey_t>), dim3(rgrid), dim3(NTHR), 0, s, (const uint32_t *)(r ? pp[(r + 1) & 1] : nxt0),
+    RD_LAUNCH("longest.key_round", (k_forest_round<lpkey_t>), dim3(rgrid), dim3(NTHR), 0, s, (const uint32_t *)(r ? pp[(r + 1) & 1] : nxt0),
               pp[r & 1], nkey, nnodes, (const uint32_t *)(f1 + r), f1 + r + 1);
   RD_LAUNCH("longest.heads", (k_lp_tile<LP_HEADS>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_dirs, nodata, (const uint32_t *)sfp, w, h,
             tilesX, ntiles, cx, cy, diag, nkey, nidx, f2, (uint32_t *)nullptr, (uint32_t *)nullptr, (double *)nullptr, 0.0);
   RD_LAUNCH("longest.cut", k_lp_cut, dim3(nnodes / NTHR), dim3(NTHR), 0, s, (const uint32_t *)nxt0, (const lpkey_t *)nkey, pp[1], nnodes);
   for (int r = 0; r < rounds; r++)
-    RD_LAUNCH("longest.head_round", (k_lp_round<uint32_t>), dim3(rgrid), dim3(NTHR), 0, s, (const uint32_t *)pp[(r + 1) & 1], pp[r & 1],
+    RD_LAUNCH("longest.head_round", (k_forest_round<uint32_t>), dim3(rgrid), dim3(NTHR), 0, s, (const uint32_t *)pp[(r + 1) & 1], pp[r & 1],
               nidx, nnodes, (const uint32_t *)(f2 + r), f2 + r + 1);
   RD_LAUNCH("longest.write", (k_lp_tile<LP_WRITE>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_dirs, nodata, (const uint32_t *)sfp, w, h,
             tilesX, ntiles, cx, cy, diag, nkey, nidx, (uint32_t *)nullptr, fc, d_steps, d_length, length_nodata);

@@ -8,11 +8,9 @@
 // and order(v) = max { k : v in S_k }.  A level k is therefore "mark the junctions of S_k, close the marks downstream",
 // and the closure is what the link forest of accum.hip / upslope.hip is built for, run with marks instead of sums:
 //   k_so_init    order <- 1 on channel cells, 0 elsewhere: from here on "order != 0" IS the channel mask.
-//   k_so_links   every 64 x 64 tile once: each cell pointer-jumped (synchronously: equal distances) to the in-tile end of
-//                its channel path; a border cell publishes the node its path leaves the tile to (nxt0: one word per border
-//                cell, 256 slots per tile).  What has no end after 4096 steps runs into a loop inside the tile, and the
-//                cell it has reached lies ON the loop -- the jump is a rotation of the loop, so every loop cell is
-//                reached by one: those get 255.
+//   k_so_links   the node links of the channel paths, as d8_forest.hpp's k_forest_links with the channel mask.  What has
+//                no end after 4096 steps runs into a loop inside the tile, and the cell it has reached lies ON the loop --
+//                the jump is a rotation of the loop, so every loop cell is reached by one: those get 255.
 //   loops across tiles: the same argument on the nodes (k_so_round without marks, ping-pong buffers so that every node
 //                covers the same distance; k_so_loopmark marks what the unfinished nodes have reached), then
 //                k_so_close<SO_LOOPS> writes 255 along the in-tile paths below the marked entries.
@@ -25,8 +23,7 @@
 //   A level returns at once (a device-side flag, no host synchronisation) when the level before it found no junction, and
 //   a tile is skipped at level k when it holds no cell of order k (tmax: S_{k+1} lies inside S_k).
 // Loop cells are children of loop cells only, so 255 never enters a finite order; their tributaries are ordinary trees.
-#include "common.hpp"
-#include "tile_front.hpp"
+#include "d8_forest.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -34,11 +31,7 @@
 
 namespace rdgpu {
 
-constexpr uint32_t SO_NONE = 0xFFFFFFFFu;
 constexpr uint32_t SO_ORDER_LOOP = 255u;
-constexpr uint32_t SO_END = 0x8000u, SO_CELL = 0x7FFFu;   // k_so_links' tile pointers: | SO_END when the cell is the END of the path
-constexpr int SO_RPT = LT / 4;                           // rows (cells) per thread of a tile pass
-constexpr int SO_JUMPS = 12;                             // 2^12 = 4096 cells: any loop-free path inside a tile
 enum { SO_LOOPS = 0, SO_SEED = 1, SO_WRITE = 2 };
 
 struct SoTile {   // a tile's LDS state
@@ -73,14 +66,6 @@ __device__ __forceinline__ int so_children(const SoTile &T, int lx, int ly, uint
   return n;
 }
 
-__device__ __forceinline__ uint32_t so_node(int gx, int gy, uint32_t tilesX) {
-  return ((uint32_t)(gy / LT) * tilesX + (uint32_t)(gx / LT)) * 256u + (uint32_t)border_slot(gx % LT, gy % LT);
-}
-__device__ __forceinline__ void so_border_cell(int slot, int &bx, int &by) {
-  bx = slot < LT ? slot : slot < 2 * LT ? slot - LT : slot < 3 * LT - 2 ? 0 : LT - 1;
-  by = slot < LT ? 0 : slot < 2 * LT ? LT - 1 : slot < 3 * LT - 2 ? slot - 2 * LT + 1 : slot - (3 * LT - 2) + 1;
-}
-
 // ---- element-wise ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NTHR) void k_so_channels(const double *__restrict__ accum, double nodata, double threshold, uint64_t n,
                                                       uint8_t *__restrict__ chan) {
@@ -109,10 +94,10 @@ __global__ __launch_bounds__(NTHR, 5) void k_so_links(const uint8_t *__restrict_
   stage_dirs_rows(order, w, h, x0, y0, (uint8_t)0, T.so);
   __syncthreads();
   const int lx = threadIdx.x & (LT - 1), ly0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  uint32_t p[SO_RPT], q[SO_RPT];
+  uint32_t p[FOREST_RPT];
   bool chan_here = false;
 #pragma unroll
-  for (int j = 0; j < SO_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int ly = ly0 + 4 * j;
     const uint32_t self = (uint32_t)(ly * LPS + lx);
     int tx, ty, kind = 0;
@@ -120,50 +105,36 @@ __global__ __launch_bounds__(NTHR, 5) void k_so_links(const uint8_t *__restrict_
       chan_here = true;
       kind = so_link(T, lx, ly, tx, ty);
     }
-    p[j] = kind == 1 ? (uint32_t)(ty * LPS + tx) : (self | SO_END);
+    p[j] = kind == 1 ? (uint32_t)(ty * LPS + tx) : (self | FOREST_END);
     T.lp[self] = (uint16_t)p[j];
     T.mk[self] = 0;
   }
   const bool any_chan = __syncthreads_or(chan_here);
-  // synchronous doubling: after round r a pointer without SO_END covers exactly 2^(r+1) cells
-#pragma unroll 1
-  for (int it = 0; it < SO_JUMPS; it++) {
-    bool moving = false;
-#pragma unroll
-    for (int j = 0; j < SO_RPT; j++) q[j] = (p[j] & SO_END) ? p[j] : T.lp[p[j]];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < SO_RPT; j++) {
-      p[j] = q[j];
-      moving |= !(q[j] & SO_END);
-      T.lp[(ly0 + 4 * j) * LPS + lx] = (uint16_t)q[j];
-    }
-    if (!__syncthreads_or(moving)) break;
-  }
+  forest_jump_sync(T.lp, p, lx, ly0);
   bool loop_here = false;
 #pragma unroll
-  for (int j = 0; j < SO_RPT; j++)
-    if (!(p[j] & SO_END)) { T.mk[p[j]] = 1; loop_here = true; }
+  for (int j = 0; j < FOREST_RPT; j++)
+    if (!(p[j] & FOREST_END)) { T.mk[p[j]] = 1; loop_here = true; }
   if (__syncthreads_or(loop_here)) {
 #pragma unroll
-    for (int j = 0; j < SO_RPT; j++) {
+    for (int j = 0; j < FOREST_RPT; j++) {
       const int ly = ly0 + 4 * j;
       if (T.mk[ly * LPS + lx]) order[(size_t)(y0 + ly) * w + (x0 + lx)] = (uint8_t)SO_ORDER_LOOP;   // (a channel cell: inside the raster)
     }
   }
   // the node a path that ENTERS the tile at a border cell leaves it to, one border cell per thread
   const int slot = (int)threadIdx.x;
-  uint32_t word = SO_NONE;
-  if (any_chan && slot < 4 * LT - 4) {
+  uint32_t word = FOREST_NONE;
+  if (any_chan && slot < BORDER_SLOTS) {
     int bx, by, tx, ty;
-    so_border_cell(slot, bx, by);
-    const uint32_t rp = T.lp[by * LPS + bx], root = rp & SO_CELL;
-    if (T.so[(by + 1) * SDW + SDO + bx] != 0 && (rp & SO_END)) {
+    border_cell(slot, bx, by);
+    const uint32_t rp = T.lp[by * LPS + bx], root = rp & FOREST_CELL;
+    if (T.so[(by + 1) * SDW + SDO + bx] != 0 && (rp & FOREST_END)) {
       const int ry = (int)root / LPS, rx = (int)root - ry * LPS;
-      if (so_link(T, rx, ry, tx, ty) == 2) word = so_node(x0 + tx, y0 + ty, tilesX);
+      if (so_link(T, rx, ry, tx, ty) == 2) word = tile_node(x0 + tx, y0 + ty, tilesX);
     }
   }
-  nxt0[(size_t)t * 256 + slot] = word;
+  nxt0[(size_t)t * TILE_SLOTS + slot] = word;
   if (threadIdx.x == 0) tmax[t] = any_chan ? 1 : 0;
 }
 
@@ -175,13 +146,13 @@ __global__ __launch_bounds__(NTHR) void k_so_round(const uint32_t *__restrict__ 
                                                    uint32_t ntiles, const uint8_t *__restrict__ tmax, uint32_t k,
                                                    const uint32_t *__restrict__ gate, uint32_t *flag_out) {
   if (*gate == 0) return;
-  const uint32_t nnodes = ntiles * 256u;
+  const uint32_t nnodes = ntiles * (uint32_t)TILE_SLOTS;
   bool flag = false;
   for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     if (tmax[t] < k) continue;
-    const uint32_t i = t * 256u + threadIdx.x;
+    const uint32_t i = t * (uint32_t)TILE_SLOTS + threadIdx.x;
     const uint32_t n = src[i];
-    uint32_t n2 = SO_NONE;
+    uint32_t n2 = FOREST_NONE;
     if (n < nnodes) {
       n2 = src[n];
       if (nmark) {
@@ -200,7 +171,7 @@ __global__ __launch_bounds__(NTHR) void k_so_loopmark(const uint32_t *__restrict
                                                       const uint8_t *__restrict__ tmax, const uint32_t *__restrict__ gate) {
   if (*gate == 0) return;
   const uint32_t i = blockIdx.x * NTHR + threadIdx.x;
-  if (i >= nnodes || tmax[i / 256u] == 0) return;   // (a tile without channel cells took no part in the rounds)
+  if (i >= nnodes || tmax[i / (uint32_t)TILE_SLOTS] == 0) return;   // (a tile without channel cells took no part in the rounds)
   const uint32_t n = last[i];
   if (n < nnodes) nmark[n] = 1;
 }
@@ -222,11 +193,11 @@ __global__ __launch_bounds__(NTHR, 5) void k_so_close(const uint8_t *__restrict_
   stage_dirs_rows(order, w, h, x0, y0, (uint8_t)0, T.so);
   __syncthreads();
   const int lx = threadIdx.x & (LT - 1), ly0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  uint32_t p[SO_RPT], q[SO_RPT];
+  uint32_t p[FOREST_RPT];
   uint32_t exitmask = 0;
   bool seeded = false;
 #pragma unroll
-  for (int j = 0; j < SO_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int ly = ly0 + 4 * j;
     const uint32_t self = (uint32_t)(ly * LPS + lx);
     const uint32_t o = T.so[(ly + 1) * SDW + SDO + lx];
@@ -237,7 +208,7 @@ __global__ __launch_bounds__(NTHR, 5) void k_so_close(const uint8_t *__restrict_
       if (MODE != SO_LOOPS) seed = o != SO_ORDER_LOOP && so_children(T, lx, ly, k) >= 2;
       if (MODE != SO_SEED) {
         const int slot = border_slot(lx, ly);
-        if (slot >= 0 && nmark[(size_t)t * 256 + slot]) seed = true;
+        if (slot >= 0 && nmark[(size_t)t * TILE_SLOTS + slot]) seed = true;
       }
     }
     p[j] = kind == 1 ? (uint32_t)(ty * LPS + tx) : self;
@@ -246,35 +217,24 @@ __global__ __launch_bounds__(NTHR, 5) void k_so_close(const uint8_t *__restrict_
     T.mk[self] = seed ? 1 : 0;
     seeded |= seed;
   }
-  if (!__syncthreads_or(seeded)) return;
+  // the marks pushed down the in-tile paths (a marked cell pushes to itself at an end: nothing new)
+  const auto mark = [&](uint32_t self, uint32_t to) {
+    if (!T.mk[self] || T.mk[to]) return false;
+    T.mk[to] = 1;
+    return true;
+  };
+  if (!forest_close(T.lp, p, seeded, lx, ly0, mark)) return;
   if (MODE == SO_SEED && threadIdx.x == 0) *lvl_out = 1;
-  // the marks pushed down the in-tile paths: round r pushes by 2^r; a round that marks nothing new has closed them
-#pragma unroll 1
-  for (int it = 0; it < SO_JUMPS; it++) {
-    bool fresh = false;
-#pragma unroll
-    for (int j = 0; j < SO_RPT; j++) q[j] = T.lp[p[j]];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < SO_RPT; j++) {
-      const uint32_t self = (uint32_t)((ly0 + 4 * j) * LPS + lx);
-      if (T.mk[self] && !T.mk[p[j]]) { T.mk[p[j]] = 1; fresh = true; }
-      T.lp[self] = (uint16_t)q[j];
-    }
-    if (!__syncthreads_or(fresh)) break;
-#pragma unroll
-    for (int j = 0; j < SO_RPT; j++) p[j] = q[j];
-  }
   bool done = false;
 #pragma unroll
-  for (int j = 0; j < SO_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int ly = ly0 + 4 * j;
     if (!T.mk[ly * LPS + lx]) continue;
     if (MODE == SO_SEED) {
       if (exitmask >> j & 1u) {
         int tx, ty;
         so_link(T, lx, ly, tx, ty);
-        nmark[so_node(x0 + tx, y0 + ty, tilesX)] = 1;
+        nmark[tile_node(x0 + tx, y0 + ty, tilesX)] = 1;
         done = true;
       }
     } else {
@@ -328,23 +288,17 @@ __global__ __launch_bounds__(NTHR) void k_so_kinds(const uint8_t *__restrict__ d
 }
 
 // ---- drivers ----------------------------------------------------------------------------------------------------------
-static void so_check_dims(int w, int h, const char *who) {
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, std::string(who) + ": width and height must be positive");
-  if ((uint64_t)w * (uint64_t)h > 0xFFFF0000ull) throw Error(RDGPU_ERR_ARG, std::string(who) + ": raster too large");
-}
-
 static thread_local int so_last_levels = 0, so_last_rounds = 0, so_last_launches = 0;
 
 static void stream_order_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, const uint8_t *d_chan, uint8_t *d_order,
                                 hipStream_t s, const char *who) {
   if (!d_dirs || !d_order) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-  so_check_dims(w, h, who);
+  check_forest_dims(w, h, who);
   const uint64_t n = (uint64_t)w * h;
-  const uint32_t tilesX = (w + LT - 1) / LT, ntiles = tilesX * ((h + LT - 1) / LT);
-  const uint32_t nnodes = ntiles * 256u;
-  int rounds = 1;
-  while ((1ull << (rounds - 1)) < nnodes) rounds++;   // ceil(log2(nodes)) + 1
-  int levels = 0;                                     // order k needs 2^(k-1) heads: levels 1 .. floor(log2(cells))
+  const ForestDims fd(w, h);
+  const uint32_t tilesX = fd.tilesX, ntiles = fd.ntiles, nnodes = (uint32_t)fd.nnodes;
+  const int rounds = forest_rounds(nnodes);
+  int levels = 0;   // order k needs 2^(k-1) heads: levels 1 .. floor(log2(cells))
   while ((2ull << levels) <= n) levels++;
   if (levels > 30) levels = 30;
   Workspace &ws = Workspace::get();
@@ -399,7 +353,7 @@ static void stream_order_device(const uint8_t *d_dirs, uint8_t nodata, int w, in
 static void channels_device(const double *d_accum, double nodata, double threshold, int w, int h, uint8_t *d_chan, hipStream_t s,
                             const char *who) {
   if (!d_accum || !d_chan) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-  so_check_dims(w, h, who);
+  check_forest_dims(w, h, who);
   if (!std::isfinite(threshold)) throw Error(RDGPU_ERR_ARG, std::string(who) + ": the threshold must be finite");
   const uint64_t n = (uint64_t)w * h;
   RD_LAUNCH("streams.channels", k_so_channels, dim3((uint32_t)((n + NTHR - 1) / NTHR)), dim3(NTHR), 0, s, d_accum, nodata, threshold,
@@ -409,7 +363,7 @@ static void channels_device(const double *d_accum, double nodata, double thresho
 static void stream_links_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, const uint8_t *d_chan, const uint8_t *d_order,
                                 uint8_t *d_kind, hipStream_t s, const char *who) {
   if (!d_dirs || !d_order || !d_kind) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-  so_check_dims(w, h, who);
+  check_forest_dims(w, h, who);
   const uint64_t n = (uint64_t)w * h;
   RD_LAUNCH("streams.kinds", k_so_kinds, dim3((uint32_t)((n + NTHR - 1) / NTHR)), dim3(NTHR), 0, s, d_dirs, nodata, w, h, d_chan,
             d_order, d_kind);
@@ -425,7 +379,7 @@ extern "C" int rdgpu_d8_stream_order(const uint8_t *dirs, uint8_t dir_nodata, in
   return guarded([&] {
     const char *who = "rdgpu_d8_stream_order";
     if (!dirs || !order) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-    so_check_dims(width, height, who);
+    check_forest_dims(width, height, who);
     const size_t n = (size_t)width * height;
     Workspace &ws = Workspace::get();
     uint8_t *dd = ws.buf<uint8_t>("host.dirs", n);
@@ -456,7 +410,7 @@ extern "C" int rdgpu_d8_channels_f64(const double *accum, double accum_nodata, d
   return guarded([&] {
     const char *who = "rdgpu_d8_channels_f64";
     if (!accum || !chan) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-    so_check_dims(width, height, who);
+    check_forest_dims(width, height, who);
     if (!std::isfinite(threshold)) throw Error(RDGPU_ERR_ARG, std::string(who) + ": the threshold must be finite");
     const size_t n = (size_t)width * height;
     Workspace &ws = Workspace::get();
@@ -480,7 +434,7 @@ extern "C" int rdgpu_d8_stream_links(const uint8_t *dirs, uint8_t dir_nodata, in
   return guarded([&] {
     const char *who = "rdgpu_d8_stream_links";
     if (!dirs || !order || !kind) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-    so_check_dims(width, height, who);
+    check_forest_dims(width, height, who);
     const size_t n = (size_t)width * height;
     Workspace &ws = Workspace::get();
     uint8_t *dd = ws.buf<uint8_t>("host.dirs", n);

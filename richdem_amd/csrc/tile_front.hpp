@@ -1,5 +1,6 @@
-// tile_front.hpp -- the common front end of the 64 x 64 tile passes over a D8 direction raster (accum.hip, upslope.hip):
-// the staged directions, the byte tables of the eight directions and the numbering of a tile's border cells.
+// tile_front.hpp -- the common front end of the 64 x 64 tile passes over a D8 direction raster (accum.hip and the engines
+// of d8_forest.hpp): the staged directions, the byte tables of the eight directions and the numbering of a tile's border
+// cells.
 #pragma once
 
 #include "common.hpp"
@@ -13,14 +14,29 @@ __device__ __forceinline__ int d8dx(int n) { return (n == 1 || n == 2 || n == 8)
 __device__ __forceinline__ int d8dy(int n) { return (n >= 2 && n <= 4) ? -1 : (n >= 6 && n <= 8) ? 1 : 0; }
 
 // the tile passes work on LT x LT tiles; a tile's 4 LT - 4 border cells are numbered top row, bottom row, left column,
-// right column (the link forest's nodes: 256 slots per tile)
+// right column (the link forest's nodes: 256 slots per tile).  This numbering is a data format: every engine on the forest
+// reads and writes node tables laid out by it.
 constexpr int LT = 64;
+constexpr int TILE_SLOTS = 256;           // a tile's nodes, the spare ones included
+constexpr int BORDER_SLOTS = 4 * LT - 4;  // the slots that stand for a border cell
+static_assert(BORDER_SLOTS <= TILE_SLOTS && TILE_SLOTS == NTHR, "one border cell per thread, one node word per thread");
 __device__ __forceinline__ int border_slot(int lx, int ly) {
   if (ly == 0) return lx;
   if (ly == LT - 1) return LT + lx;
   if (lx == 0) return 2 * LT + (ly - 1);
   if (lx == LT - 1) return 2 * LT + (LT - 2) + (ly - 1);
   return -1;
+}
+// the inverse: the cell of slot < BORDER_SLOTS.  (Through two locals: assigned straight to the references, accum.hip's
+// hand-tuned kernels come out of the compiler with another block layout than with the expressions written in place.)
+__device__ __forceinline__ void border_cell(int slot, int &bx, int &by) {
+  const int x = slot < LT ? slot : slot < 2 * LT ? slot - LT : slot < 3 * LT - 2 ? 0 : LT - 1;
+  const int y = slot < LT ? 0 : slot < 2 * LT ? LT - 1 : slot < 3 * LT - 2 ? slot - 2 * LT + 1 : slot - (3 * LT - 2) + 1;
+  bx = x; by = y;
+}
+// the node of the raster cell (gx, gy), a border cell of its tile
+__device__ __forceinline__ uint32_t tile_node(int gx, int gy, uint32_t tilesX) {
+  return ((uint32_t)(gy / LT) * tilesX + (uint32_t)(gx / LT)) * (uint32_t)TILE_SLOTS + (uint32_t)border_slot(gx % LT, gy % LT);
 }
 
 // The pointer tables of the tile passes are gathered at random by all 64 lanes; with rows of 64 two-byte entries every row

@@ -17,8 +17,7 @@
 // Seeds cost no raster of their own: the OUTPUT raster holds them between the passes.  Only tiles that contain a seed
 // are initialised and read back (a flag per tile), so a handful of pour points costs nothing per cell.  The position of a
 // seed in the caller's list is scattered with atomicMin: of two entries for one cell the first wins, deterministically.
-#include "common.hpp"
-#include "tile_front.hpp"
+#include "d8_forest.hpp"
 
 #include <algorithm>
 #include <string>
@@ -29,8 +28,6 @@ namespace rdgpu {
 constexpr uint32_t UP_NONE = 0xFFFFFFFFu;
 constexpr unsigned long long UP_RESOLVED = 1ull << 63;
 enum { UP_CATCH = 0, UP_OUTLET = 1, UP_CELLS = 2 };   // int32 labels | uint32 outlet indices | the reference's 2 / 1 / 255
-constexpr uint32_t UP_END = 0x8000u, UP_CELL = 0x7FFFu;   // a tile pointer: the cell's table index | UP_END when that cell is the END of the path
-constexpr int UP_RPT = LT / 4;                         // rows (cells) per thread of a tile pass
 
 template <int MODE> struct UpOut { using type = int32_t; };
 template <> struct UpOut<UP_OUTLET> { using type = uint32_t; };
@@ -38,7 +35,7 @@ template <> struct UpOut<UP_CELLS> { using type = uint8_t; };
 
 struct UpTile {   // a tile's LDS state
   uint8_t sd[SDH * SDW] __attribute__((aligned(4)));   // staged directions (tile_front.hpp)
-  uint16_t lp[LT * LPS];                               // per cell: a cell further down its in-tile path, | UP_END once that is known to be its end
+  uint16_t lp[LT * LPS];                               // per cell: a tile pointer (d8_forest.hpp), FOREST_END once that cell is known to be its end
   uint32_t sv[LT * LPS];                               // per cell: position of the seed on it in the seed list (UP_NONE: none); k_up_final: the ends' answers
 };
 
@@ -58,25 +55,19 @@ __device__ __forceinline__ int up_link(const uint8_t *sd, int lx, int ly, int x0
   return (tx >= 0 && tx < LT && ty >= 0 && ty < LT) ? 1 : 2;
 }
 
-// the node of the raster cell (gx, gy), a border cell of its tile
-__device__ __forceinline__ uint32_t up_node(int gx, int gy, uint32_t tilesX) {
-  return ((uint32_t)(gy / LT) * tilesX + (uint32_t)(gx / LT)) * 256u + (uint32_t)border_slot(gx % LT, gy % LT);
-}
-
 // Stages the tile, loads its seeds and pointer-jumps every cell to the in-tile end of its path: p[j] is the end of the
-// thread's cell (lx, ly0 + 4 j) where it carries UP_END (an end itself has self | UP_END); a cell whose pointer does not
-// runs into a direction loop inside the tile.  The flag, not "points to itself", marks an end: three hops round a loop
-// of three cells come back to the start.  Returns the mask of the thread's cells that are seeds.
+// thread's cell (lx, ly0 + 4 j) where it carries FOREST_END (an end itself has self | FOREST_END); a cell whose pointer
+// does not runs into a direction loop inside the tile.  Returns the mask of the thread's cells that are seeds.
 template <int MODE>
 __device__ __forceinline__ uint32_t up_tile_ends(UpTile &T, const uint8_t *__restrict__ dirs, uint8_t nodata, int w, int h, int x0,
                                                  int y0, const typename UpOut<MODE>::type *seeds, bool has_seeds,
-                                                 uint32_t (&p)[UP_RPT]) {
+                                                 uint32_t (&p)[FOREST_RPT]) {
   stage_dirs_rows(dirs, w, h, x0, y0, nodata, T.sd);
   const int lx = threadIdx.x & (LT - 1), ly0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   uint32_t seedmask = 0;
-  uint32_t sidx[UP_RPT];
+  uint32_t sidx[FOREST_RPT];
 #pragma unroll
-  for (int j = 0; j < UP_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int ly = ly0 + 4 * j, gx = x0 + lx, gy = y0 + ly;
     uint32_t s = UP_NONE;
     if (MODE != UP_OUTLET && has_seeds && gx < w && gy < h) {
@@ -89,12 +80,12 @@ __device__ __forceinline__ uint32_t up_tile_ends(UpTile &T, const uint8_t *__res
   }
   __syncthreads();
 #pragma unroll
-  for (int j = 0; j < UP_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int ly = ly0 + 4 * j;
     const uint32_t self = (uint32_t)(ly * LPS + lx);
     int tx, ty;
     const int k = up_link<MODE>(T.sd, lx, ly, x0, y0, w, h, nodata, tx, ty);
-    p[j] = (k == 1 && sidx[j] == UP_NONE) ? (uint32_t)(ty * LPS + tx) : (self | UP_END);   // a seed absorbs, like an exit or a sink
+    p[j] = (k == 1 && sidx[j] == UP_NONE) ? (uint32_t)(ty * LPS + tx) : (self | FOREST_END);   // a seed absorbs, like an exit or a sink
     T.lp[self] = (uint16_t)p[j];
     T.sv[self] = sidx[j];
   }
@@ -105,10 +96,10 @@ __device__ __forceinline__ uint32_t up_tile_ends(UpTile &T, const uint8_t *__res
   for (int it = 0; it < 12; it++) {
     bool moving = false;
 #pragma unroll
-    for (int j = 0; j < UP_RPT; j++) {
-      const uint32_t q = (p[j] & UP_END) ? p[j] : T.lp[p[j]];
-      const uint32_t r = (q & UP_END) ? q : T.lp[q];
-      moving |= !(r & UP_END);
+    for (int j = 0; j < FOREST_RPT; j++) {
+      const uint32_t q = (p[j] & FOREST_END) ? p[j] : T.lp[p[j]];
+      const uint32_t r = (q & FOREST_END) ? q : T.lp[q];
+      moving |= !(r & FOREST_END);
       p[j] = r;
       T.lp[(ly0 + 4 * j) * LPS + lx] = (uint16_t)r;
     }
@@ -134,25 +125,25 @@ __global__ __launch_bounds__(NTHR, 5) void k_up_tile(const uint8_t *__restrict__
   if (t >= ntiles) return;
   const int x0 = (int)(t % tilesX) * LT, y0 = (int)(t / tilesX) * LT;
   const bool has_seeds = MODE != UP_OUTLET && tileflag[t] != 0;
-  uint32_t p[UP_RPT];
+  uint32_t p[FOREST_RPT];
   up_tile_ends<MODE>(T, dirs, nodata, w, h, x0, y0, seeds, has_seeds, p);
   // what a path that ENTERS the tile at a border cell comes to, one border cell per thread
   const int slot = (int)threadIdx.x;
   unsigned long long word = UP_RESOLVED | none;   // (the four spare slots; a path into an in-tile loop)
-  if (slot < 4 * LT - 4) {
-    const int bx = slot < LT ? slot : slot < 2 * LT ? slot - LT : slot < 3 * LT - 2 ? 0 : LT - 1;
-    const int by = slot < LT ? 0 : slot < 2 * LT ? LT - 1 : slot < 3 * LT - 2 ? slot - 2 * LT + 1 : slot - (3 * LT - 2) + 1;
-    const uint32_t rp = T.lp[by * LPS + bx], root = rp & UP_CELL;
-    if (rp & UP_END) {
+  if (slot < BORDER_SLOTS) {
+    int bx, by;
+    border_cell(slot, bx, by);
+    const uint32_t rp = T.lp[by * LPS + bx], root = rp & FOREST_CELL;
+    if (rp & FOREST_END) {
       const int ry = (int)root / LPS, rx = (int)root - ry * LPS;
       const uint32_t s = T.sv[root];
       int tx, ty;
       if (s != UP_NONE) word = UP_RESOLVED | up_seed_value<MODE>(s, seed_labels);
-      else if (up_link<MODE>(T.sd, rx, ry, x0, y0, w, h, nodata, tx, ty) == 2) word = up_node(x0 + tx, y0 + ty, tilesX);
+      else if (up_link<MODE>(T.sd, rx, ry, x0, y0, w, h, nodata, tx, ty) == 2) word = tile_node(x0 + tx, y0 + ty, tilesX);
       else if (MODE == UP_OUTLET && T.sd[(ry + 1) * SDW + SDO + rx] != nodata) word = UP_RESOLVED | ((uint32_t)(y0 + ry) * (uint32_t)w + (uint32_t)(x0 + rx));
     }
   }
-  node[(size_t)t * 256 + slot] = word;
+  node[(size_t)t * TILE_SLOTS + slot] = word;
 }
 
 // flags[r]: round r left a node unresolved
@@ -183,28 +174,28 @@ __global__ __launch_bounds__(NTHR, 5) void k_up_final(const uint8_t *__restrict_
   if (t >= ntiles) return;
   const int x0 = (int)(t % tilesX) * LT, y0 = (int)(t / tilesX) * LT;
   const bool has_seeds = MODE != UP_OUTLET && tileflag[t] != 0;
-  uint32_t p[UP_RPT];
+  uint32_t p[FOREST_RPT];
   const uint32_t seedmask = up_tile_ends<MODE>(T, dirs, nodata, w, h, x0, y0, out, has_seeds, p);
   const int lx = threadIdx.x & (LT - 1), ly0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   // the ends' answers: every end is some thread's own cell (all node reads of the block in flight together)
   uint32_t endmask = 0;
-  unsigned long long nv[UP_RPT];
+  unsigned long long nv[FOREST_RPT];
 #pragma unroll
-  for (int j = 0; j < UP_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int ly = ly0 + 4 * j;
     nv[j] = 0;
-    if (p[j] != ((uint32_t)(ly * LPS + lx) | UP_END) || (seedmask >> j & 1u)) continue;
+    if (p[j] != ((uint32_t)(ly * LPS + lx) | FOREST_END) || (seedmask >> j & 1u)) continue;
     int tx, ty;
     if (up_link<MODE>(T.sd, lx, ly, x0, y0, w, h, nodata, tx, ty) == 2) {
-      nv[j] = node[up_node(x0 + tx, y0 + ty, tilesX)];
+      nv[j] = node[tile_node(x0 + tx, y0 + ty, tilesX)];
       endmask |= 1u << j;
     }
   }
 #pragma unroll
-  for (int j = 0; j < UP_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int ly = ly0 + 4 * j;
     const uint32_t self = (uint32_t)(ly * LPS + lx);
-    if (p[j] != (self | UP_END)) continue;
+    if (p[j] != (self | FOREST_END)) continue;
     uint32_t a = none;
     if (seedmask >> j & 1u) a = up_seed_value<MODE>(T.sv[self], seed_labels);
     else if (endmask >> j & 1u) a = (nv[j] & UP_RESOLVED) ? (uint32_t)nv[j] : none;
@@ -213,10 +204,10 @@ __global__ __launch_bounds__(NTHR, 5) void k_up_final(const uint8_t *__restrict_
   }
   __syncthreads();
 #pragma unroll
-  for (int j = 0; j < UP_RPT; j++) {
+  for (int j = 0; j < FOREST_RPT; j++) {
     const int ly = ly0 + 4 * j, gx = x0 + lx, gy = y0 + ly;
     if (gx >= w || gy >= h) continue;
-    uint32_t a = (p[j] & UP_END) ? T.sv[p[j] & UP_CELL] : none;   // else: into a direction loop inside the tile
+    uint32_t a = (p[j] & FOREST_END) ? T.sv[p[j] & FOREST_CELL] : none;   // else: into a direction loop inside the tile
     if (MODE == UP_CELLS && (seedmask >> j & 1u)) a = 2u;
     out[(size_t)gy * w + gx] = (O)a;
   }
@@ -251,11 +242,6 @@ __global__ __launch_bounds__(NTHR) void k_up_seed_scatter(const uint32_t *__rest
 }
 
 // ---- drivers ----------------------------------------------------------------------------------------------------------
-static void up_check_dims(int w, int h, const char *who) {
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, std::string(who) + ": width and height must be positive");
-  if ((uint64_t)w * (uint64_t)h > 0xFFFF0000ull) throw Error(RDGPU_ERR_ARG, std::string(who) + ": raster too large");
-}
-
 // seeds_checked: the caller has verified every seed cell (host entries); else they are verified here, which costs the
 // one host synchronisation of the call
 template <int MODE>
@@ -264,17 +250,17 @@ static void upslope_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, 
                            const char *who) {
   using O = typename UpOut<MODE>::type;
   if (!d_dirs || !d_out) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-  up_check_dims(w, h, who);
+  check_forest_dims(w, h, who);
   if (MODE != UP_OUTLET && n_seeds && (!d_cells || (MODE == UP_CATCH && !d_labels)))
     throw Error(RDGPU_ERR_ARG, std::string(who) + ": null seed array");
   if (n_seeds == UP_NONE) throw Error(RDGPU_ERR_ARG, std::string(who) + ": too many seeds");
-  const uint32_t tilesX = (w + LT - 1) / LT, ntiles = tilesX * ((h + LT - 1) / LT);
-  const uint64_t nnodes = (uint64_t)ntiles * 256;
+  const ForestDims fd(w, h);
+  const uint32_t tilesX = fd.tilesX, ntiles = fd.ntiles;
+  const uint64_t nnodes = fd.nnodes;
   Workspace &ws = Workspace::get();
   unsigned long long *node = ws.buf<unsigned long long>("upslope.node", nnodes);
   uint8_t *tileflag = ws.buf<uint8_t>("upslope.tileflag", ntiles);
-  int rounds = 1;
-  while ((1ull << (rounds - 1)) < nnodes) rounds++;   // ceil(log2(nodes)) + 1
+  const int rounds = forest_rounds(nnodes);
   uint32_t *flags = ws.buf<uint32_t>("upslope.flags", (size_t)rounds + 1);   // [rounds]: a seed outside the raster
   RD_HIP(hipMemsetAsync(flags, 0, ((size_t)rounds + 1) * sizeof(uint32_t), s));
   if (MODE != UP_OUTLET) {
@@ -307,7 +293,7 @@ static void upslope_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, 
 // before y moves by one.  Where the reference would mark a cell outside the raster (undefined behaviour there) this
 // throws.
 static std::vector<uint32_t> upslope_line(int w, int h, int x0, int y0, int x1, int y1, const char *who) {
-  up_check_dims(w, h, who);
+  check_forest_dims(w, h, who);
   if (x0 > x1) { std::swap(x0, x1); std::swap(y0, y1); }
   const Error outside(RDGPU_ERR_ARG, std::string(who) + ": the line leaves the raster");
   if (x0 < 0 || x1 >= w || y0 < 0 || y0 >= h) throw outside;   // (x0, y0) and a cell of column x1 are always marked
@@ -348,7 +334,7 @@ static void upslope_host(const uint8_t *dirs, uint8_t nodata, int w, int h, cons
                          const char *who) {
   using O = typename UpOut<MODE>::type;
   if (!dirs || !out) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-  up_check_dims(w, h, who);
+  check_forest_dims(w, h, who);
   const size_t n = (size_t)w * h;
   Workspace &ws = Workspace::get();
   std::vector<uint32_t> line;

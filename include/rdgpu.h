@@ -997,6 +997,69 @@ int rdgpu_d8_longest_flow_path_dev(const uint8_t *d_dirs, uint8_t dir_nodata, in
                                    double *d_length /* nullable */, double length_nodata, uint8_t *d_on_basin_path /* nullable */,
                                    void *hip_stream);
 
+/* ---- weighted accumulation on the D8 direction forest, and the total upstream length -----------
+ * The reference's FlowAccumulation (methods/flow_accumulation_generic.hpp:33-100) on the proportions of GIVEN D8
+ * directions, without the [h, w, 9] proportions array.  Directions are uint8 D8 codes (0 NO_FLOW, 1..8 index the
+ * neighbour in the reference's dx / dy tables, dir_nodata); weights is a raster of W of the same size.
+ *   A cell PARTICIPATES iff dirs != dir_nodata.  A participating cell CONTRIBUTES iff its weight is not weight_nodata
+ *   (compared with == in W: -0.0 equals a NoData of 0.0) and, for f32 and f64, is not a NaN (a NaN never contributes,
+ *   whatever weight_nodata is).  A cell that does not contribute still passes on what it receives; infinities are added
+ *   as they are.
+ *   The LINK of a participating cell c exists iff its code is 1..8, its target lies in the raster and the target
+ *   participates; otherwise c's tree ends at c.
+ *   A cell is ON A LOOP iff following links from it comes back to it.
+ *   T(v), for a participating cell v, holds v and every cell u whose chain of links reaches v with no cell of that chain
+ *   before v on a loop.  For a cell off every loop this is its whole drainage area; for a loop cell it is the trees that
+ *   enter the loop at that cell: the links of a loop carry nothing.  Nothing is special-cased for loops and no loop
+ *   sentinel is written.
+ *   sum[v] is the sum of the weights of the contributing cells of T(v); sum_nodata where v does not participate.
+ * This is what the reference leaves in its accumulation array (loop cells keep their own weight plus what arrived), with
+ * two deliberate differences: edge cells take part like any other cell, and the NoData value is the caller's.
+ * W: i8 u8 i16 u16 i32 u32 with S = int64_t: exact and identical from run to run; the sum fits int64_t on every raster
+ * below 2^31 cells.  W: f32 f64 with S = double: every weight is converted to double exactly, then added in double in an
+ * unspecified order -- exact, and therefore reproducible, whenever every partial sum is representable (integer-valued
+ * weights, as for rdgpu_fa_d8); otherwise within the recursive-summation bound of the true sum,
+ * |sum[v] - true| <= g * (sum of |w| over T(v)), g = (k - 1) u / (1 - (k - 1) u), u = 2^-53, k the contributing cells
+ * of T(v).  64-bit integer weights are NOT declared.
+ * Every cell of sum is stored exactly once (sum is also the accumulator: a cell that receives inflow is afterwards
+ * changed by atomic adds alone, so nothing but the final value may be read from it); the inputs are not modified.  A null pointer, a non-positive size or more than 0xFFFF0000 cells returns RDGPU_ERR_ARG before any device
+ * work; nothing is written then.  The _dev forms take device pointers and are ordered on hip_stream without
+ * synchronising it.  Scratch (4 bytes per cell) comes from the workspace pool. */
+#define RDGPU_DECL_WEIGHTED(SUF, W, S)                                                                                    \
+  int rdgpu_d8_flow_accum_weighted_##SUF(const uint8_t *dirs, uint8_t dir_nodata, const W *weights, W weight_nodata,     \
+                                         int width, int height, S *sum, S sum_nodata);                                   \
+  int rdgpu_d8_flow_accum_weighted_dev_##SUF(const uint8_t *d_dirs, uint8_t dir_nodata, const W *d_weights,              \
+                                             W weight_nodata, int width, int height, S *d_sum, S sum_nodata,             \
+                                             void *hip_stream);
+RDGPU_DECL_WEIGHTED(i8, int8_t, int64_t)
+RDGPU_DECL_WEIGHTED(u8, uint8_t, int64_t)
+RDGPU_DECL_WEIGHTED(i16, int16_t, int64_t)
+RDGPU_DECL_WEIGHTED(u16, uint16_t, int64_t)
+RDGPU_DECL_WEIGHTED(i32, int32_t, int64_t)
+RDGPU_DECL_WEIGHTED(u32, uint32_t, int64_t)
+RDGPU_DECL_WEIGHTED(f32, float, double)
+RDGPU_DECL_WEIGHTED(f64, double, double)
+#undef RDGPU_DECL_WEIGHTED
+/* The total upstream length (TauDEM's tlen): the summed length of every link of the tree above a cell.  Participation,
+ * links, loops and T(v) are those of the block above.  Per-cell outputs, each a nullable pointer (a call must request at
+ * least one):
+ *   steps    uint32 [3][height][width] plane k: the number of cells u of T(v), v excluded, whose link is of kind k --
+ *                                      plane 0 along x (codes 1, 5), plane 1 along y (codes 3, 7), plane 2 diagonal:
+ *                                      rdgpu_d8_flow_path's three kinds.  All 0xFFFFFFFF where v does not participate.
+ *   length   float64                   (double)nx * cell_x + (double)ny * cell_y + (double)nd * diag of those three
+ *                                      counts, evaluated as rdgpu_d8_flow_path's dist is (a rounding after every
+ *                                      product and every sum, no fused multiply-add, diag computed once on the
+ *                                      host); length_nodata where v does not participate.
+ * Exact and identical from run to run.  cell_x and cell_y: their sign is ignored; zero or not finite is RDGPU_ERR_ARG.
+ * A null dirs, no output requested, a non-positive size or more than 0xFFFF0000 cells returns RDGPU_ERR_ARG before any
+ * device work; nothing is written then.  The _dev form takes device pointers and is ordered on hip_stream without
+ * synchronising it.  Scratch (20 bytes per cell) comes from the workspace pool. */
+int rdgpu_d8_total_upstream_length(const uint8_t *dirs, uint8_t dir_nodata, int width, int height, double cell_x, double cell_y,
+                                   uint32_t *steps /* nullable */, double *length /* nullable */, double length_nodata);
+int rdgpu_d8_total_upstream_length_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int width, int height, double cell_x,
+                                       double cell_y, uint32_t *d_steps /* nullable */, double *d_length /* nullable */,
+                                       double length_nodata, void *hip_stream);
+
 /* ---- depression inventory: labels and one record per depression of the fill --------------------
  * No reference counterpart (the flat inventory of the lakes FillDepressions produces; the depression hierarchy is not
  * built).  Let W = FillDepressions<topology>(dem) exactly as rdgpu_fill_<T> computes it; NoData is an elevation like any

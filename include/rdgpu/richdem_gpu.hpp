@@ -890,6 +890,82 @@ void d8_longest_flow_path(const F &flowdirs, G &length) {
   detail::longest_run(flowdirs, length, cx, cy, nullptr, nullptr);
 }
 
+// ---- weighted accumulation and total upstream length on the D8 forest (the definition is in rdgpu.h) ----------------
+namespace detail {
+#define RDGPU_SHIM_WEIGHTED(SUF, T, S)                                                                          \
+  inline int c_weighted(const uint8_t *d, uint8_t dnd, const T *v, T vnd, int w, int h, S *sum, S snd) {        \
+    return rdgpu_d8_flow_accum_weighted_##SUF(d, dnd, v, vnd, w, h, sum, snd);                                  \
+  }
+RDGPU_SHIM_WEIGHTED(u8, uint8_t, int64_t) RDGPU_SHIM_WEIGHTED(i8, int8_t, int64_t) RDGPU_SHIM_WEIGHTED(u16, uint16_t, int64_t)
+RDGPU_SHIM_WEIGHTED(i16, int16_t, int64_t) RDGPU_SHIM_WEIGHTED(u32, uint32_t, int64_t) RDGPU_SHIM_WEIGHTED(i32, int32_t, int64_t)
+RDGPU_SHIM_WEIGHTED(f32, float, double) RDGPU_SHIM_WEIGHTED(f64, double, double)
+#undef RDGPU_SHIM_WEIGHTED
+template <class T, class S>
+int c_weighted(const uint8_t *, uint8_t, const T *, T, int, int, S *, S) { unsupported("d8_flow_accum_weighted"); }
+}  // namespace detail
+
+// sum <- the sum of `weights` over everything that drains through each cell along the GIVEN directions, the cell included
+// (richdem::FlowAccumulation on the proportions of these directions, without the proportions array).  Cells whose weight
+// is the weights' NoData (or a NaN) add nothing but pass on what they receive.  sum is int64_t for int8 .. uint32 weights
+// and double for float and double weights (64-bit integer weights throw); its NoData, kept if it has been set and written
+// where the direction is NoData, defaults to -1.  It takes the directions' size, geotransform and projection.
+template <class F, class V, class G>
+void d8_flow_accum_weighted(const F &flowdirs, const V &weights, G &sum) {
+  using T = detail::elem_t<const V>;
+  using S = detail::elem_t<G>;
+  static_assert(std::is_same<detail::elem_t<const F>, uint8_t>::value || std::is_same<detail::elem_t<F>, uint8_t>::value,
+                "d8_flow_accum_weighted: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<S, typename std::conditional<std::is_floating_point<T>::value, double, int64_t>::type>::value,
+                "d8_flow_accum_weighted: the sum raster is int64_t for integer weights, double for float and double weights");
+  if (weights.width() != flowdirs.width() || weights.height() != flowdirs.height())
+    throw std::runtime_error("d8_flow_accum_weighted: the weights must have the directions' size");
+  const S sum_nodata = sum.noData();
+  sum.resize(flowdirs);
+  sum.setNoData(sum_nodata);
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  detail::check(detail::c_weighted(flowdirs.data(), flowdirs.noData(), (const T *)weights.data(), (T)weights.noData(),
+                                   flowdirs.width(), flowdirs.height(), (S *)sum.data(), sum_nodata), "d8_flow_accum_weighted");
+}
+
+// length <- the total length of the links of the tree above each cell (TauDEM's tlen), NoData -1; *along_x, *along_y,
+// *diagonal (uint32_t; the second form leaves them out) <- how many of those links run along x, along y and diagonally, NoData
+// 0xFFFFFFFF.  The cell lengths are the directions' |geotransform[1]|, |geotransform[5]|; the outputs take the directions'
+// size, geotransform and projection.
+namespace detail {
+template <class F, class G>
+void tlen_run(const F &flowdirs, G &length, uint32_t *steps) {
+  static_assert(std::is_same<elem_t<const F>, uint8_t>::value || std::is_same<elem_t<F>, uint8_t>::value,
+                "d8_total_upstream_length: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<elem_t<G>, double>::value, "d8_total_upstream_length: the length raster must be double");
+  double cx, cy;
+  cell_lengths(flowdirs, "d8_total_upstream_length", cx, cy);
+  length.resize(flowdirs);
+  length.setNoData(-1.0);
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  check(rdgpu_d8_total_upstream_length(flowdirs.data(), flowdirs.noData(), flowdirs.width(), flowdirs.height(), cx, cy, steps,
+                                       length.data(), -1.0), "d8_total_upstream_length");
+}
+}  // namespace detail
+template <class F, class G, class C>
+void d8_total_upstream_length(const F &flowdirs, G &length, C *along_x, C *along_y, C *diagonal) {
+  static_assert(std::is_same<detail::elem_t<C>, uint32_t>::value, "d8_total_upstream_length: the step rasters must be uint32_t");
+  if (!along_x || !along_y || !diagonal)
+    throw std::runtime_error("d8_total_upstream_length: the three step rasters are given together or not at all");
+  const size_t n = (size_t)flowdirs.width() * (size_t)flowdirs.height();
+  std::vector<uint32_t> steps(3 * n);
+  detail::tlen_run(flowdirs, length, steps.data());
+  C *planes[3] = {along_x, along_y, diagonal};
+  for (int k = 0; k < 3; k++) {
+    planes[k]->resize(flowdirs);
+    planes[k]->setNoData(0xFFFFFFFFu);
+    for (size_t i = 0; i < n; i++) planes[k]->data()[i] = steps[k * n + i];
+  }
+}
+template <class F, class G>
+void d8_total_upstream_length(const F &flowdirs, G &length) {
+  detail::tlen_run(flowdirs, length, nullptr);
+}
+
 // ---- upslope extremes on the D8 forest (no reference counterpart; the definition is in rdgpu.h) ----------------------
 namespace detail {
 #define RDGPU_SHIM_EXTREME(SUF, T)                                                                                      \

@@ -1468,3 +1468,97 @@ def d8_longest_flow_path_dev(dirs, dir_nodata: int = 255, cell=(1.0, 1.0), lengt
                                                _dev_plane(length, (h, w), torch.float64, who), ctypes.c_double(length_nodata),
                                                _dev_plane(on_basin_path, (h, w), torch.uint8, who), _stream_ptr()),
           "rdgpu_d8_longest_flow_path_dev")
+
+
+# ---- weighted accumulation and total upstream length (csrc/accum_weighted.hip) ------------------
+_WEIGHTED_SUFFIX = {k: v for k, v in _SUFFIX.items() if v not in ("i64", "u64")}
+_TLEN_WANT = ("steps", "length")
+
+
+def _sum_scalar(s: str, sum_nodata):
+    return ctypes.c_double(float(sum_nodata)) if s in ("f32", "f64") else _scalar("i64", sum_nodata)
+
+
+def d8_flow_accum_weighted(dirs: np.ndarray, weights: np.ndarray, weight_nodata, dir_nodata: int = 255, sum_nodata=-1) -> np.ndarray:
+    """The sum of `weights` over everything that drains through each cell of a D8 direction raster, the cell included
+    (include/rdgpu.h states the definition; direction loops carry nothing along their own links): int64 for int8 .. uint32
+    weights (exact), float64 for float32 / float64 weights.  Cells whose weight equals weight_nodata, and NaNs, add
+    nothing but pass on what they receive; sum_nodata where dirs == dir_nodata."""
+    who = "d8_flow_accum_weighted"
+    dirs = _dirs2d(dirs, who)
+    if not isinstance(weights, np.ndarray) or weights.shape != dirs.shape or weights.dtype not in _WEIGHTED_SUFFIX:
+        raise RdgpuError(f"{who}: the weights are an array of the directions' shape, element types int8 .. uint32, float32, float64")
+    s = _WEIGHTED_SUFFIX[weights.dtype]
+    wts = np.ascontiguousarray(weights)
+    h, w = dirs.shape
+    out = np.empty((h, w), np.float64 if s in ("f32", "f64") else np.int64)
+    check(getattr(lib(), f"rdgpu_d8_flow_accum_weighted_{s}")(_ptr(dirs), ctypes.c_uint8(dir_nodata), _ptr(wts), _scalar(s, weight_nodata),
+                                                              w, h, _ptr(out), _sum_scalar(s, sum_nodata)),
+          "rdgpu_d8_flow_accum_weighted")
+    return out
+
+
+def d8_flow_accum_weighted_dev(dirs, weights, weight_nodata, out, dir_nodata: int = 255, sum_nodata=-1) -> None:
+    """out (CUDA tensor: int64 for integer weights, float64 for float32 / float64 weights) <- d8_flow_accum_weighted of dirs
+    (uint8 CUDA tensor) and weights (CUDA tensor of int8 .. uint32 as far as torch has them, float32 or float64), on torch's
+    current stream and without synchronising it."""
+    import torch
+
+    who = "d8_flow_accum_weighted_dev"
+    h, w = _dev2d(dirs, who, torch.uint8)
+    m = {torch.int8: "i8", torch.uint8: "u8", torch.int16: "i16", torch.int32: "i32", torch.float32: "f32", torch.float64: "f64"}
+    for name, s in (("uint16", "u16"), ("uint32", "u32")):
+        if hasattr(torch, name):
+            m[getattr(torch, name)] = s
+    if weights.dtype not in m:
+        raise RdgpuError(f"{who}: unsupported weight dtype {weights.dtype}")
+    if _dev2d(weights, who) != (h, w):
+        raise RdgpuError(f"{who}: shape mismatch")
+    s = m[weights.dtype]
+    if out is None:
+        raise RdgpuError(f"{who}: no output given")
+    check(getattr(lib(), f"rdgpu_d8_flow_accum_weighted_dev_{s}")(
+        ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata), ctypes.c_void_p(weights.data_ptr()), _scalar(s, weight_nodata),
+        w, h, _dev_plane(out, (h, w), torch.float64 if s in ("f32", "f64") else torch.int64, who), _sum_scalar(s, sum_nodata),
+        _stream_ptr()), "rdgpu_d8_flow_accum_weighted_dev")
+
+
+def d8_total_upstream_length(dirs: np.ndarray, cell_x: float = 1.0, cell_y: float = 1.0, dir_nodata: int = 255,
+                             want=("steps", "length"), length_nodata: float = -1.0) -> dict:
+    """The total length of the links of the tree above every cell (TauDEM's tlen; include/rdgpu.h states the definition): a
+    dict with the planes named in `want` -- "steps" (uint32 [3, h, w]: the links along x, along y and diagonal above the
+    cell, 0xFFFFFFFF where dirs == dir_nodata) and "length" (float64, length_nodata there)."""
+    who = "d8_total_upstream_length"
+    dirs = _dirs2d(dirs, who)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in _TLEN_WANT for k in want):
+        raise RdgpuError(f"{who}: want names at least one of {_TLEN_WANT}")
+    cx, cy = _cell2((cell_x, cell_y), who)
+    h, w = dirs.shape
+    out = {}
+    if "steps" in want:
+        out["steps"] = np.empty((3, h, w), np.uint32)
+    if "length" in want:
+        out["length"] = np.empty((h, w), np.float64)
+    check(lib().rdgpu_d8_total_upstream_length(_ptr(dirs), ctypes.c_uint8(dir_nodata), w, h, cx, cy, _ptr(out.get("steps")),
+                                               _ptr(out.get("length")), ctypes.c_double(length_nodata)),
+          "rdgpu_d8_total_upstream_length")
+    return out
+
+
+def d8_total_upstream_length_dev(dirs, cell_x: float = 1.0, cell_y: float = 1.0, dir_nodata: int = 255, steps=None, length=None,
+                                 length_nodata: float = -1.0) -> None:
+    """The planes given (CUDA tensors: steps int32 [3, h, w] holding the uint32 counts bit for bit, -1 where
+    dirs == dir_nodata; length float64 [h, w]) <- d8_total_upstream_length of dirs (uint8 CUDA tensor), on torch's current
+    stream and without synchronising it.  At least one plane must be given."""
+    import torch
+
+    who = "d8_total_upstream_length_dev"
+    h, w = _dev2d(dirs, who, torch.uint8)
+    if steps is None and length is None:
+        raise RdgpuError(f"{who}: no output requested")
+    cx, cy = _cell2((cell_x, cell_y), who)
+    check(lib().rdgpu_d8_total_upstream_length_dev(ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata), w, h, cx, cy,
+                                                   _dev_plane(steps, (3, h, w), torch.int32, who),
+                                                   _dev_plane(length, (h, w), torch.float64, who), ctypes.c_double(length_nodata),
+                                                   _stream_ptr()), "rdgpu_d8_total_upstream_length_dev")

@@ -10,6 +10,7 @@
 #include <map>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -278,6 +279,16 @@ struct Key32<float> {
     if (b == 0x80000000u) b = 0;
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
   }
+  // The same key without a compare: v + 0.0f turns -0.0f into +0.0f and leaves every other non-NaN value as it is
+  // (round to nearest, denormals kept, no contraction: the build's flags), and the sign fold is one xor with the sign
+  // spread over the word.  Equal to to() for every non-NaN bit pattern (tests/cpp/key32_exhaustive.cpp).  On gfx950 that
+  // is add, ashr, or, xor where to() is two v_cmp / v_cndmask pairs with a hazard wait each.  Device code on the fill's
+  // hot path asks for it (key32_fast below), and minds where the add lands: the compiler moves it up to the value's
+  // load.  Host code keeps to(): a process whose FTZ / DAZ bits another library has set would flush denormals in the add.
+  __host__ __device__ static inline uint32_t to_fold(float v) {
+    const uint32_t b = __builtin_bit_cast(uint32_t, v + 0.0f);
+    return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
+  }
   __host__ __device__ static inline float from(uint32_t k) {
     uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
     return __builtin_bit_cast(float, b);
@@ -313,6 +324,12 @@ struct Key32<uint8_t> {
   __host__ __device__ static inline uint32_t to(uint8_t v) { return v; }
   __host__ __device__ static inline uint8_t from(uint32_t k) { return (uint8_t)k; }
 };
+// Key32<T>::to(v) in its cheapest device form: floats without compares, every other type as it is
+template <class T>
+__device__ __forceinline__ uint32_t key32_fast(T v) {
+  if constexpr (std::is_same<T, float>::value) return Key32<float>::to_fold(v);
+  else return Key32<T>::to(v);
+}
 
 // XCD-aware block -> tile mapping: the dispatcher places block b on XCD b % 8 (performance
 // observation only, MI355X_MICROARCH.md); giving each XCD a contiguous band of tiles keeps halo

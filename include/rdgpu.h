@@ -1107,6 +1107,71 @@ RDGPU_DECL_DEPR(i64, int64_t)   /* RDGPU_ERR_UNSUPPORTED */
 RDGPU_DECL_DEPR(u64, uint64_t)  /* RDGPU_ERR_UNSUPPORTED */
 #undef RDGPU_DECL_DEPR
 
+/* ---- flow distance and drop (HAND) DOWN to the stop cells over D-infinity / MFD proportions ----
+ * No reference counterpart (TauDEM's DinfDistDown is the product meant).  Proportions are the reference's nine floats
+ * per cell, [height][width][9]: slot 0 is -2 for NoData, slots 1..8 the shares to the neighbours 1 left, 2 up-left,
+ * 3 up, 4 up-right, 5 right, 6 down-right, 7 down, 8 down-left.
+ *   THE GRAPH is the generic accumulation's: the RECEIVERS R(c) of a data cell c are the neighbours n with
+ *   props(c, n) > 0 that lie inside the raster and are not NoData.  A cell on the raster's edge has R(c) empty.  A share
+ *   into NoData is dropped; it is not an error.
+ *   A STOP CELL is, with chan given (uint8 mask), a data cell with chan != 0; with chan == NULL a data cell with R(c)
+ *   empty.
+ *   Every data cell ends in one of three states.  RESOLVED: a stop cell, with value 0; and a non-stop cell with R(c) not
+ *   empty, once every cell of R(c) is decided, if under strict != 0 every receiver is RESOLVED, under strict == 0 at
+ *   least one is.  DEAD: a non-stop cell with R(c) empty (only with chan given), and a non-stop cell whose receivers are
+ *   all decided and that does not meet the condition above.  UNDECIDED: a cell on a cycle of positive shares, or one that
+ *   depends on such a cell.  A stop cell on a cycle is RESOLVED and breaks the cycle for its donors.
+ *   The CONTRIBUTING receivers of c are the RESOLVED members of R(c) (under strict != 0: all of R(c)).
+ * Outputs, both float64 [height][width], each a nullable pointer (a call must request at least one):
+ *   dist   the increment towards receiver n is len(n) = |cell_x| for n in {1, 5}, |cell_y| for n in {3, 7}, diag
+ *          otherwise; diag = sqrt(cell_x * cell_x + cell_y * cell_y) computed once on the host.
+ *   drop   the increment is (double)z(c) - (double)z(n); it needs the elevations.  Not clamped: an unfilled DEM gives
+ *          negative values.
+ * Per contributing receiver n, v_n = Q(n) + inc(c, n): one double addition (for drop, the one subtraction first).  stat
+ * combines them:
+ *   stat == 1   Q(c) = min v_n;   stat == 2   Q(c) = max v_n   (taken over n = 1..8 in that order with < and >);
+ *   stat == 0   with exactly one contributing receiver Q(c) = v_n, no multiply and no divide; otherwise
+ *               num = sum (double)p_n * v_n, den = sum (double)p_n, both over n = 1..8 in that order starting from 0.0,
+ *               every product and every sum rounded on its own (no fused multiply-add), Q(c) = num / den.
+ * DEAD, undecided and NoData cells get out_nodata.  Both outputs are functions of the inputs alone: every value is
+ * computed once, from final operands in a fixed order, so they are reproducible bit for bit.  With chan == NULL no cell
+ * is DEAD and strict makes no difference.
+ * cell_x and cell_y: their sign is ignored; zero or not finite is RDGPU_ERR_ARG.  A null props9 (dem), no output
+ * requested, drop without elev, stat outside 0..2, a non-positive size or more than 0xFFFF0000 cells returns
+ * RDGPU_ERR_ARG before any device work; nothing is written then.  Inputs are never written.  The _dev forms take device
+ * pointers and are ordered on hip_stream without synchronising it.
+ * rdgpu_dinf_distance_down_<T> takes a DEM: the proportions are FM_Tarboton's in compact form (5 bytes per cell, the
+ * array is never materialised) and the elevations are the DEM's.  T: u8 i8 i16 u16 i32 u32 f32 f64.
+ * rdgpu_mfd_distance_rounds: the work-list launches of the last call.  RDGPU_MFD_DISTANCE_STACK_BELOW: lists shorter
+ * than this many cells run in the kernel that keeps its by-products on a per-wavefront stack (default 4194304; 0: never).
+ * Scratch (13 bytes per cell, shared with the accumulation; 8 more for drop from a DEM that is not float64) comes from
+ * the workspace pool. */
+int rdgpu_mfd_distance_down(const float *props9, int width, int height, const uint8_t *chan /* nullable */,
+                            const double *elev /* nullable; required iff drop */, int stat, int strict, double cell_x,
+                            double cell_y, double *dist /* nullable */, double *drop /* nullable */, double out_nodata);
+int rdgpu_mfd_distance_down_dev(const float *d_props9, int width, int height, const uint8_t *d_chan /* nullable */,
+                                const double *d_elev /* nullable; required iff drop */, int stat, int strict, double cell_x,
+                                double cell_y, double *d_dist /* nullable */, double *d_drop /* nullable */,
+                                double out_nodata, void *hip_stream);
+int rdgpu_mfd_distance_rounds(uint32_t *rounds);
+#define RDGPU_DECL_DINF_DIST(SUF, T)                                                                                     \
+  int rdgpu_dinf_distance_down_##SUF(const T *dem, T nodata, int width, int height, const uint8_t *chan /* nullable */,  \
+                                     int stat, int strict, double cell_x, double cell_y, double *dist /* nullable */,    \
+                                     double *drop /* nullable */, double out_nodata);                                    \
+  int rdgpu_dinf_distance_down_dev_##SUF(const T *d_dem, T nodata, int width, int height,                                \
+                                         const uint8_t *d_chan /* nullable */, int stat, int strict, double cell_x,      \
+                                         double cell_y, double *d_dist /* nullable */, double *d_drop /* nullable */,    \
+                                         double out_nodata, void *hip_stream);
+RDGPU_DECL_DINF_DIST(u8, uint8_t)
+RDGPU_DECL_DINF_DIST(i16, int16_t)
+RDGPU_DECL_DINF_DIST(u16, uint16_t)
+RDGPU_DECL_DINF_DIST(i32, int32_t)
+RDGPU_DECL_DINF_DIST(u32, uint32_t)
+RDGPU_DECL_DINF_DIST(f32, float)
+RDGPU_DECL_DINF_DIST(f64, double)
+RDGPU_DECL_DINF_DIST(i8, int8_t)
+#undef RDGPU_DECL_DINF_DIST
+
 /* ---- synthetic input (test/bench input generator) ----------- */
 int rdgpu_synth_dem_dev_f32(float *d_dem, int width, int height, int seed, int x0, int y0,
                             float tilt, void *hip_stream);

@@ -836,6 +836,103 @@ void d8_hand(const E &dem, const F &flowdirs, G &hand) {
   d8_hand(dem, flowdirs, hand, static_cast<const F *>(nullptr));
 }
 
+// ---- distance and drop DOWN to the stop cells over D-infinity / MFD proportions (no reference counterpart; the
+// definition is in rdgpu.h) ---------------------------------------------------------------------------------------------
+enum class DistanceStat { Average = 0, Minimum = 1, Maximum = 2 };
+struct DistanceDownOptions {
+  DistanceStat stat = DistanceStat::Average;   // how a cell's receivers are combined
+  bool strict = true;                          // every receiver must reach a stop cell (false: at least one)
+  double out_nodata = -9999.0;                 // NoData of both outputs: cells without a value
+};
+namespace detail {
+#define RDGPU_SHIM_DINF_DIST(SUF, T)                                                                                        \
+  inline int c_dinf_dist(const T *z, T nd, int w, int h, const uint8_t *c, int st, int strict, double cx, double cy, double *d, \
+                         double *r, double ond) {                                                                           \
+    return rdgpu_dinf_distance_down_##SUF(z, nd, w, h, c, st, strict, cx, cy, d, r, ond);                                   \
+  }
+RDGPU_SHIM_DINF_DIST(u8, uint8_t) RDGPU_SHIM_DINF_DIST(i8, int8_t) RDGPU_SHIM_DINF_DIST(u16, uint16_t)
+RDGPU_SHIM_DINF_DIST(i16, int16_t) RDGPU_SHIM_DINF_DIST(u32, uint32_t) RDGPU_SHIM_DINF_DIST(i32, int32_t)
+RDGPU_SHIM_DINF_DIST(f32, float) RDGPU_SHIM_DINF_DIST(f64, double)
+#undef RDGPU_SHIM_DINF_DIST
+template <class T>
+int c_dinf_dist(const T *, T, int, int, const uint8_t *, int, int, double, double, double *, double *, double) {
+  unsupported("DinfDistanceDown");
+}
+template <class G>
+double *dist_plane(G *out, int w, int h, double nodata) {
+  if (!out) return nullptr;
+  static_assert(std::is_same<elem_t<G>, double>::value, "distance down: the output rasters must be double");
+  out->resize(w, h);
+  out->setNoData(nodata);
+  return out->data();
+}
+template <class C>
+const uint8_t *dist_mask(int w, int h, const C *channels, const char *fn) {
+  if (!channels) return nullptr;
+  if (channels->width() != w || channels->height() != h)
+    throw std::runtime_error(std::string(fn) + ": the channel mask must have the raster's size");
+  return channels->data();
+}
+}  // namespace detail
+
+// *dist, *drop (each optional, at least one) <- the distance and the drop from every cell down to the stop cells over the
+// proportions `props` (Array3D<float>): the cells of the channel mask, or without one the cells that have no receiver.
+// `elevations` (Array2D<double>, required for drop) are taken as they are.  Cell lengths cell_x, cell_y.  The outputs take
+// the proportions' width and height, NoData opt.out_nodata.
+template <class P, class E, class G, class C>
+void FlowDistanceDown(const P &props, const E *elevations, G *dist, G *drop, const C *channels, double cell_x = 1.0,
+                      double cell_y = 1.0, const DistanceDownOptions &opt = DistanceDownOptions()) {
+  static_assert(std::is_same<detail::elem_t<E>, double>::value, "FlowDistanceDown: the elevations must be Array2D<double>");
+  const int w = props.width(), h = props.height();
+  if (!dist && !drop) throw std::runtime_error("FlowDistanceDown: no output requested");
+  if (drop && !elevations) throw std::runtime_error("FlowDistanceDown: the drop needs the elevations");
+  if (elevations && (elevations->width() != w || elevations->height() != h))
+    throw std::runtime_error("FlowDistanceDown: the elevations must have the proportions' size");
+  const uint8_t *mask = detail::dist_mask(w, h, channels, "FlowDistanceDown");
+  double *pd = detail::dist_plane(dist, w, h, opt.out_nodata), *pr = detail::dist_plane(drop, w, h, opt.out_nodata);
+  if (w == 0 || h == 0) return;
+  const float *p9 = detail::raw3(const_cast<P &>(props), 0);   // (the reference's accessor is non-const; read only)
+  detail::check(rdgpu_mfd_distance_down(p9, w, h, mask, elevations ? (const double *)elevations->data() : nullptr, (int)opt.stat,
+                                        opt.strict ? 1 : 0, cell_x, cell_y, pd, pr, opt.out_nodata), "FlowDistanceDown");
+}
+// the distance alone
+template <class P, class G>
+void FlowDistanceDown(const P &props, G &dist, double cell_x = 1.0, double cell_y = 1.0,
+                      const DistanceDownOptions &opt = DistanceDownOptions()) {
+  const int w = props.width(), h = props.height();
+  double *pd = detail::dist_plane(&dist, w, h, opt.out_nodata);
+  if (w == 0 || h == 0) return;
+  detail::check(rdgpu_mfd_distance_down(detail::raw3(const_cast<P &>(props), 0), w, h, nullptr, nullptr, (int)opt.stat,
+                                        opt.strict ? 1 : 0, cell_x, cell_y, pd, nullptr, opt.out_nodata), "FlowDistanceDown");
+}
+
+// The same over the D-infinity proportions of a DEM (FM_Tarboton, never materialised), elevations and cell lengths
+// (|geotransform[1]|, |geotransform[5]|) the DEM's; the outputs take the DEM's size, geotransform and projection.
+template <class E, class G, class C>
+void DinfDistanceDown(const E &dem, G *dist, G *drop, const C *channels, const DistanceDownOptions &opt = DistanceDownOptions()) {
+  using T = detail::elem_t<E>;
+  const int w = dem.width(), h = dem.height();
+  if (!dist && !drop) throw std::runtime_error("DinfDistanceDown: no output requested");
+  double cx, cy;
+  detail::cell_lengths(dem, "DinfDistanceDown", cx, cy);
+  const uint8_t *mask = detail::dist_mask(w, h, channels, "DinfDistanceDown");
+  for (G *o : {dist, drop})
+    if (o) {
+      static_assert(std::is_same<detail::elem_t<G>, double>::value, "DinfDistanceDown: the output rasters must be double");
+      o->resize(dem);
+      o->setNoData(opt.out_nodata);
+    }
+  if (w == 0 || h == 0) return;
+  detail::check(detail::c_dinf_dist((const T *)dem.data(), (T)dem.noData(), w, h, mask, (int)opt.stat, opt.strict ? 1 : 0, cx, cy,
+                                    dist ? dist->data() : nullptr, drop ? drop->data() : nullptr, opt.out_nodata),
+                "DinfDistanceDown");
+}
+// height above the drainage reached over the D-infinity proportions: the drop down to the channel mask
+template <class E, class G, class C>
+void DinfHand(const E &dem, G &hand, const C &channels, const DistanceDownOptions &opt = DistanceDownOptions()) {
+  DinfDistanceDown(dem, static_cast<G *>(nullptr), &hand, &channels, opt);
+}
+
 // ---- longest upstream flow path on the D8 forest (no reference counterpart; the definition is in rdgpu.h) -----------
 // length <- the length of the longest flow path that ends at each cell; *from_cell (optional, uint32_t) <- the flat index
 // of that path's head, the lowest on a tie; *on_basin_path (optional, uint8_t) <- 1 on the longest path of every basin,

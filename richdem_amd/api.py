@@ -1562,3 +1562,144 @@ def d8_total_upstream_length_dev(dirs, cell_x: float = 1.0, cell_y: float = 1.0,
                                                    _dev_plane(steps, (3, h, w), torch.int32, who),
                                                    _dev_plane(length, (h, w), torch.float64, who), ctypes.c_double(length_nodata),
                                                    _stream_ptr()), "rdgpu_d8_total_upstream_length_dev")
+
+
+# ---- flow distance and drop (HAND) down to the stop cells over D-infinity / MFD proportions (csrc/mfd_distance.hip) ----
+_DIST_WANT = ("dist", "drop")
+_DIST_STAT = {"ave": 0, "min": 1, "max": 2}
+
+
+def _dist_stat(stat, who) -> int:
+    if isinstance(stat, str):
+        if stat not in _DIST_STAT:
+            raise RdgpuError(f"{who}: stat is one of {tuple(_DIST_STAT)}")
+        return _DIST_STAT[stat]
+    return int(stat)   # the C-ABI's numbering; it rejects what is outside 0..2
+
+
+def _dist_want(want, who):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in _DIST_WANT for k in want):
+        raise RdgpuError(f"{who}: want names at least one of {_DIST_WANT}")
+    return want
+
+
+def _props3(props, who):
+    if not isinstance(props, np.ndarray) or props.ndim != 3 or props.shape[2] != 9 or props.dtype != np.float32:
+        raise RdgpuError(f"{who}: expected a float32 proportions array [h, w, 9]")
+    return np.ascontiguousarray(props)
+
+
+def _dist_planes(want, h, w):
+    return {k: np.empty((h, w), np.float64) for k in _DIST_WANT if k in want}
+
+
+def mfd_distance_down(props: np.ndarray, chan: np.ndarray | None = None, elev: np.ndarray | None = None, stat="ave",
+                      strict: bool = True, cell=(1.0, 1.0), out_nodata: float = -1.0, want=("dist",)) -> dict:
+    """Distance ("dist") and drop ("drop", needs elev) down to the stop cells over a proportions array [h, w, 9]
+    (include/rdgpu.h states the definition): a dict with the float64 planes named in `want`.  chan: an optional uint8 mask
+    of the stop cells (None: the cells without receivers); stat "ave" / "min" / "max" combines a cell's receivers; strict:
+    every receiver must reach a stop cell; out_nodata where there is no value.  elev of any real dtype is taken as float64."""
+    who = "mfd_distance_down"
+    props = _props3(props, who)
+    h, w = props.shape[:2]
+    chan = _mask2d(chan, (h, w), who)
+    want = _dist_want(want, who)
+    if elev is not None:
+        if not isinstance(elev, np.ndarray) or elev.shape != (h, w):
+            raise RdgpuError(f"{who}: elev is an array of the proportions' raster shape")
+        elev = np.ascontiguousarray(elev, dtype=np.float64)
+    cx, cy = _cell2(cell, who)
+    out = _dist_planes(want, h, w)
+    check(lib().rdgpu_mfd_distance_down(_ptr(props), w, h, _ptr(chan), _ptr(elev), _dist_stat(stat, who), int(bool(strict)), cx, cy,
+                                        _ptr(out.get("dist")), _ptr(out.get("drop")), ctypes.c_double(out_nodata)),
+          "rdgpu_mfd_distance_down")
+    return out
+
+
+def dinf_distance_down(dem: np.ndarray, nodata, chan: np.ndarray | None = None, stat="ave", strict: bool = True, cell=(1.0, 1.0),
+                       out_nodata: float = -1.0, want=("dist",)) -> dict:
+    """mfd_distance_down over the D-infinity proportions of dem (FM_Tarboton, never materialised), elevations the DEM's."""
+    who = "dinf_distance_down"
+    dem, s = _elev(dem, who, mfd=True)
+    h, w = dem.shape
+    chan = _mask2d(chan, (h, w), who)
+    want = _dist_want(want, who)
+    cx, cy = _cell2(cell, who)
+    out = _dist_planes(want, h, w)
+    check(getattr(lib(), f"rdgpu_dinf_distance_down_{s}")(_ptr(dem), _scalar(s, nodata), w, h, _ptr(chan), _dist_stat(stat, who),
+                                                          int(bool(strict)), cx, cy, _ptr(out.get("dist")), _ptr(out.get("drop")),
+                                                          ctypes.c_double(out_nodata)), "rdgpu_dinf_distance_down")
+    return out
+
+
+def dinf_hand(dem: np.ndarray, nodata, chan: np.ndarray, stat="ave", strict: bool = True, out_nodata: float = -9999.0) -> np.ndarray:
+    """float64 raster: height above the drainage reached over the D-infinity proportions of dem -- the "drop" plane of
+    dinf_distance_down with the channel mask chan.  Not clamped."""
+    return dinf_distance_down(dem, nodata, chan, stat, strict, (1.0, 1.0), out_nodata, want=("drop",))["drop"]
+
+
+def mfd_distance_rounds() -> int:
+    """Work-list launches of the last mfd_distance_down / dinf_distance_down / dinf_hand call or _dev form."""
+    r = ctypes.c_uint32(0)
+    check(lib().rdgpu_mfd_distance_rounds(ctypes.byref(r)), "rdgpu_mfd_distance_rounds")
+    return r.value
+
+
+def _torch_mfd_suffix(t, who) -> str:
+    import torch
+
+    m = {torch.int8: "i8", torch.uint8: "u8", torch.int16: "i16", torch.int32: "i32", torch.float32: "f32", torch.float64: "f64"}
+    for name, s in (("uint16", "u16"), ("uint32", "u32")):
+        if hasattr(torch, name):
+            m[getattr(torch, name)] = s
+    if t.dtype not in m:
+        raise RdgpuError(f"{who}: unsupported elevation dtype {t.dtype}")
+    return m[t.dtype]
+
+
+def mfd_distance_down_dev(props, chan=None, elev=None, stat="ave", strict: bool = True, cell=(1.0, 1.0), out_nodata: float = -1.0,
+                          dist=None, drop=None) -> None:
+    """The planes given (float64 CUDA tensors [h, w]) <- mfd_distance_down of props (float32 CUDA tensor [h, w, 9]), chan
+    an optional uint8 CUDA mask, elev a float64 CUDA tensor; on torch's current stream and without synchronising it.  At
+    least one plane must be given."""
+    import torch
+
+    who = "mfd_distance_down_dev"
+    if not (props.is_cuda and props.dim() == 3 and props.shape[2] == 9 and props.is_contiguous() and props.dtype == torch.float32):
+        raise RdgpuError(f"{who}: expected a contiguous float32 tensor [h, w, 9] on the GPU")
+    h, w = props.shape[:2]
+    if dist is None and drop is None:
+        raise RdgpuError(f"{who}: no output requested")
+    cx, cy = _cell2(cell, who)
+    check(lib().rdgpu_mfd_distance_down_dev(ctypes.c_void_p(props.data_ptr()), w, h, _dev_mask(chan, (h, w), who),
+                                            _dev_plane(elev, (h, w), torch.float64, who), _dist_stat(stat, who), int(bool(strict)),
+                                            cx, cy, _dev_plane(dist, (h, w), torch.float64, who),
+                                            _dev_plane(drop, (h, w), torch.float64, who), ctypes.c_double(out_nodata), _stream_ptr()),
+          "rdgpu_mfd_distance_down_dev")
+
+
+def dinf_distance_down_dev(dem, nodata, chan=None, stat="ave", strict: bool = True, cell=(1.0, 1.0), out_nodata: float = -1.0,
+                           dist=None, drop=None) -> None:
+    """The planes given (float64 CUDA tensors) <- dinf_distance_down of dem (CUDA tensor of any element type torch has of
+    int8 .. uint32, float32, float64), on torch's current stream.  At least one plane must be given."""
+    import torch
+
+    who = "dinf_distance_down_dev"
+    h, w = _dev2d(dem, who)
+    s = _torch_mfd_suffix(dem, who)
+    if dist is None and drop is None:
+        raise RdgpuError(f"{who}: no output requested")
+    cx, cy = _cell2(cell, who)
+    check(getattr(lib(), f"rdgpu_dinf_distance_down_dev_{s}")(ctypes.c_void_p(dem.data_ptr()), _scalar(s, nodata), w, h,
+                                                              _dev_mask(chan, (h, w), who), _dist_stat(stat, who),
+                                                              int(bool(strict)), cx, cy,
+                                                              _dev_plane(dist, (h, w), torch.float64, who),
+                                                              _dev_plane(drop, (h, w), torch.float64, who),
+                                                              ctypes.c_double(out_nodata), _stream_ptr()),
+          "rdgpu_dinf_distance_down_dev")
+
+
+def dinf_hand_dev(dem, nodata, chan, out, stat="ave", strict: bool = True, out_nodata: float = -9999.0) -> None:
+    """out (float64 CUDA tensor) <- dinf_hand of dem and the uint8 CUDA channel mask chan."""
+    dinf_distance_down_dev(dem, nodata, chan, stat, strict, (1.0, 1.0), out_nodata, drop=out)

@@ -18,17 +18,10 @@
 // pending-donor count; it continues inline with the first receiver it completed and flags the others;
 // flagged cells are compacted into the next round's work list.  f64 sums in a different order than the
 // reference's FIFO: exact for integer-valued flows, f64 rounding otherwise.
-#include "common.hpp"
-
-#include <algorithm>
+#include "mfd_shared.hpp"
 
 namespace rdgpu {
 
-constexpr int NTHR = 256;
-static inline uint32_t sgrid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + NTHR - 1) / NTHR, 256u * 32u); }
-
-__device__ __forceinline__ int mdx(int n) { return (n == 1 || n == 2 || n == 8) ? -1 : (n >= 4 && n <= 6) ? 1 : 0; }
-__device__ __forceinline__ int mdy(int n) { return (n >= 2 && n <= 4) ? -1 : (n >= 6 && n <= 8) ? 1 : 0; }
 
 // ------------------------------------------------------------------------------------------
 // D-infinity per cell, on the 3 x 3 window of elevations (rows y-1, y, y+1; columns x-1, x, x+1).
@@ -258,27 +251,6 @@ __global__ __launch_bounds__(NTHR) void k_tarboton_props(const uint8_t *__restri
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// proportions accessors
-// ------------------------------------------------------------------------------------------
-struct PropsAcc {   // the reference's Array3D<float>
-  const float *props;
-  __device__ __forceinline__ bool nodata(uint64_t c) const { return props[9 * c] == -2.0f; }
-  __device__ __forceinline__ float share(uint64_t c, int n) const { return props[9 * c + n]; }
-};
-struct DinfAcc {    // compact D-infinity form
-  const uint8_t *rcv;
-  const float *sh1, *sh2;
-  __device__ __forceinline__ bool nodata(uint64_t c) const { return rcv[c] == 255; }
-  __device__ __forceinline__ float share(uint64_t c, int n) const {
-    const int rr = rcv[c], r = rr & 0xF;
-    if (rr == 255 || r < 1 || r > 8) return -1.0f;
-    if (n == r) return sh1[c];
-    if ((rr & 0x10) && n == (r == 8 ? 1 : r + 1)) return sh2[c];
-    return -1.0f;
-  }
-};
-
 constexpr uint32_t PEND_NODATA = 0xFFFFFFFFu;
 
 // deps, flow_accumulation_generic.hpp:47-58 (donors are interior cells only), + the initial ready flags :61-64
@@ -387,71 +359,6 @@ __global__ __launch_bounds__(NTHR) void k_mfd_nodata(ACC a, double *acc, uint64_
   const uint64_t stride = (uint64_t)gridDim.x * NTHR;
   for (uint64_t c = (uint64_t)blockIdx.x * NTHR + threadIdx.x; c < n; c += stride)
     if (a.nodata(c)) acc[c] = -1.0;                                     // ACCUM_NO_DATA, :95-97
-}
-
-// ---- ready flags -> work list (count / scan / fill; flags are cleared) ------------------------------
-constexpr int CPB = 4096;
-__global__ __launch_bounds__(NTHR) void k_rdy_count(const uint8_t *__restrict__ f, uint64_t n, uint32_t *counts) {
-  __shared__ uint32_t ws[NTHR / 64];
-  const uint64_t base = (uint64_t)blockIdx.x * CPB;
-  uint32_t cnt = 0;
-#pragma unroll 4
-  for (int j = 0; j < CPB / NTHR; j++) {
-    const uint64_t c = base + (uint64_t)j * NTHR + threadIdx.x;
-    if (c < n && f[c]) cnt++;
-  }
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) counts[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-__global__ __launch_bounds__(1024) void k_rdy_scan(uint32_t *counts, uint32_t m, uint32_t *total) {
-  __shared__ uint32_t part[1024];
-  const uint32_t chunk = (m + 1023u) / 1024u;
-  const uint32_t lo = threadIdx.x * chunk, hi = min(lo + chunk, m);
-  uint32_t s = 0;
-  for (uint32_t i = lo; i < hi; i++) s += counts[i];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    uint32_t v = (threadIdx.x >= (uint32_t)o) ? part[threadIdx.x - o] : 0;
-    __syncthreads();
-    part[threadIdx.x] += v;
-    __syncthreads();
-  }
-  uint32_t run = threadIdx.x ? part[threadIdx.x - 1] : 0;
-  for (uint32_t i = lo; i < hi; i++) {
-    const uint32_t v = counts[i];
-    counts[i] = run;
-    run += v;
-  }
-  if (threadIdx.x == 1023) *total = part[1023];
-}
-__global__ __launch_bounds__(NTHR) void k_rdy_fill(uint8_t *f, uint64_t n, const uint32_t *__restrict__ offsets,
-                                                   uint32_t *__restrict__ out) {
-  __shared__ uint32_t ws[NTHR / 64];
-  const uint64_t base = (uint64_t)blockIdx.x * CPB;
-  uint32_t run = offsets[blockIdx.x];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int j = 0; j < CPB / NTHR; j++) {
-    const uint64_t c = base + (uint64_t)j * NTHR + threadIdx.x;
-    const bool hit = c < n && f[c];
-    if (hit) f[c] = 0;
-    const unsigned long long bal = __ballot(hit);
-    const uint32_t rank = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) ws[wv] = __popcll(bal);
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < NTHR / 64; k++) {
-      const uint32_t v = ws[k];
-      if (k < wv) woff += v;
-      tot += v;
-    }
-    if (hit) out[run + woff + rank] = (uint32_t)c;
-    run += tot;
-    __syncthreads();
-  }
 }
 
 // The same step with the round's by-products consumed where they arise (r04f).  In k_mfd_round a cell completed "on the
@@ -703,13 +610,8 @@ static void fm_mfd_device(const T *d_z, T nodata, int w, int h, int method, doub
   RD_LAUNCH("mfd.fm_mfd", (k_fm_mfd<T>), dim3(sgrid((uint64_t)w * h)), dim3(NTHR), 0, s, d_z, nodata, d_props, w, h, method, xparam);
 }
 
-static void check_dims(int w, int h, const char *who) {
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, std::string(who) + ": width and height must be positive");
-  if ((uint64_t)w * (uint64_t)h > 0xFFFF0000ull) throw Error(RDGPU_ERR_ARG, std::string(who) + ": raster too large");
-}
-
 template <class T>
-static DinfAcc tarboton_device(const T *d_z, T nodata, int w, int h, hipStream_t s) {
+DinfAcc tarboton_device(const T *d_z, T nodata, int w, int h, hipStream_t s) {
   const uint64_t n = (uint64_t)w * h;
   Workspace &ws = Workspace::get();
   uint8_t *rcv = ws.buf<uint8_t>("mfd.rcv", n);
@@ -720,13 +622,14 @@ static DinfAcc tarboton_device(const T *d_z, T nodata, int w, int h, hipStream_t
   }
   return DinfAcc{rcv, sh1, sh2};
 }
-
-template <class T>
-static void host_dem(const T *dem, int w, int h, T **d) {
-  const size_t n = (size_t)w * h;
-  *d = Workspace::get().buf<T>("host.dem", n);
-  RD_HIP(hipMemcpy(*d, dem, n * sizeof(T), hipMemcpyHostToDevice));
-}
+template DinfAcc tarboton_device<uint8_t>(const uint8_t *, uint8_t, int, int, hipStream_t);   // (mfd_distance.hip)
+template DinfAcc tarboton_device<int8_t>(const int8_t *, int8_t, int, int, hipStream_t);
+template DinfAcc tarboton_device<uint16_t>(const uint16_t *, uint16_t, int, int, hipStream_t);
+template DinfAcc tarboton_device<int16_t>(const int16_t *, int16_t, int, int, hipStream_t);
+template DinfAcc tarboton_device<uint32_t>(const uint32_t *, uint32_t, int, int, hipStream_t);
+template DinfAcc tarboton_device<int32_t>(const int32_t *, int32_t, int, int, hipStream_t);
+template DinfAcc tarboton_device<float>(const float *, float, int, int, hipStream_t);
+template DinfAcc tarboton_device<double>(const double *, double, int, int, hipStream_t);
 
 }  // namespace rdgpu
 

@@ -281,7 +281,10 @@ RDGPU_DECL_WS(u64, uint64_t)
  *                              a fill synchronises twice, rdgpu_fill_stats::host_syncs)
  *   RDGPU_FILL_TAIL_ROOTS=<n>  a round entered by at most n live roots and 8 n pair records, and every round after it,
  *                              runs in the single-workgroup tail kernel (default 1024); 0: never, every round is
- *                              full-width launches; a huge value: from round 2 on */
+ *                              full-width launches; a huge value: from round 2 on
+ *   RDGPU_FILL_DISSOLVE=0      every pit of the descent forest is a basin (default: a pit whose lowest neighbour lies in its
+ *                              64 x 64 tile and drains elsewhere joins that neighbour's tree and is raised on its own;
+ *                              rdgpu_fill_stats::dissolved_pits) */
 /* Statistics of the last fill on this process (for DESIGN.md / bench.py reporting). */
 typedef struct rdgpu_fill_stats {
   uint64_t cells;       /* width*height                                   */
@@ -292,7 +295,9 @@ typedef struct rdgpu_fill_stats {
   uint32_t tile_cells;  /* cells per scan tile                               */
   uint32_t edge_records; /* component-pair records the first raster pass handed to rounds 2.. (0: raster rounds) */
   uint32_t host_syncs;   /* stream synchronisations inside the fill (r06: 2 -- after the descent, after the rounds) */
-  uint32_t reserved;
+  uint32_t dissolved_pits; /* of `basins`: pits the descent dissolved -- single cells whose lowest neighbour drains elsewhere;
+                              they get no row in the basin tables and no pair records (0 with RDGPU_FILL_DISSOLVE=0, in the
+                              shards, the fills with outlets and the classic path); this word was `reserved` */
 } rdgpu_fill_stats;
 int rdgpu_fill_get_stats(rdgpu_fill_stats *out);
 

@@ -37,7 +37,7 @@ class rdgpu_fill_stats(ctypes.Structure):
         ("tile_cells", ctypes.c_uint32),
         ("edge_records", ctypes.c_uint32),
         ("host_syncs", ctypes.c_uint32),
-        ("reserved", ctypes.c_uint32),
+        ("dissolved_pits", ctypes.c_uint32),
     ]
 
 
@@ -78,7 +78,7 @@ def fill_stats() -> dict:
     check(lib().rdgpu_fill_get_stats(ctypes.byref(st)), "rdgpu_fill_get_stats")
     return {"cells": st.cells, "basins": st.basins, "rounds": st.rounds, "jump_passes": st.jump_passes,
             "scan_tiles": st.scan_tiles, "tile_cells": st.tile_cells, "edge_records": st.edge_records,
-            "host_syncs": st.host_syncs}
+            "host_syncs": st.host_syncs, "dissolved_pits": st.dissolved_pits}
 
 
 def profile_enable(on: bool = True) -> None:

@@ -2048,7 +2048,7 @@ struct FusedBuf {
   uint16_t *lab16;                 // [cells] slot of the cell's root within its descent tile
   uint32_t *G;                     // [gcap] node table: stripe s owns [s * rcap, (s + 1) * rcap)
   uint32_t *tile_base, *tile_count;   // [descent tiles]
-  unsigned long long *counters;    // [stripe * FSTRIDE] (nodes << 32) | pits of the stripe
+  unsigned long long *counters;    // [stripe * FSTRIDE] (nodes << 32) | pits of the stripe; [stripe * FSTRIDE + 1] its dissolved pits
   uint32_t gcap, rcap, smask;
   uint32_t *overflow;
   // the first and last column of every descent tile as compact records (key, slot), [tile][side][row]: the pair pass takes
@@ -2062,22 +2062,27 @@ struct FusedBuf {
   uint16_t *edgeR = nullptr;
 };
 
-// after the descent: dense basin ids.  out[0] = basins, out[1] = nodes in use, out[2] = the fullest stripe's node count
+// after the descent: dense basin ids.  out[0] = basins, out[1] = nodes in use, out[2] = the fullest stripe's node count,
+// out[3] = dissolved pits (no basins: not in out[0])
 __global__ __launch_bounds__(64) void k_stripe_offsets(const unsigned long long *__restrict__ counters, uint32_t nstripes,
-                                                       uint32_t *pitoff, uint32_t *out) {
+                                                       uint32_t *pitoff, uint32_t *out, uint32_t *forest_max) {
   const uint32_t s = threadIdx.x;
   const unsigned long long c = s < nstripes ? counters[s * FSTRIDE] : 0ull;
   const uint32_t pits = (uint32_t)c, nodes = (uint32_t)(c >> 32);
   uint32_t incl = pits, tot = nodes, mx = nodes;
+  uint32_t dis = s < nstripes ? (uint32_t)counters[s * FSTRIDE + 1] : 0u;   // the stripe's dissolved pits (k_descent16)
+  uint32_t mxd = nodes + dis;   // the stripe's nodes had no pit dissolved: what the node table is asked to hold (fill_fused)
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
     const uint32_t v = __shfl_up(incl, o, 64);
     if ((int)s >= o) incl += v;
     tot += __shfl_xor(tot, o, 64);
     mx = max(mx, (uint32_t)__shfl_xor(mx, o, 64));
+    dis += __shfl_xor(dis, o, 64);
+    mxd = max(mxd, (uint32_t)__shfl_xor(mxd, o, 64));
   }
   if (s < nstripes) pitoff[s] = incl - pits;
-  if (s == 63) { out[0] = incl; out[1] = tot; out[2] = mx; }
+  if (s == 63) { out[0] = incl; out[1] = tot; out[2] = mx; out[3] = dis; *forest_max = mxd; }
 }
 
 // OUTLETS: cells flagged in `outlet` drain like the raster's border cells (interior outlets: the restricted fills of
@@ -2092,8 +2097,13 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
                                                     uint32_t tilesX, uint32_t ntiles, const uint8_t *__restrict__ outlet = nullptr,
                                                     const uint8_t *__restrict__ skip = nullptr,
                                                     const uint32_t *__restrict__ tlist = nullptr, int open_top = 0,
-                                                    int open_bottom = 0) {
+                                                    int open_bottom = 0, int dissolve = 0) {
   // tlist (optional, with OUTLETS): the tiles to work on, one block each (ntiles = the raster's tiles all the same)
+  // dissolve (block-uniform; the plain fill only): a pit whose lowest neighbour q lies in the tile and does not drain
+  // into it is no basin of its own -- it points at q, and its label carries q's direction for the finalize
+  constexpr bool DIS_OK = !OUTLETS && !CUT;
+  const bool dis = DIS_OK && dissolve != 0;
+  __shared__ uint32_t dcnt;
   __shared__ uint32_t sk[DLH * DLW];
   // rows of LPD = 66 entries: with 64 two-byte entries every row starts on the same LDS bank and the jumps' gathers --
   // neighbouring columns of different rows -- collide (29 % of the kernel's LDS cycles, r03e)
@@ -2169,6 +2179,7 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
       if (gx >= 0 && gx < w && gy >= 0 && gy < h) kk = key32_fast<T>(z[(size_t)gy * w + gx]);
       sk[ly * DLW + lxh] = kk;
     }
+    if (DIS_OK && threadIdx.x == 0) dcnt = 0;
   }
   __syncthreads();
   // (the wavefront's index as a SCALAR: everything derived from the row -- bounds tests, LDS row offsets -- then runs on the
@@ -2190,7 +2201,10 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
   uint16_t *const slot16 = reinterpret_cast<uint16_t *>(sk);   // valid once the keys are dead (after the edge keys are out)
   const uint32_t selfb0 = (uint32_t)((ly0 * LPD + lx) * 2);
   uint32_t p[RPT];                                 // the cell's pointer: byte offset into lp
-  uint32_t codes[RPT / 4] = {0, 0, 0, 0};          // one byte per row: 0 pit, 1..8 exit towards that neighbour, 9 drains off the raster
+  // four bits per row, rows 0..7 and 8..15: 1..8 the lowest neighbour (an exit's target, a pit's q), 9 drains off the raster.
+  // (Two words and one select to read a row's: with four words of a byte per row the select chain became an indexed load
+  // from a copy of the words in scratch memory.)
+  uint32_t codesLo = 0, codesHi = 0;
   uint32_t rootmask = 0, pitmask = 0, outmask = 0;
   {
     // packed word of a candidate: [15:0] byte delta + 134, [19:16] exit code, [26:24] column 0 / 1 / 2, [27] row above, [29] row below
@@ -2250,9 +2264,10 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
       const uint32_t rel = selfp ? (uint32_t)(2 * LPD + 2) : (W & 0xFFFFu);   // (the delta's bias: the cell itself)
       p[j] = rel + (self - (uint32_t)(2 * LPD + 2));
       *reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(lp) + self) = (uint16_t)p[j];
-      const uint32_t cexit = (W >> 16) & 15u, cin = stays ? 0u : cexit;
-      const uint32_t code = border ? 9u : cin;
-      codes[j >> 2] |= code << (8 * (j & 3));
+      const uint32_t cexit = (W >> 16) & 15u;   // (a pit keeps the code of its lowest neighbour: pitmask tells it from an exit)
+      const uint32_t code = border ? 9u : cexit;
+      if (j < 8) codesLo |= code << (4 * (j & 7));
+      else codesHi |= code << (4 * (j & 7));
       bool root = incell & selfp;
       if (OUTLETS) {   // the tile's outlets share slot 0
         const bool outroot = root & border;
@@ -2271,13 +2286,39 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
   }
   // (the masks and codes are formed HERE, in vector registers: left to the compiler they sink below the jump loop, which
   // keeps sixteen rows of lane masks alive in scalar registers and spills them lane by lane)
-  asm volatile("" : "+v"(rootmask), "+v"(pitmask), "+v"(outmask), "+v"(codes[0]), "+v"(codes[1]), "+v"(codes[2]), "+v"(codes[3]));
+  asm volatile("" : "+v"(rootmask), "+v"(pitmask), "+v"(outmask), "+v"(codesLo), "+v"(codesHi));
   // the tile's first and last column: the KEYS of the compact records for the pair pass (before the keys' array is reused)
   if (fo.edgeK && threadIdx.x < 2 * DH) {
     const int side = threadIdx.x >> 6, lye = threadIdx.x & (DH - 1), lxe = side ? DW - 1 : 0;
     fo.edgeK[((size_t)t * 2 + side) * DH + lye] = sk[(lye + 1) * DLW + lxe + 1];
   }
   __syncthreads();
+  auto code_of = [codesLo, codesHi](int j) -> int {   // row j's code (j varies per lane)
+    return (int)((j < 8 ? codesLo : codesHi) >> (4 * (j & 7)) & 15u);
+  };
+  // ---- pits that are no depressions.  q, the lowest neighbour of pit p, does not drain into p: then q is not
+  // in p's basin, the lowest pass out of that basin is key(q) and only p lies below it.  p points at q -- its catchment
+  // joins q's tree, p is no root and no basin -- and the finalize raises p alone to max(key(q), level).  lp[q] is q's
+  // pointer as classify stored it (q is never such a pit itself: p is a lower neighbour of q), the jumps start after the
+  // second barrier: a cell of another wavefront that read the old lp[p] == p twice would take p for its root.
+  uint32_t dissmask = 0;
+  if (dis) {
+    for (uint32_t m = pitmask; m; m &= m - 1) {
+      const int j = __ffs((int)m) - 1;
+      const int code = code_of(j);   // 1..8: a pit is no border cell
+      const int n = code <= 4 ? code - 1 : code, nr = n >= 6 ? 2 : n >= 3 ? 1 : 0, nc = n - 3 * nr;
+      const int qx = lx + nc - 1, qy = ly0 + j + nr - 1;
+      if ((unsigned)qx >= (unsigned)DW || (unsigned)qy >= (unsigned)DH) continue;   // q lies in the next tile: p stays a pit
+      const uint32_t self = selfb0 + (uint32_t)(j * LPD * 2), qb = (uint32_t)((qy * LPD + qx) * 2);
+      if ((uint32_t)*reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(lp) + qb) == self) continue;   // q drains into p
+      *reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(lp) + self) = (uint16_t)qb;   // (p[j] stays: the first jump reads lp[self])
+      dissmask |= 1u << j;
+    }
+    rootmask &= ~dissmask;
+    pitmask &= ~dissmask;
+    if (dissmask) atomicAdd(&dcnt, (uint32_t)__popc(dissmask));
+    __syncthreads();
+  }
   {   // pointer jumping inside the tile: every wavefront on its own rows until they all point to roots; no barriers
     const char *const lpb = reinterpret_cast<const char *>(lp);
     uint32_t gact = (1u << (RPT / 4)) - 1u;   // (scalar) groups of four rows with a pointer that may still move
@@ -2345,6 +2386,8 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
     fo.tile_count[t] = nr;
     fits_s = (unsigned long long)rl + nr <= fo.rcap ? 1u : 0u;
     if (!fits_s) *fo.overflow = 1;
+    // the dissolved pits of the stripe: the second word of the stripe's line (a statistic: nothing waits for it)
+    if (DIS_OK && dis && dcnt != 0u) atomicAdd(&fo.counters[st * FSTRIDE + 1], (unsigned long long)dcnt);
   }
   {   // (the roots' slots do not depend on the counter: written beside thread 0's atomic)
     uint32_t pre = incl - mine;
@@ -2369,12 +2412,11 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
     for (uint32_t m = rootmask; m; m &= m - 1) {
       const int j = __ffs((int)m) - 1;
       const int ly = ly0 + j;
-      const uint32_t cw = j < 8 ? (j < 4 ? codes[0] : codes[1]) : (j < 12 ? codes[2] : codes[3]);
-      const int code = (int)(cw >> (8 * (j & 3)) & 15u);
+      const int code = code_of(j);
       const int n = code <= 4 ? code - 1 : code;   // 3x3 position of the root's descent neighbour (codes 1..8)
       const int nr = n >= 6 ? 2 : n >= 3 ? 1 : 0, nc = n - 3 * nr;
       const uint32_t pend = LAB_PEND | ((uint32_t)(y0 + ly + nr - 1) * (uint32_t)w + (uint32_t)(x0 + lx + nc - 1));
-      const uint32_t word = code == 0 ? pit++ : code == 9 ? OUTP : pend;
+      const uint32_t word = (pitmask >> j & 1u) ? pit++ : code == 9 ? OUTP : pend;
       fo.G[nodes0 + slot] = word;
       slot++;
     }
@@ -2396,6 +2438,16 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
         if ((gx < w) & (gy < h)) fo.lab16[(size_t)gy * w + gx] = rv;   // (< 4096: not every cell of a tile can be a root)
       }
     }
+    // a dissolved pit's label once more, with its flag and the position of q in the four bits a slot leaves free:
+    // slot | (8 | code - 1) << 12.  (The thread that stored the plain label above: the two stores keep their order.  A
+    // dissolved pit lies in the raster; lp[self] is p[j], the cell's root, since the jumps' first pass.)
+    if (DIS_OK)
+      for (uint32_t m = dissmask; m; m &= m - 1) {
+        const int j = __ffs((int)m) - 1;
+        const uint32_t root = *reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(lp) + selfb0 + (uint32_t)(j * LPD * 2));
+        const uint32_t slot = *reinterpret_cast<const uint16_t *>(sl + root);
+        fo.lab16[(size_t)(y0 + ly0 + j) * w + gx] = (uint16_t)(slot | ((8u | (uint32_t)(code_of(j) - 1)) << 12));
+      }
     // the tile's first and last column, the SLOTS of the compact records: two wavefronts, one row per lane, coalesced.
     // A cell past the raster's end gets slot 0: the pair pass does read such a record (a ring cell outside the raster is
     // loaded from a clamped position and discarded afterwards), and follows its slot into the node table.
@@ -2454,7 +2506,7 @@ __global__ __launch_bounds__(NTHR) void k_resolve_nodes(uint32_t *G, const unsig
       if (lx == 0u || lx == (uint32_t)(DW - 1)) src = edgeS + ((size_t)tile * 2 + (lx != 0u)) * DH + ly;
       else if (ly == 0u || ly == (uint32_t)(DH - 1)) src = edgeR + ((size_t)tile * 2 + (ly != 0u)) * DW + lx;
     }
-    fn = tile_base[tile] + *src;
+    fn = tile_base[tile] + (*src & (uint16_t)(DW * DH - 1));   // (the raster's label of a dissolved pit carries a flag)
     last = cell;
     v = __hip_atomic_load(&G[fn], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (++hops > (1 << 22)) { *flag = 1; break; }   // (cannot happen: descent paths are loop free)
@@ -2628,7 +2680,16 @@ __global__ __launch_bounds__(NTHR) void k_finalize16(T *z, const uint16_t *__res
 #pragma unroll
     for (int e = 0; e < 4; e++) {
       if (gx + e >= w) continue;
-      const uint32_t L = sl[lq.v[e] & (uint16_t)(DW * DH - 1)];
+      const uint32_t lab = lq.v[e];
+      uint32_t L = sl[lab & (uint32_t)(DW * DH - 1)];
+      if (lab & 0x8000u) {
+        // a dissolved pit (k_descent16): its floor is the key of q, the neighbour it points at, in the same descent
+        // tile and basin.  z[q] is read now, maybe while another thread raises it: to max(key(q), L), so the same result.
+        const int d = (int)(lab >> 12) & 7, n = d < 4 ? d : d + 1, nr = n >= 6 ? 2 : n >= 3 ? 1 : 0, nc = n - 3 * nr;
+        const T zn = z[(size_t)(gy + nr - 1) * w + (size_t)(gx + e + nc - 1)];   // (no border cell: q lies in the raster)
+        const uint32_t kq = Key32<T>::to(zn);
+        L = kq > L ? kq : L;
+      }
       if (L > Key32<T>::to(zq.v[e])) { zq.v[e] = Key32<T>::from(L); any = true; }
     }
     if (any) {
@@ -2664,6 +2725,8 @@ constexpr int NT_CAP = 1024;   // node-table entries of one descent tile held in
 static_assert(NT_CAP * 4 <= TW * TH * 2, "the node table lives in the boundary list's storage");
 static_assert(TW == DW && DH % TH == 0, "a scan tile lies inside one descent tile");
 constexpr uint32_t NO_TILE = 0xFFFFFFFFu;
+// a 16-bit label's slot: the plain fill's descent flags a dissolved pit in the four bits above it, for the finalize alone
+constexpr uint32_t LAB16_SLOT = (uint32_t)(DW * DH - 1);
 constexpr int RING = 2 * LW + 2 * TH;   // ring cells of a tile: two rows of LW, two columns of TH
 
 // A pair that found no slot in the tile's table goes straight to the BLOCK's segment (k_pairs16: one segment per
@@ -2751,7 +2814,7 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
       const size_t e = ((size_t)dtn * 2 + (rx == 0 ? 1 : 0)) * DH + (uint32_t)(gy % DH);
       const size_t g = col ? (size_t)y0 * w + x0 : (size_t)gy * w + gx;   // (a column cell reads nothing new from the raster)
       rtb = tile_base[dtn];
-      rl = col ? (uint32_t)edgeS[e] : (uint32_t)lab16[g];
+      rl = col ? (uint32_t)edgeS[e] : (uint32_t)lab16[g] & LAB16_SLOT;
       rkey = col ? edgeK[e] : 0u;
       rz = z[g];
     }
@@ -2828,12 +2891,12 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
 #pragma unroll
         for (int r = 0; r < 2; r++)
 #pragma unroll
-          for (int e = 0; e < 4; e++) cq[r][e] = ntab[lq[r].v[e]];
+          for (int e = 0; e < 4; e++) cq[r][e] = ntab[lq[r].v[e] & LAB16_SLOT];
       } else {   // more nodes than the table holds (white noise): gathered
 #pragma unroll
         for (int r = 0; r < 2; r++)
 #pragma unroll
-          for (int e = 0; e < 4; e++) cq[r][e] = curN[tbC + (uint32_t)lq[r].v[e]];
+          for (int e = 0; e < 4; e++) cq[r][e] = curN[tbC + ((uint32_t)lq[r].v[e] & LAB16_SLOT)];
       }
       if (x0 + TW <= w && y0 + TH <= h) {   // (block-uniform) the whole tile lies in the raster: no tests
 #pragma unroll
@@ -3135,31 +3198,57 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   const uint32_t *dl = listed ? lists->d : nullptr, *sl_ = listed ? lists->d + lists->stride : nullptr,
                  *fl = listed ? lists->d + 2 * (size_t)lists->stride : nullptr;
   if (listed && lists->n[0] == 0) return true;   // nothing but walls anywhere: nothing to raise
+  // RDGPU_FILL_DISSOLVE=0: every pit of the descent forest stays a basin (the plain fill; shards and outlets never dissolve)
+  const char *env_dis = getenv("RDGPU_FILL_DISSOLVE");
+  const int dissolve = (!outlet && !sharded && !(env_dis && env_dis[0] == '0')) ? 1 : 0;
   // (outlets never come with a cut; the kernel reads outlet, skip and dl only with OUTLETS, the cut rows only with CUT)
   with_flag(vec, [&](auto V) {
     auto descent = [&](auto OUTLETS, auto CUT) {
       RD_LAUNCH("fill.descent", (k_descent16<T, TOPO, V, OUTLETS, CUT>), dim3(listed ? lists->n[0] : xcd_grid(dnt)), dim3(NTHR), 0, s,
-                (const T *)d_z, fo, w, h, dtx, dnt, outlet, skip, dl, open_top, open_bottom);
+                (const T *)d_z, fo, w, h, dtx, dnt, outlet, skip, dl, open_top, open_bottom, dissolve);
     };
     if (outlet) descent(std::true_type(), std::false_type());
     else if (sharded) descent(std::false_type(), std::true_type());
     else descent(std::false_type(), std::false_type());
   });
   RD_LAUNCH("fill.stripe_offsets", k_stripe_offsets, dim3(1), dim3(64), 0, s, (const unsigned long long *)fo.counters, nstripes, pitoff,
-            dflags + 8);
+            dflags + 8, dflags + 6);
   RD_HIP(hipMemcpyAsync(hw, dflags + 4, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   RD_HIP(hipStreamSynchronize(s));
   g_stats.host_syncs++;
-  if (hw[1] != 0) { if (getenv("RDGPU_FILL_DEBUG")) fprintf(stderr, "fill_fused: node table overflow (nstripes %u rcap %u)\n", nstripes, fo.rcap); return false; }   // more nodes than a stripe's table holds: nothing was written to the DEM
-  const uint32_t B = hw[4], NNmax = hw[6];   // basins; nodes of the fullest stripe
-  g_stats.basins = B;
+  // more nodes than a stripe's table holds: nothing was written to the DEM.  The dissolved pits of a stripe count as the
+  // nodes they would have been (hw[2]), so which rasters take the compact path does not depend on the rule: a raster of
+  // nothing but such pits (a D4 checkerboard: every second cell) would fit with it and overflow without.
+  if (hw[1] != 0 || hw[2] > fo.rcap) { if (getenv("RDGPU_FILL_DEBUG")) fprintf(stderr, "fill_fused: node table overflow (nstripes %u rcap %u)\n", nstripes, fo.rcap); return false; }
+  const uint32_t B = hw[4], NNmax = hw[6];   // basins (rows of the tables); nodes of the fullest stripe
+  const uint32_t ndis = hw[7];               // pits the descent dissolved: no basins, each raised to its neighbour's key at least
+  g_stats.basins = (uint64_t)B + ndis;       // (the pits of the descent forest, as ever)
+  g_stats.dissolved_pits = ndis;
   if (sharded) {
     *keep = FillBuffers();
     keep->B = B;
     if (B == 0) { keep->trivial = true; return true; }   // no pits and no terminals: nothing to raise
   }
-  if (B == 0) return true;        // no pits: nothing to raise
+  if (B == 0 && ndis == 0) return true;        // no pits: nothing to raise
   const dim3 ngrid(cdiv(std::max(NNmax, 1u), NTHR), nstripes);
+  auto finalize = [&](const uint32_t *curN_, const uint32_t *acc_) {
+    // (no table of node levels on this path: the finalize takes a tile's levels from curN and acc as it stages them)
+    with_flag(vec, [&](auto V) {
+      RD_LAUNCH("fill.finalize", (k_finalize16<T, V>), dim3(listed ? lists->n[2] : xcd_grid(dnt)), dim3(NTHR), 0, s, d_z,
+                (const uint16_t *)fo.lab16, (const uint32_t *)nullptr, (const uint32_t *)fo.tile_base, (const uint32_t *)fo.tile_count, w,
+                h, dtx, dnt, skip, fl, curN_, acc_);
+    });
+  };
+  if (B == 0) {   // nothing but dissolved pits: every node is the outside's (level 0), the pits rise to their neighbours' keys
+    uint32_t *acc0 = ws.buf<uint32_t>("fill.acc", 1);
+    RD_HIP(hipMemsetAsync(acc0, 0, sizeof(uint32_t), s));
+    RD_LAUNCH("fill.resolve_nodes", k_resolve_nodes, ngrid, dim3(NTHR), 0, s, fo.G, (const unsigned long long *)fo.counters,
+              (const uint32_t *)pitoff, fo.rcap, (const uint16_t *)fo.lab16, (const uint32_t *)fo.tile_base, w, dtx, B, curN, dflags,
+              (const uint32_t *)nullptr, (const uint16_t *)fo.edgeS, (const uint16_t *)fo.edgeR);
+    g_stats.jump_passes = 1;
+    finalize(curN, acc0);
+    return true;
+  }
   uint32_t *tid = nullptr;
   if (sharded) {
     tid = alloc->get<uint32_t>("fill.tid", (size_t)B + 1);
@@ -3356,12 +3445,7 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
     return true;
   }
   if (listed && lists->n[2] == 0) return true;
-  // (no table of node levels on this path: the finalize takes a tile's levels from curN and acc as it stages them)
-  with_flag(vec, [&](auto V) {
-    RD_LAUNCH("fill.finalize", (k_finalize16<T, V>), dim3(listed ? lists->n[2] : xcd_grid(dnt)), dim3(NTHR), 0, s, d_z,
-              (const uint16_t *)fo.lab16, (const uint32_t *)nullptr, (const uint32_t *)fo.tile_base, (const uint32_t *)fo.tile_count, w,
-              h, dtx, dnt, skip, fl, (const uint32_t *)curN, (const uint32_t *)acc);
-  });
+  finalize((const uint32_t *)curN, (const uint32_t *)acc);
   return true;
 }
 

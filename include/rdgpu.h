@@ -963,6 +963,65 @@ RDGPU_DECL_HAND(f32, float)
 RDGPU_DECL_HAND(f64, double)
 #undef RDGPU_DECL_HAND
 
+/* ---- stream reaches on the D8 direction forest: reach labels, one record per reach, reach catchments ----
+ * No reference counterpart (TauDEM's StreamNet calls these links; rdgpu_d8_stream_links above keeps that name for its
+ * per-cell kinds).  Directions are uint8 D8 codes (0 NO_FLOW, 1..8, dir_nodata); chan is the optional uint8 mask of the
+ * stream-order block (NULL: every cell with dirs != dir_nodata is a channel cell).  CHANNEL CELL and CHANNEL CHILDREN are
+ * those of that block; the CHANNEL TARGET of a channel cell is the cell its code 1..8 points at, if that is a channel
+ * cell (else it has none).
+ *   A channel cell is a TOP iff it has 0 channel children (a head) or at least 2 (a junction).  A junction belongs to
+ *   the reach below it.  A channel cell with exactly one channel child belongs to the reach of that child.
+ *   A REACH is a top together with every cell that reaches it by walking up through only-children.
+ *   The BOTTOM of a reach is its cell whose channel target does not exist (a mouth) or is a junction.  Every bottom has
+ *   exactly one top.  A channel cell on a direction loop that no channel tributary joins has no top and belongs to NO
+ *   reach.  A loop that a tributary joins is an ordinary reach from that junction round to the cell before it; its
+ *   `down` is then its own label or that of another loop reach.  Nothing is special-cased for loops.
+ *   NUMBERING: reaches are labelled 1..N by ascending raster index y * width + x of their bottom cell, independent of
+ *   any execution order.  0 means "none".
+ *   The CATCHMENT of a cell c with dirs != dir_nodata: follow the path of c (the path of the upslope block, over the
+ *   full directions, c included) to its first channel cell; the catchment is that cell's reach label.  It is 0 when the
+ *   path ends or enters a loop before meeting a channel cell, when that channel cell has no reach, and on NoData cells.
+ *   On a channel cell, catchment equals reach.  Equivalently -- the engine's route -- it is the label of the first
+ *   reach-bottom on c's path: to_cell of rdgpu_d8_flow_path with the bottoms as chan.
+ * Outputs, each nullable except count:
+ *   reach      uint32  the label of the reach a channel cell belongs to, 0 elsewhere.
+ *   catchment  uint32  as defined above.
+ *   table      the first min(N, capacity) records by label (table[i] describes label i + 1); records past N are not
+ *              touched.  table == NULL with capacity == 0 is the sizing call.
+ *   count      always the true N.  A call with only count is valid.
+ * Every requested plane is written on every cell; inputs are never written.  Every field is an integer count or a
+ * function of integer counts: exact, and identical from run to run.
+ * A null dirs or count, a null table with a non-zero capacity, a non-positive size or more than 0xFFFF0000 cells, cell
+ * lengths that are zero or not finite (their sign is ignored) return RDGPU_ERR_ARG before any device work; nothing is
+ * written then.  The _dev form takes device pointers (d_count included) and is ordered on hip_stream without
+ * synchronising it.  Scratch comes from the workspace pool: 3 bytes per cell (bottom mask, cell class, rank of a bottom
+ * in its block of 256 cells), the flow-path engine's 2.5, and 4 more when neither label plane is requested while the
+ * table is (the drainage cells live in a requested plane otherwise). */
+typedef struct rdgpu_reach {
+  uint32_t top_cell;        /* its head or junction */
+  uint32_t bottom_cell;
+  uint32_t down;            /* label of the reach its bottom's channel target belongs to; 0 at a mouth */
+  uint32_t up;              /* channel children of top_cell: 0 head, 2..8 junction; == number of reaches whose down is
+                               this label */
+  uint32_t cells;           /* channel cells in the reach */
+  uint32_t catchment_cells; /* cells whose catchment is this label, channel cells included */
+  uint32_t steps[3];        /* cells of the reach that have a channel target, by the kind of that step: x (codes 1, 5),
+                               y (3, 7), diagonal; the bottom's step into the junction it joins counts, a mouth's does
+                               not exist */
+  uint32_t order;           /* order[top_cell] if an order raster is given (it is constant along a reach), else 0; not
+                               checked */
+  double length;            /* steps as a length, evaluated as rdgpu_d8_flow_path's dist is (a rounding after every
+                               product and every sum, diag once on the host) */
+} rdgpu_reach;              /* 48 bytes, no implicit padding */
+int rdgpu_d8_stream_reaches(const uint8_t *dirs, uint8_t dir_nodata, int width, int height, const uint8_t *chan /* nullable */,
+                            const uint8_t *order /* nullable */, double cell_x, double cell_y, uint32_t *reach /* nullable */,
+                            uint32_t *catchment /* nullable */, rdgpu_reach *table /* nullable */, uint32_t capacity,
+                            uint32_t *count);
+int rdgpu_d8_stream_reaches_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int width, int height,
+                                const uint8_t *d_chan /* nullable */, const uint8_t *d_order /* nullable */, double cell_x,
+                                double cell_y, uint32_t *d_reach /* nullable */, uint32_t *d_catchment /* nullable */,
+                                rdgpu_reach *d_table /* nullable */, uint32_t capacity, uint32_t *d_count, void *hip_stream);
+
 /* ---- longest upstream flow path on the D8 direction forest -------------------------------------
  * No reference counterpart (TauDEM's plen, WhiteboxTools' MaxUpslopeFlowpathLength and LongestFlowpath).  Directions are
  * uint8 D8 codes (0 NO_FLOW, 1..8, dir_nodata).

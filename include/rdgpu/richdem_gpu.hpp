@@ -836,6 +836,40 @@ void d8_hand(const E &dem, const F &flowdirs, G &hand) {
   d8_hand(dem, flowdirs, hand, static_cast<const F *>(nullptr));
 }
 
+// ---- stream reaches on the D8 forest (no reference counterpart; the definitions are in rdgpu.h) ----------------------
+// reach <- the label 1..N of every channel cell's reach (0 elsewhere), catchment <- the label of the reach every cell
+// drains through (0: none), table[i] <- the record of label i + 1.  channels and order are optional (nullptr: every cell
+// with a direction is a channel cell; no order in the records).  The cell lengths are the directions' |geotransform[1]|,
+// |geotransform[5]|; the outputs take the directions' size, geotransform and projection, NoData 0.  Two calls of the
+// engine: the sizing call, then the one that fills everything.
+template <class F, class C, class O, class R>
+void d8_stream_reaches(const F &flowdirs, const C *channels, const O *order, R &reach, R &catchment, std::vector<rdgpu_reach> &table) {
+  static_assert(std::is_same<detail::elem_t<const F>, uint8_t>::value || std::is_same<detail::elem_t<F>, uint8_t>::value,
+                "d8_stream_reaches: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<detail::elem_t<R>, uint32_t>::value, "d8_stream_reaches: the label rasters must be uint32_t");
+  const char *fn = "d8_stream_reaches";
+  double cx, cy;
+  detail::cell_lengths(flowdirs, fn, cx, cy);
+  const uint8_t *mask = detail::path_mask(flowdirs, channels, fn);
+  if (order && (order->width() != flowdirs.width() || order->height() != flowdirs.height()))
+    throw std::runtime_error(std::string(fn) + ": the order raster must have the directions' size");
+  const uint8_t *ord = order ? order->data() : nullptr;
+  reach.resize(flowdirs);
+  reach.setNoData(0);
+  catchment.resize(flowdirs);
+  catchment.setNoData(0);
+  table.clear();
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  uint32_t n = 0;
+  detail::check(rdgpu_d8_stream_reaches(flowdirs.data(), flowdirs.noData(), flowdirs.width(), flowdirs.height(), mask, ord, cx, cy,
+                                        nullptr, nullptr, nullptr, 0, &n), fn);
+  table.resize(n);
+  uint32_t got = 0;
+  detail::check(rdgpu_d8_stream_reaches(flowdirs.data(), flowdirs.noData(), flowdirs.width(), flowdirs.height(), mask, ord, cx, cy,
+                                        reach.data(), catchment.data(), n ? table.data() : nullptr, n, &got), fn);
+  if (got != n) throw std::runtime_error(std::string(fn) + ": the count changed between the two calls");
+}
+
 // ---- distance and drop DOWN to the stop cells over D-infinity / MFD proportions (no reference counterpart; the
 // definition is in rdgpu.h) ---------------------------------------------------------------------------------------------
 enum class DistanceStat { Average = 0, Minimum = 1, Maximum = 2 };

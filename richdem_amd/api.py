@@ -1273,6 +1273,81 @@ def d8_hand_dev(dem, dirs, dem_nodata, out, dir_nodata: int = 255, channels=None
                                                    ctypes.c_double(out_nodata), _stream_ptr()), "rdgpu_d8_hand_dev")
 
 
+# ---- stream reaches: reach labels, per-reach table, reach catchments (csrc/reaches.hip) ----------
+REACH_DTYPE = np.dtype([("top_cell", np.uint32), ("bottom_cell", np.uint32), ("down", np.uint32), ("up", np.uint32),
+                        ("cells", np.uint32), ("catchment_cells", np.uint32), ("steps", np.uint32, (3,)), ("order", np.uint32),
+                        ("length", np.float64)])   # rdgpu_reach
+_REACH_WANT = ("reach", "catchment", "table")
+
+
+def d8_stream_reaches(dirs: np.ndarray, dir_nodata: int = 255, channels: np.ndarray | None = None, order: np.ndarray | None = None,
+                      cell=(1.0, 1.0), want=_REACH_WANT) -> dict:
+    """The reaches of the channel network -- the stretches between heads and junctions -- (include/rdgpu.h states the
+    definitions): a dict with "count" (N) and what `want` names of "reach" (uint32: the label 1..N of a channel cell's
+    reach, 0 elsewhere), "catchment" (uint32: the label of the reach a cell drains through, 0 for none) and "table"
+    (``REACH_DTYPE`` [N]; ``table[i]`` describes label ``i + 1``).  Labels ascend with the raster index of the reach's
+    bottom cell.  channels=None: every cell with a direction is a channel cell; order: an optional uint8 stream-order raster
+    copied into the records.  With "table": two calls, the sizing call (no raster pass beyond the classification), then
+    the one that fills it."""
+    who = "d8_stream_reaches"
+    dirs = _dirs2d(dirs, who)
+    chan = _mask2d(channels, dirs.shape, who)
+    if order is not None and (not isinstance(order, np.ndarray) or order.dtype != np.uint8 or order.shape != dirs.shape):
+        raise RdgpuError(f"{who}: the order raster is a uint8 array of the directions' shape")
+    order = None if order is None else np.ascontiguousarray(order)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if any(k not in _REACH_WANT for k in want):
+        raise RdgpuError(f"{who}: want names some of {_REACH_WANT}")
+    cx, cy = _cell2(cell, who)
+    h, w = dirs.shape
+    count = ctypes.c_uint32(0)
+
+    def call(reach, catchment, table):
+        check(lib().rdgpu_d8_stream_reaches(_ptr(dirs), ctypes.c_uint8(dir_nodata), w, h, _ptr(chan), _ptr(order), cx, cy, _ptr(reach),
+                                            _ptr(catchment), None if table is None or len(table) == 0 else _ptr(table),
+                                            ctypes.c_uint32(0 if table is None else len(table)), ctypes.byref(count)),
+              "rdgpu_d8_stream_reaches")
+        return int(count.value)
+
+    out = {}
+    if "table" in want:
+        out["table"] = np.zeros(call(None, None, None), REACH_DTYPE)
+    if "reach" in want:
+        out["reach"] = np.empty((h, w), np.uint32)
+    if "catchment" in want:
+        out["catchment"] = np.empty((h, w), np.uint32)
+    n = out["count"] = call(out.get("reach"), out.get("catchment"), out.get("table"))
+    if "table" in want and n != len(out["table"]):
+        raise RdgpuError(f"{who}: the count changed between the two calls ({len(out['table'])} -> {n})")
+    return out
+
+
+def d8_stream_reaches_dev(dirs, dir_nodata: int = 255, channels=None, order=None, cell=(1.0, 1.0), reach=None, catchment=None,
+                          table=None):
+    """The same on HBM-resident tensors, on torch's current stream and without synchronising it: dirs, channels and order
+    uint8 CUDA tensors; reach and catchment int32 CUDA tensors [h, w] holding the uint32 labels bit for bit, or ``None``;
+    table a contiguous CUDA tensor of any element type holding 48 bytes per record (its capacity is its size in bytes
+    // 48; ``.cpu().numpy().view(REACH_DTYPE)`` reads it) or ``None``.  Returns a one-element int32 CUDA tensor that holds
+    the number of reaches once the stream gets there."""
+    import torch
+
+    who = "d8_stream_reaches_dev"
+    h, w = _dev2d(dirs, who, torch.uint8)
+    cx, cy = _cell2(cell, who)
+    cap = 0
+    if table is not None:
+        if not (table.is_cuda and table.is_contiguous()):
+            raise RdgpuError(f"{who}: expected a contiguous table tensor on the GPU")
+        cap = table.numel() * table.element_size() // REACH_DTYPE.itemsize
+    count = torch.zeros(1, dtype=torch.int32, device=dirs.device)
+    check(lib().rdgpu_d8_stream_reaches_dev(ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata), w, h,
+                                            _dev_mask(channels, (h, w), who), _dev_mask(order, (h, w), who), cx, cy,
+                                            _dev_plane(reach, (h, w), torch.int32, who), _dev_plane(catchment, (h, w), torch.int32, who),
+                                            None if cap == 0 else ctypes.c_void_p(table.data_ptr()), ctypes.c_uint32(cap),
+                                            ctypes.c_void_p(count.data_ptr()), _stream_ptr()), "rdgpu_d8_stream_reaches_dev")
+    return count
+
+
 # ---- depression inventory: labels and one record per depression of the fill -------------------------------------
 DEPRESSION_DTYPE = np.dtype([("first_cell", np.uint32), ("pit_cell", np.uint32), ("outlet_cell", np.uint32), ("cells", np.uint32),
                              ("level", np.float64), ("pit_elevation", np.float64), ("volume", np.float64)])   # rdgpu_depression

@@ -284,7 +284,12 @@ RDGPU_DECL_WS(u64, uint64_t)
  *                              full-width launches; a huge value: from round 2 on
  *   RDGPU_FILL_DISSOLVE=0      every pit of the descent forest is a basin (default: a pit whose lowest neighbour lies in its
  *                              64 x 64 tile and drains elsewhere joins that neighbour's tree and is raised on its own;
- *                              rdgpu_fill_stats::dissolved_pits) */
+ *                              rdgpu_fill_stats::dissolved_pits)
+ *   RDGPU_FILL_FLOODED=0       the finalize reads every tile (default: a 64 x 64 tile whose node levels are one level
+ *                              strictly above the tile's largest key -- a tile wholly under one lake -- is written at
+ *                              that level without its elevations or labels being read)
+ *   RDGPU_FILL_COUNT_FLOODED=1 the finalize counts the tiles it writes that way, one atomic add each, for
+ *                              rdgpu_fill_flooded_tiles (default: no counter, no atomics) */
 /* Statistics of the last fill on this process (for DESIGN.md / bench.py reporting). */
 typedef struct rdgpu_fill_stats {
   uint64_t cells;       /* width*height                                   */
@@ -300,6 +305,10 @@ typedef struct rdgpu_fill_stats {
                               shards, the fills with outlets and the classic path); this word was `reserved` */
 } rdgpu_fill_stats;
 int rdgpu_fill_get_stats(rdgpu_fill_stats *out);
+/* Tiles the last plain fill of the calling thread wrote without reading them.  Counted only under
+ * RDGPU_FILL_COUNT_FLOODED=1 (else 0, as after a fill with outlets, a shard or RDGPU_FILL_FLOODED=0).  The fill itself
+ * does not wait for the count: this call synchronises with the fill's stream. */
+int rdgpu_fill_flooded_tiles(uint64_t *out);
 
 /* ---- row-block shards: the tile protocol of programs/parallel_priority_flood over GPUs ---------
  * Mirrors the reference's tiled Priority-Flood (Barnes 2016; programs/parallel_priority_flood/main.cpp:

@@ -81,6 +81,14 @@ def fill_stats() -> dict:
             "host_syncs": st.host_syncs, "dissolved_pits": st.dissolved_pits}
 
 
+def fill_flooded_tiles() -> int:
+    """64 x 64 tiles the last plain fill wrote without reading them; counted only under RDGPU_FILL_COUNT_FLOODED=1
+    (else 0).  Waits for the fill's stream."""
+    n = ctypes.c_uint64(0)
+    check(lib().rdgpu_fill_flooded_tiles(ctypes.byref(n)), "rdgpu_fill_flooded_tiles")
+    return int(n.value)
+
+
 def profile_enable(on: bool = True) -> None:
     lib().rdgpu_profile_enable(1 if on else 0)
 

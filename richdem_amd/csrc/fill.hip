@@ -2085,6 +2085,19 @@ __global__ __launch_bounds__(64) void k_stripe_offsets(const unsigned long long 
   if (s == 63) { out[0] = incl; out[1] = tot; out[2] = mx; out[3] = dis; *forest_max = mxd; }
 }
 
+// maximum / minimum over the 64 lanes, in every lane: a DPP prefix scan (row shifts, then row broadcasts) whose last lane
+// holds the result -- six VALU instructions and a v_readlane
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false));   // row_shr:1 (0: the identity)
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false));   // row_shr:2
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false));   // row_shr:4
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false));   // row_shr:8
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));   // row_bcast:15 -> rows 1, 3
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2, 3
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return ~wave_max_u32(~v); }
+
 // OUTLETS: cells flagged in `outlet` drain like the raster's border cells (interior outlets: the restricted fills of
 // pfdirs.hip); the instantiation of the plain fill does not look at the pointer.
 // There, all outlets of a tile share ONE node (slot 0: a tile of walls has thousands of them), node 0 of the table is a
@@ -2097,13 +2110,18 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
                                                     uint32_t tilesX, uint32_t ntiles, const uint8_t *__restrict__ outlet = nullptr,
                                                     const uint8_t *__restrict__ skip = nullptr,
                                                     const uint32_t *__restrict__ tlist = nullptr, int open_top = 0,
-                                                    int open_bottom = 0, int dissolve = 0) {
+                                                    int open_bottom = 0, int dissolve = 0,
+                                                    uint32_t *__restrict__ tile_max = nullptr) {
   // tlist (optional, with OUTLETS): the tiles to work on, one block each (ntiles = the raster's tiles all the same)
   // dissolve (block-uniform; the plain fill only): a pit whose lowest neighbour q lies in the tile and does not drain
   // into it is no basin of its own -- it points at q, and its label carries q's direction for the finalize
+  // tile_max (optional; the plain fill only): tile_max[t] = the largest key among the tile's cells, for the finalize's
+  // flooded-tile test (k_finalize16).  0xFFFFFFFF for a tile that is not interior: it holds a border cell, which is never
+  // raised, or cells outside the raster -- such a tile never passes the test.
   constexpr bool DIS_OK = !OUTLETS && !CUT;
   const bool dis = DIS_OK && dissolve != 0;
   __shared__ uint32_t dcnt;
+  __shared__ uint32_t wkmax[NTHR / 64];
   __shared__ uint32_t sk[DLH * DLW];
   // rows of LPD = 66 entries: with 64 two-byte entries every row starts on the same LDS bank and the jumps' gathers --
   // neighbouring columns of different rows -- collide (29 % of the kernel's LDS cycles, r03e)
@@ -2206,6 +2224,7 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
   // from a copy of the words in scratch memory.)
   uint32_t codesLo = 0, codesHi = 0;
   uint32_t rootmask = 0, pitmask = 0, outmask = 0;
+  uint32_t kmax = 0;   // the largest key of the thread's cells (interior tiles with tile_max: the keys are live only here)
   {
     // packed word of a candidate: [15:0] byte delta + 134, [19:16] exit code, [26:24] column 0 / 1 / 2, [27] row above, [29] row below
     constexpr uint32_t WT0 = 0u | (1u << 16) | (1u << 24) | (1u << 27), WT1 = 2u | (2u << 16) | (1u << 25) | (1u << 27),
@@ -2239,6 +2258,7 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
       uint32_t ba, bb, bc, bm, bW;
       triple(ly + 2, ba, bb, bc, bm, bW);
       const uint32_t kc = mb;
+      if (DIS_OK && INNER) kmax = max(kmax, kc);
       const bool midfirst = ma <= mc;
       const uint32_t mm = midfirst ? ma : mc;
       const uint32_t bk = min(min(tm, mm), bm);
@@ -2291,6 +2311,10 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
   if (fo.edgeK && threadIdx.x < 2 * DH) {
     const int side = threadIdx.x >> 6, lye = threadIdx.x & (DH - 1), lxe = side ? DW - 1 : 0;
     fo.edgeK[((size_t)t * 2 + side) * DH + lye] = sk[(lye + 1) * DLW + lxe + 1];
+  }
+  if (DIS_OK && tile_max) {   // (block-uniform) one reduction per wavefront; thread 0 stores the tile's word with its bases
+    const uint32_t wm = wave_max_u32(kmax);
+    if ((threadIdx.x & 63) == 0) wkmax[wave_s] = wm;
   }
   __syncthreads();
   auto code_of = [codesLo, codesHi](int j) -> int {   // row j's code (j varies per lane)
@@ -2384,6 +2408,7 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
     rbase = st * fo.rcap + rl;
     fo.tile_base[t] = rbase;
     fo.tile_count[t] = nr;
+    if (DIS_OK && tile_max) tile_max[t] = inner ? max(max(wkmax[0], wkmax[1]), max(wkmax[2], wkmax[3])) : 0xFFFFFFFFu;
     fits_s = (unsigned long long)rl + nr <= fo.rcap ? 1u : 0u;
     if (!fits_s) *fo.overflow = 1;
     // the dissolved pits of the stripe: the second word of the stripe's line (a statistic: nothing waits for it)
@@ -2636,39 +2661,91 @@ __global__ __launch_bounds__(NTHR) void k_node_levels(const uint32_t *__restrict
 // 16-bit labels in quads; a quad is written back only when one of its cells is raised.
 // curN / acc (optional, both or none; lvl is not read then): the kernel forms the levels itself, level of a node = acc[its
 // basin], while it stages them -- the table pass that wrote lvl[] for this one reader (k_node_levels) is not needed.
-template <class T, bool VEC>
+// FLOOD (the plain fill, with curN / acc and tile_max): a tile wholly under one lake is written without being
+// read.  The block stages its levels FIRST and reduces their minimum and maximum; when all are one level L and L lies
+// strictly above tile_max[t], the tile's largest key (k_descent16), every cell of the tile comes out at L whatever it
+// holds -- max(key, L) = L, a dissolved pit's max(key(q), L) = L as well, q being a cell of the tile -- so neither z nor
+// lab16 is loaded.  Strictly: a cell AT the level keeps its bits today (-0.0 under a lake at +0.0).  Such a tile lies
+// inside the raster (tile_max is 0xFFFFFFFF elsewhere).  Every other tile loads its quads after the decision and goes on
+// as ever.  flooded (optional): counts the tiles written that way, for rdgpu_fill_flooded_tiles.
+template <class T, bool VEC, bool FLOOD = false>
 __global__ __launch_bounds__(NTHR) void k_finalize16(T *z, const uint16_t *__restrict__ lab16, const uint32_t *__restrict__ lvl,
                                                      const uint32_t *__restrict__ tile_base, const uint32_t *__restrict__ tile_count,
                                                      int w, int h, uint32_t tilesX, uint32_t ntiles,
                                                      const uint8_t *__restrict__ skip = nullptr,
                                                      const uint32_t *__restrict__ tlist = nullptr,
                                                      const uint32_t *__restrict__ curN = nullptr,
-                                                     const uint32_t *__restrict__ acc = nullptr) {
+                                                     const uint32_t *__restrict__ acc = nullptr,
+                                                     const uint32_t *__restrict__ tile_max = nullptr,
+                                                     unsigned long long *flooded = nullptr) {
   __shared__ uint32_t sl[DH * DW];
+  __shared__ uint32_t wlo[NTHR / 64], whi[NTHR / 64];
   const uint32_t t = tlist ? tlist[blockIdx.x] : xcd_tile(blockIdx.x, ntiles);
   if (t >= ntiles) return;
   if (skip && skip[t]) return;
   const int x0 = (int)(t % tilesX) * DW, y0 = (int)(t / tilesX) * DH;
   const int qx = threadIdx.x & 15, ry = threadIdx.x >> 4;   // 16 quads per row, rows ry, ry + 16, ry + 32, ry + 48
   const int gx = x0 + 4 * qx;
-  // the thread's quads first (in flight while the node levels arrive), then the tile's levels into LDS
   Quad<T> zqs[DH / 16];
   Quad<uint16_t> lqs[DH / 16];
+  auto load_quads = [&]() {
 #pragma unroll
-  for (int r = 0; r < DH / 16; r++) {
-    const int gy = y0 + ry + 16 * r;
-    const bool in = gx < w && gy < h;
-    const size_t g = in ? (size_t)gy * w + gx : 0;
-    zqs[r] = load_quad<T, VEC>(z + (g - (in ? gx : 0)), in ? gx : 0, w, T());
-    lqs[r] = load_quad<uint16_t, VEC>(lab16 + (g - (in ? gx : 0)), in ? gx : 0, w, (uint16_t)0);
-  }
-  const uint32_t base = tile_base[t], cnt = tile_count[t];
-  if (curN) {
-    for (uint32_t i = threadIdx.x; i < cnt; i += NTHR) sl[i] = acc[curN[base + i] & ~CLOSED];
+    for (int r = 0; r < DH / 16; r++) {
+      const int gy = y0 + ry + 16 * r;
+      const bool in = gx < w && gy < h;
+      const size_t g = in ? (size_t)gy * w + gx : 0;
+      zqs[r] = load_quad<T, VEC>(z + (g - (in ? gx : 0)), in ? gx : 0, w, T());
+      lqs[r] = load_quad<uint16_t, VEC>(lab16 + (g - (in ? gx : 0)), in ? gx : 0, w, (uint16_t)0);
+    }
+  };
+  if (FLOOD) {
+    // the tile's three words, then the two gathers, with nothing in between: every other tile's quads wait for this chain
+    const uint32_t base = tile_base[t], cnt = tile_count[t], kmax = tile_max[t];
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    for (uint32_t i = threadIdx.x; i < cnt; i += NTHR) {
+      const uint32_t L = acc[curN[base + i] & ~CLOSED];
+      sl[i] = L;
+      lo = min(lo, L);
+      hi = max(hi, L);
+    }
+    lo = wave_min_u32(lo);
+    hi = wave_max_u32(hi);
+    if ((threadIdx.x & 63) == 0) { wlo[threadIdx.x >> 6] = lo; whi[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    lo = min(min(wlo[0], wlo[1]), min(wlo[2], wlo[3]));
+    hi = max(max(whi[0], whi[1]), max(whi[2], whi[3]));
+    // (block-uniform.  lo == hi is a guard: above the tile's largest key the levels can only be one lake's)
+    if (lo == hi && lo > kmax) {
+      const T v = Key32<T>::from(lo);
+#pragma unroll
+      for (int r = 0; r < DH / 16; r++) {
+        const size_t g = (size_t)(y0 + ry + 16 * r) * w + gx;   // (an interior tile: every quad lies in the raster)
+        if (VEC) {
+          struct alignas(4 * sizeof(T)) AQ { T v[4]; };
+          AQ a;
+#pragma unroll
+          for (int e = 0; e < 4; e++) a.v[e] = v;
+          *reinterpret_cast<AQ *>(z + g) = a;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; e++) z[g + e] = v;
+        }
+      }
+      if (flooded && threadIdx.x == 0) atomicAdd(flooded, 1ull);
+      return;
+    }
+    load_quads();
   } else {
-    for (uint32_t i = threadIdx.x; i < cnt; i += NTHR) sl[i] = lvl[base + i];
+    // the thread's quads first (in flight while the node levels arrive), then the tile's levels into LDS
+    load_quads();
+    const uint32_t base = tile_base[t], cnt = tile_count[t];
+    if (curN) {
+      for (uint32_t i = threadIdx.x; i < cnt; i += NTHR) sl[i] = acc[curN[base + i] & ~CLOSED];
+    } else {
+      for (uint32_t i = threadIdx.x; i < cnt; i += NTHR) sl[i] = lvl[base + i];
+    }
+    __syncthreads();
   }
-  __syncthreads();
 #pragma unroll
   for (int r = 0; r < DH / 16; r++) {
     const int gy = y0 + ry + 16 * r;
@@ -3098,6 +3175,13 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
   if (threadIdx.x == 0) eo.segcount[seg] = min(seg_fill, eo.seglimit);
 }
 
+// tiles the last plain fill of this thread wrote without reading them (RDGPU_FILL_COUNT_FLOODED=1; else 0): the finalize's
+// counter, copied to pinned memory behind the kernel and read once its stream got there
+static thread_local unsigned long long *g_fl_pinned = nullptr;
+static thread_local unsigned long long g_fl_count = 0;
+static thread_local bool g_fl_pending = false;
+static thread_local hipStream_t g_fl_stream = nullptr;
+
 // f(std::true_type()) or f(std::false_type()): a runtime flag becomes a template argument of the launches in f
 template <class F>
 static void with_flag(bool b, F &&f) {
@@ -3148,6 +3232,8 @@ template <class T, int TOPO>
 static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outlet = nullptr, const uint8_t *skip = nullptr,
                        const SparseLists *lists = nullptr, FillBuffers *keep = nullptr, BufAlloc *alloc = nullptr,
                        int open_top = 0, int open_bottom = 0) {
+  g_fl_pending = false;
+  g_fl_count = 0;
   const char *env_edges = getenv("RDGPU_FILL_EDGES");
   if (env_edges && env_edges[0] == '0') return false;   // (the raster-round fallback lives in the classic path)
   const uint64_t n64 = (uint64_t)w * (uint64_t)h;
@@ -3201,11 +3287,22 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   // RDGPU_FILL_DISSOLVE=0: every pit of the descent forest stays a basin (the plain fill; shards and outlets never dissolve)
   const char *env_dis = getenv("RDGPU_FILL_DISSOLVE");
   const int dissolve = (!outlet && !sharded && !(env_dis && env_dis[0] == '0')) ? 1 : 0;
+  // RDGPU_FILL_FLOODED=0: the finalize reads every tile (the plain fill; shards and outlets always do).  Else the descent
+  // leaves every tile's largest key and the finalize writes the tiles wholly under one lake without reading them.
+  const char *env_fl = getenv("RDGPU_FILL_FLOODED"), *env_flc = getenv("RDGPU_FILL_COUNT_FLOODED");
+  uint32_t *tile_max = nullptr;
+  if (!outlet && !sharded && !(env_fl && env_fl[0] == '0')) tile_max = ws.buf<uint32_t>("fused.tile_max", dnt);
+  // RDGPU_FILL_COUNT_FLOODED=1: the finalize counts those tiles (rdgpu_fill_flooded_tiles; else no atomics on the path)
+  unsigned long long *flooded = nullptr;
+  if (!outlet && !sharded && env_flc && env_flc[0] == '1') {
+    flooded = ws.buf<unsigned long long>("fused.flooded", 1);
+    RD_HIP(hipMemsetAsync(flooded, 0, sizeof(unsigned long long), s));
+  }
   // (outlets never come with a cut; the kernel reads outlet, skip and dl only with OUTLETS, the cut rows only with CUT)
   with_flag(vec, [&](auto V) {
     auto descent = [&](auto OUTLETS, auto CUT) {
       RD_LAUNCH("fill.descent", (k_descent16<T, TOPO, V, OUTLETS, CUT>), dim3(listed ? lists->n[0] : xcd_grid(dnt)), dim3(NTHR), 0, s,
-                (const T *)d_z, fo, w, h, dtx, dnt, outlet, skip, dl, open_top, open_bottom, dissolve);
+                (const T *)d_z, fo, w, h, dtx, dnt, outlet, skip, dl, open_top, open_bottom, dissolve, tile_max);
     };
     if (outlet) descent(std::true_type(), std::false_type());
     else if (sharded) descent(std::false_type(), std::true_type());
@@ -3234,10 +3331,21 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   auto finalize = [&](const uint32_t *curN_, const uint32_t *acc_) {
     // (no table of node levels on this path: the finalize takes a tile's levels from curN and acc as it stages them)
     with_flag(vec, [&](auto V) {
-      RD_LAUNCH("fill.finalize", (k_finalize16<T, V>), dim3(listed ? lists->n[2] : xcd_grid(dnt)), dim3(NTHR), 0, s, d_z,
-                (const uint16_t *)fo.lab16, (const uint32_t *)nullptr, (const uint32_t *)fo.tile_base, (const uint32_t *)fo.tile_count, w,
-                h, dtx, dnt, skip, fl, curN_, acc_);
+      if (tile_max)
+        RD_LAUNCH("fill.finalize", (k_finalize16<T, V, true>), dim3(xcd_grid(dnt)), dim3(NTHR), 0, s, d_z, (const uint16_t *)fo.lab16,
+                  (const uint32_t *)nullptr, (const uint32_t *)fo.tile_base, (const uint32_t *)fo.tile_count, w, h, dtx, dnt,
+                  (const uint8_t *)nullptr, (const uint32_t *)nullptr, curN_, acc_, (const uint32_t *)tile_max, flooded);
+      else
+        RD_LAUNCH("fill.finalize", (k_finalize16<T, V>), dim3(listed ? lists->n[2] : xcd_grid(dnt)), dim3(NTHR), 0, s, d_z,
+                  (const uint16_t *)fo.lab16, (const uint32_t *)nullptr, (const uint32_t *)fo.tile_base, (const uint32_t *)fo.tile_count, w,
+                  h, dtx, dnt, skip, fl, curN_, acc_);
     });
+    if (flooded) {   // the count goes home behind the finalize; rdgpu_fill_flooded_tiles waits for it, the fill does not
+      if (!g_fl_pinned) RD_HIP(hipHostMalloc((void **)&g_fl_pinned, sizeof(unsigned long long)));
+      RD_HIP(hipMemcpyAsync(g_fl_pinned, flooded, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+      g_fl_pending = true;
+      g_fl_stream = s;
+    }
   };
   if (B == 0) {   // nothing but dissolved pits: every node is the outside's (level 0), the pits rise to their neighbours' keys
     uint32_t *acc0 = ws.buf<uint32_t>("fill.acc", 1);
@@ -4007,6 +4115,17 @@ extern "C" int rdgpu_fill_max_dep_get_stats(rdgpu_max_dep_stats *out) {
     g_md_pending = false;
   }
   *out = g_md_stats;
+  return RDGPU_OK;
+}
+
+extern "C" int rdgpu_fill_flooded_tiles(uint64_t *out) {
+  if (!out) return RDGPU_ERR_ARG;
+  if (g_fl_pending) {
+    if (hipStreamSynchronize(g_fl_stream) != hipSuccess) { set_last_error("rdgpu_fill_flooded_tiles: hipStreamSynchronize failed"); return RDGPU_ERR_HIP; }
+    g_fl_count = *g_fl_pinned;
+    g_fl_pending = false;
+  }
+  *out = g_fl_count;
   return RDGPU_OK;
 }
 

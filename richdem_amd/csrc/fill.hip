@@ -31,6 +31,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <numeric>
 #include <vector>
 
 struct rdgpu_fill_shard;
@@ -2794,17 +2795,29 @@ __global__ __launch_bounds__(NTHR) void k_finalize16(T *z, const uint16_t *__res
 // per XCD); the NEXT tile's rows, labels, ring cells and the node table of its descent tile are loaded into registers
 // while the current tile goes through its LDS phases, so the phases of successive tiles follow each other without the
 // round trips in between.  The components of the tile's own cells come from the descent
-// tile's node table staged in LDS (one coalesced read of its ~80 entries instead of 2 048 gathers); only the 196 cells
+// tile's node table staged in LDS (one coalesced read of its ~80 entries instead of 2 048 gathers); only the 129 cells
 // of the ring, which belong to the neighbouring descent tiles, are gathered one by one.  Phases, tables, records and
 // proposals are k_scan<EMIT>'s.
 // ==========================================================================================================
-constexpr int NT_CAP = 1024;   // node-table entries of one descent tile held in LDS (more: gathered from HBM)
-static_assert(NT_CAP * 4 <= TW * TH * 2, "the node table lives in the boundary list's storage");
+constexpr int NT_CAP = 512;   // node-table entries of one descent tile held in LDS (more: gathered from HBM)
+static_assert(NT_CAP * 4 <= PT_SLOTS * 8, "the node table lives in the pair table's storage");
+static_assert(NT_CAP % NTHR == 0, "a thread stages NT_CAP / NTHR entries");
+// Boundary cells the list holds.  A tile with more (block-uniform: the wavefronts' counts summed in LDS) is worked one
+// band of TH / 4 rows at a time, list -> barrier -> pair loop per band, the pair table accumulating across the bands.
+// 1 008 and not 1 024: with the four words below the kernel's LDS is 22 528 bytes, seven blocks to a CU.
+constexpr int LIST_CAP = 1008;
+static_assert(LIST_CAP >= TW * (TH / 4), "a band's boundary cells fit the list");
+static_assert(LIST_CAP >= PT_SLOTS, "the list holds the occupied slots of the pair table afterwards");
+static_assert(2 * (TH + 1) * LW * 4 + LIST_CAP * 2 + PT_SLOTS * 12 + 16 <= 22528, "k_pairs16: LDS of seven blocks per CU");
 static_assert(TW == DW && DH % TH == 0, "a scan tile lies inside one descent tile");
 constexpr uint32_t NO_TILE = 0xFFFFFFFFu;
 // a 16-bit label's slot: the plain fill's descent flags a dissolved pit in the four bits above it, for the finalize alone
 constexpr uint32_t LAB16_SLOT = (uint32_t)(DW * DH - 1);
-constexpr int RING = 2 * LW + 2 * TH;   // ring cells of a tile: two rows of LW, two columns of TH
+// The pair pass looks E, SE, S and SW only: of the halo around a tile it reads the row below, the column to the right and
+// the left column from the tile's second row down -- never the row above (the tile above finds those pairs) or the cell to
+// the left of the first row.  Those cells are neither loaded nor staged, and the LDS images start at the tile's first row.
+constexpr int PLH = TH + 1;                    // LDS rows of the pair pass: the tile's and the ring row below
+constexpr int RING = LW + TH + (TH - 1);       // ring cells: the row below, the right column, the left column from row 2
 
 // A pair that found no slot in the tile's table goes straight to the BLOCK's segment (k_pairs16: one segment per
 // resident block, filled through a counter in LDS) and proposes on its own.
@@ -2822,8 +2835,19 @@ __device__ __forceinline__ void pair_spill_local(const EdgeOut &eo, unsigned lon
   }
 }
 
+#ifdef RDGPU_PROBES
+// tools/probes/pairs_residency.py: wall_clock64() of every block of the k_pairs16 launches at entry [2 b] and at exit
+// [2 b + 1] -- all blocks of a grid of resident blocks have entered before the first one leaves
+__device__ unsigned long long *g_probe_pairs_clock = nullptr;
+extern "C" int rdgpu_probe_pairs_clock(unsigned long long *d_clock) {
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_probe_pairs_clock), &d_clock, sizeof d_clock) == hipSuccess ? 0 : 1;
+}
+#endif
+
+// The kernel is held to 96 SGPRs (it takes all 102 when let, and spills to VGPR lanes either way; no scratch): a CU admits
+// seven 256-thread blocks only up to an .sgpr_count of 96, and the LDS (22 528 B) and the VGPRs (<= 72) are cut for seven.
 template <class T, int TOPO, bool VEC>
-__global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const uint16_t *__restrict__ lab16,
+__global__ __launch_bounds__(NTHR) __attribute__((amdgpu_num_sgpr(96))) void k_pairs16(const T *__restrict__ z, const uint16_t *__restrict__ lab16,
                                                   const uint32_t *__restrict__ curN, unsigned long long *best,
                                                   int w, int h, uint32_t B, uint32_t tilesX,
                                                   const uint32_t *__restrict__ tiles_in, uint32_t nwork,
@@ -2832,11 +2856,11 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
                                                   const uint32_t *__restrict__ tile_count, uint32_t dtx,
                                                   const uint8_t *__restrict__ skip,
                                                   const uint32_t *__restrict__ edgeK, const uint16_t *__restrict__ edgeS) {
-  __shared__ __attribute__((aligned(8))) uint32_t sk[LH * LW];
-  __shared__ uint32_t sc[LH * LW];
-  __shared__ __attribute__((aligned(4))) uint16_t list[TW * TH];   // boundary cells; before that: the node table
-  uint32_t *const ntab = reinterpret_cast<uint32_t *>(list);
-  __shared__ unsigned long long pt_pair[PT_SLOTS];
+  __shared__ __attribute__((aligned(8))) uint32_t sk[PLH * LW];   // (row r = the tile's row r; column 0 = the left ring column)
+  __shared__ uint32_t sc[PLH * LW];
+  __shared__ __attribute__((aligned(4))) uint16_t list[LIST_CAP];   // boundary cells
+  __shared__ unsigned long long pt_pair[PT_SLOTS];                  // the pair table; before it is reset: the node table
+  uint32_t *const ntab = reinterpret_cast<uint32_t *>(pt_pair);
   __shared__ uint32_t pt_key[PT_SLOTS];
   __shared__ uint32_t nlist, pt_n, pt_base, seg_fill;
   uint32_t *const tab_id = sk;   // the component table lives in the keys' storage once the pairs are reduced
@@ -2873,8 +2897,9 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
   // ring cell of a thread (threads >= RING repeat the last one's loads and store nothing).  Everything that depends on
   // the thread index is recomputed from an opaque copy of it in every trip of the tile loop: hoisted out of the loop
   // these few dozen offsets and addresses cost 30 VGPRs, i.e. a third of the resident blocks.
-  auto ring_y = [](int tid) { const int rk = min(tid, RING - 1); return rk < LW ? 0 : rk < 2 * LW ? LH - 1 : (rk - 2 * LW < TH ? rk - 2 * LW + 1 : rk - 2 * LW - TH + 1); };
-  auto ring_x = [](int tid) { const int rk = min(tid, RING - 1); return rk < LW ? rk : rk < 2 * LW ? rk - LW : (rk - 2 * LW < TH ? 0 : LW - 1); };
+  // (ring coordinates as before: the cell is raster cell (x0 - 1 + ring_x, y0 - 1 + ring_y); ring_y is 1 ... TH + 1)
+  auto ring_y = [](int tid) { const int rk = min(tid, RING - 1); return rk < LW ? TH + 1 : rk < LW + TH ? rk - LW + 1 : rk - LW - TH + 2; };
+  auto ring_x = [](int tid) { const int rk = min(tid, RING - 1); return rk < LW ? rk : rk < LW + TH ? LW - 1 : 0; };
 
   auto load_a = [&](uint32_t t, int tid) {   // everything that only needs the tile's coordinates; branch free (clamped addresses)
     const int x0 = (int)(t % tilesX) * TW, y0 = (int)(t / tilesX) * TH;
@@ -2886,7 +2911,7 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
       const int gx = min(max(x0 - 1 + rx, 0), w - 1), gy = min(max(y0 - 1 + ry, 0), h - 1);
       // a ring COLUMN cell comes from the neighbouring descent tile's edge records (edgeK / edgeS, when the descent
       // wrote them): the left ring column is that tile's last column, the right one its first
-      const bool col = edgeK && ry >= 1 && ry <= TH && tid < RING;
+      const bool col = edgeK && ry <= TH && tid < RING;
       const uint32_t dtn = (uint32_t)(gy / DH) * dtx + (uint32_t)(gx / DW);
       const size_t e = ((size_t)dtn * 2 + (rx == 0 ? 1 : 0)) * DH + (uint32_t)(gy % DH);
       const size_t g = col ? (size_t)y0 * w + x0 : (size_t)gy * w + gx;   // (a column cell reads nothing new from the raster)
@@ -2935,6 +2960,9 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
     rc = curN[rtb + rl];
   };
 
+#ifdef RDGPU_PROBES
+  if (g_probe_pairs_clock && threadIdx.x == 0) g_probe_pairs_clock[2 * blockIdx.x] = g_probe_pairs_clock[2 * blockIdx.x + 1] = wall_clock64();
+#endif
   uint32_t t = next_tile(it);
   if (t == NO_TILE) return;
   load_a(t, (int)threadIdx.x);
@@ -2943,7 +2971,7 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
   for (;;) {
     int tid = (int)threadIdx.x;
     asm volatile("" : "+v"(tid));   // opaque: see above
-    const int lx = tid & (TW - 1), band = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int lane = tid & 63;
     const int rly = ring_y(tid), rlx = ring_x(tid);
     const bool isring = tid < RING;
     const int x0 = (int)(t % tilesX) * TW, y0 = (int)(t / tilesX) * TH;
@@ -2954,9 +2982,6 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
 #pragma unroll
       for (int k = 1; k < NT_CAP / NTHR; k++) ntab[tid + k * NTHR] = nt[k];
     }
-    pt_pair[tid] = ~0ull;
-    pt_key[tid] = 0xFFFFFFFFu;
-    static_assert(PT_SLOTS == NTHR, "one slot per thread");
     if (tid == 0) { nlist = 0; pt_n = 0; }
     __syncthreads();
     // ---- stage 2: keys and components of the tile and its ring into LDS ---------------------------------------------
@@ -2980,7 +3005,7 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
         for (int r = 0; r < 2; r++) {
           const int i = tid + r * NTHR;
           const int ly = i / (TW / 4), q = i - ly * (TW / 4);
-          const int o = (ly + 1) * LW + 1 + 4 * q;
+          const int o = ly * LW + 1 + 4 * q;
 #pragma unroll
           for (int e = 0; e < 4; e++) {
             sk[o + e] = key32_fast<T>(zq[r].v[e]);
@@ -2993,7 +3018,7 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
           const int i = tid + r * NTHR;
           const int ly = i / (TW / 4), q = i - ly * (TW / 4);
           const int gx = x0 + 4 * q, gy = y0 + ly;
-          const int o = (ly + 1) * LW + 1 + 4 * q;
+          const int o = ly * LW + 1 + 4 * q;
 #pragma unroll
           for (int e = 0; e < 4; e++) {
             const bool in = gy < h && gx + e < w;
@@ -3005,9 +3030,9 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
       if (isring) {
         const int gx = x0 - 1 + rlx, gy = y0 - 1 + rly;
         const bool ok = gx >= 0 && gx < w && gy >= 0 && gy < h;
-        const bool col = edgeK && rly >= 1 && rly <= TH;
-        sk[rly * LW + rlx] = ok ? (col ? rkey : key32_fast<T>(rz)) : 0u;
-        sc[rly * LW + rlx] = ok ? rc : (B | CLOSED);
+        const bool col = edgeK && rly <= TH;
+        sk[(rly - 1) * LW + rlx] = ok ? (col ? rkey : key32_fast<T>(rz)) : 0u;
+        sc[(rly - 1) * LW + rlx] = ok ? rc : (B | CLOSED);
       }
     }
     // ---- the next tile's loads go out now and land while this tile is worked on ---------------------------------------
@@ -3016,13 +3041,28 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
     const uint32_t tl = tn != NO_TILE ? tn : t;   // (no next tile: this one's rows once more -- cheaper than a branch)
     load_a(tl, tid);
     __syncthreads();
+    // (the node table's storage becomes the pair table: every lookup in it was made before the barrier above)
+    pt_pair[tid] = ~0ull;
+    pt_key[tid] = 0xFFFFFFFFu;
+    static_assert(PT_SLOTS == NTHR, "one slot per thread");
     // ---- phase 1: detect (k_scan's) -----------------------------------------------------------------------------------
-    const int gxl = x0 + lx;
-    const int yb = band * ROWS;
-    {
+    constexpr int NF = TOPO == 8 ? 4 : 2;
+    const int foff[4] = {1, TOPO == 8 ? LW + 1 : LW, LW, LW - 1};
+    // pass 0 lists the whole tile.  Only when that is more than the list holds do passes 1 ... 4 follow, one band each
+    // (white noise; a tile of the bench DEM has ~450 boundary cells): the wavefront of the band detects once more.
+#pragma nounroll
+    for (int pass = 0;; pass++) {
+    // (the thread's offsets once more from an opaque copy of its index, so that none of them is kept across the pair loop
+    // for the passes that hardly ever come)
+    asm volatile("" : "+v"(tid));
+    const int band = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (pass == 0 || band == pass - 1) {
+      const int lx = tid & (TW - 1), lane = tid & 63;
+      const int gxl = x0 + lx;
+      const int yb = band * ROWS;
       uint32_t c1[3], c2[3];
       {
-        const int o = (yb + 1) * LW + lx;
+        const int o = yb * LW + lx;   // (c1[0] of the tile's first row is the one cell nobody staged: it is not used)
 #pragma unroll
         for (int e = 0; e < 3; e++) c1[e] = sc[o + e];
       }
@@ -3035,41 +3075,42 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
       for (int j = 0; j < ROWS; j++) {
         const int ly = yb + j;
         {
-          const int o = (ly + 2) * LW + lx;
+          const int o = (ly + 1) * LW + lx;
 #pragma unroll
           for (int e = 0; e < 3; e++) c2[e] = sc[o + e];
         }
         const uint32_t C = c1[1];
         uint32_t df = (c1[2] ^ C) | (c2[1] ^ C);
         if (TOPO == 8) df |= (c2[0] ^ C) | (c2[2] ^ C);
+        // (opaque: else the or-chain becomes one compare per neighbour and the or is done on lane masks, by the scalar unit)
+        asm volatile("" : "+v"(df));
         bnd[j] = df != 0 && colin && j < rows_in;
         bal[j] = __builtin_amdgcn_ballot_w64(bnd[j]);   // (the builtin: __ballot() costs two VALU instructions)
 #pragma unroll
         for (int e = 0; e < 3; e++) c1[e] = c2[e];
       }
-      // (the node table's storage becomes the list: every lookup in it was made before the barrier above)
       uint32_t total = 0;
 #pragma unroll
       for (int j = 0; j < ROWS; j++) total += (uint32_t)__popcll(bal[j]);
       if (total) {
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(&nlist, total);
-        base = __shfl(base, 0, 64);
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (base + total <= (uint32_t)LIST_CAP)   // (else nlist ends above LIST_CAP, and the bands' passes follow)
 #pragma unroll
         for (int j = 0; j < ROWS; j++) {
           if (bnd[j])
             list[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[j], 0u))] =
-                (uint16_t)((yb + j + 1) * LW + lx + 1);
+                (uint16_t)((yb + j) * LW + lx + 1);
           base += (uint32_t)__popcll(bal[j]);
         }
       }
     }
     __syncthreads();
-    load_b(tid);
+    if (pass == 0) load_b(tid);
     // ---- phase 2: the pairs (k_scan<EMIT>'s) -----------------------------------------------------------------------
     const uint32_t nl = nlist;
-    constexpr int NF = TOPO == 8 ? 4 : 2;
-    const int foff[4] = {1, TOPO == 8 ? LW + 1 : LW, LW, LW - 1};
+    if (nl <= (uint32_t)LIST_CAP)
     for (uint32_t i = tid; i < nl; i += NTHR) {
       const int o = list[i];
       const uint32_t C = sc[o], kc = sk[o];
@@ -3109,6 +3150,11 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
           else if (!pair_insert(pt_pair, pt_key, lo[j], hi[j], pk[j])) pair_spill_local(eo, best, seg, &seg_fill, lo[j], hi[j], pk[j]);
         }
       }
+    }
+    if (pass == 0 ? nl <= (uint32_t)LIST_CAP : pass == TH / ROWS) break;
+    __syncthreads();   // every thread has read nlist and is through with the list
+    if (tid == 0) nlist = 0;
+    __syncthreads();
     }
     __syncthreads();
     tab_id[tid] = 0xFFFFFFFFu;
@@ -3173,6 +3219,9 @@ __global__ __launch_bounds__(NTHR) void k_pairs16(const T *__restrict__ z, const
   // (after an overflow seg_fill can lie past seglimit: the rounds enqueued before the host sees the flag read only the
   // records that were written)
   if (threadIdx.x == 0) eo.segcount[seg] = min(seg_fill, eo.seglimit);
+#ifdef RDGPU_PROBES
+  if (g_probe_pairs_clock && threadIdx.x == 0) g_probe_pairs_clock[2 * blockIdx.x + 1] = wall_clock64();
+#endif
 }
 
 // tiles the last plain fill of this thread wrote without reading them (RDGPU_FILL_COUNT_FLOODED=1; else 0): the finalize's
@@ -3210,14 +3259,34 @@ static void fill_finalize16(T *d_z, int w, int h, const FillBuffers &fb, hipStre
 // lists (optional, with skip): device arrays [descent tiles to visit | scan tiles to visit | tiles to finalize], each of
 // `stride` entries, and their lengths on the host
 // resident blocks of the persistent pair pass: what the kernel's registers and LDS let a CU hold (asked of the runtime),
-// times the CUs, rounded to a multiple of 8 so that every XCD gets the same number
+// times the CUs, rounded to a multiple of 8 so that every XCD gets the same number.
+// At most PAIRS_BPC per CU: the runtime answers 8 for a 256-thread block of 81 - 96 SGPRs, a CU admits
+// floor(800 / (ceil(sgpr / 16) * 16 + 16)) = 7 of them.  The tiles are dealt out over the grid beforehand, so an eighth block
+// would wait for a resident one to finish and then walk its share alone.
+constexpr int PAIRS_BPC = 7;
 template <class K>
 static int pairs_blocks(K kernel) {
   int dev = 0, cus = 0, bpc = 0;
   RD_HIP(hipGetDevice(&dev));
   RD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   RD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kernel, NTHR, 0));
+  bpc = std::min(bpc, PAIRS_BPC);
   return std::max(8, (cus * std::max(bpc, 1)) / 8 * 8);
+}
+
+// Grid of the first list round (k_edge_round<true>): a block takes the chunks blk, blk + grid, ... of NTHR * EPT records, and
+// a segment is `cps` chunks of which only the first few hold records.  How evenly the blocks share those is decided by
+// grid mod cps: at 8192 blocks and 34 chunks per segment (1792 segments at S3) the remainder 32 gives four filled chunks to
+// 40 % of the blocks and none to 35 %.  The remainder nearest to the golden section of cps (and coprime to it) spreads every
+// block's chunks over the segment: 522 -> 511 us there (the rest of what the kernel lost against 1536 segments of 40
+// chunks, 475 us, is the larger number of partly filled chunks: 14 336 against 13 824).
+static uint32_t seg_round_grid(uint32_t maxg, uint32_t nchunks, uint32_t cps) {
+  if (nchunks <= maxg || cps < 3 || cps >= maxg) return std::min(maxg, nchunks);
+  uint32_t step = (uint32_t)(cps * 0.6180339887 + 0.5);
+  while (std::gcd(step, cps) != 1) step++;
+  step %= cps;
+  const uint32_t g = maxg - maxg % cps + step;
+  return g > maxg ? g - cps : g;
 }
 
 struct SparseLists {
@@ -3470,7 +3539,8 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
       const uint32_t *ia = elist[ein], *ib = elist[ein] + pcap[ein], *ik = elist[ein] + 2 * pcap[ein];
       uint32_t *oa = elist[eout], *ob = elist[eout] + pcap[eout], *ok = elist[eout] + 2 * pcap[eout];
       if (eseg)   // round 2 reads the segmented list of the raster pass: the segments' fill counts are on the device
-        RD_LAUNCH("fill.edge_round", (k_edge_round<true>), dim3(std::min<uint32_t>(4 * gcap, cdiv(ecap, NTHR * EPT))), dim3(NTHR), 0,
+        RD_LAUNCH("fill.edge_round", (k_edge_round<true>),
+                  dim3(seg_round_grid(4 * gcap, (uint32_t)cdiv(ecap, NTHR * EPT), segcap / (NTHR * EPT))), dim3(NTHR), 0,
                   s, ia, ib, ik, (uint32_t)ecap, (const uint32_t *)segcount, segcap, (const uint32_t *)cur, best, B, oa, ob, ok, ne_next,
                   (const uint32_t *)nullptr, gate);
       else

@@ -638,7 +638,7 @@ def fa_tarboton_dev(dem, nodata, accum) -> None:
 
 
 def flow_accumulation_rounds() -> int:
-    """Launches of the work-list kernels (k_mfd_round / k_mfd_stack, csrc/mfd.hip) in the last generic accumulation --
+    """Launches of the work-list kernels (k_wl_buffer / k_wl_stack, csrc/mfd_worklist.hpp) in the last generic accumulation --
     FlowAccumFromProps, FA_Tarboton, FA_Holmgren / Freeman / Quinn / D4 and their _dev forms (rdgpu_flow_accumulation_rounds)."""
     r = ctypes.c_uint32()
     check(lib().rdgpu_flow_accumulation_rounds(ctypes.byref(r)), "rdgpu_flow_accumulation_rounds")

@@ -15,10 +15,10 @@
 //
 // Accumulation: "last arriver continues" generalised to several receivers.  A completed cell pushes
 // share*total to each receiver with a returning device-scope atomic add and decrements the receiver's
-// pending-donor count; it continues inline with the first receiver it completed and flags the others;
-// flagged cells are compacted into the next round's work list.  f64 sums in a different order than the
-// reference's FIFO: exact for integer-valued flows, f64 rounding otherwise.
-#include "mfd_shared.hpp"
+// pending-donor count; the receivers it completed are the work list's to continue with (mfd_worklist.hpp).
+// f64 sums in a different order than the reference's FIFO: exact for integer-valued flows, f64 rounding
+// otherwise.
+#include "mfd_worklist.hpp"
 
 namespace rdgpu {
 
@@ -278,81 +278,47 @@ __global__ __launch_bounds__(NTHR) void k_mfd_init(ACC a, uint32_t *pending, uin
   }
 }
 
-// One round: every thread takes one COMPLETED cell of the round's list and pushes its total to the receivers --
-// all returning adds in flight together, one wait, then all counter decrements together: two memory round trips
-// per cell however many receivers it has.  It continues inline with the first receiver it completed; the others go
-// into the thread's LDS buffer, and at the end the block appends all buffered cells to the next round's list with
-// ONE counter add (same-address atomics serialise at ~12 ns on this chip, and full-raster flag compaction cost
-// 4 ms per round x hundreds of rounds: r01b FA_Tarboton 1.2 s at 40k x 40k).  A thread whose buffer could not
-// take a worst case (8 completions) hands its current cell over to the next round unprocessed.
-constexpr int MBUF = 20;
+// The work list's step (mfd_worklist.hpp) for the COMPLETED cell c: its total goes to the receivers -- all returning adds
+// in flight together, one wait, then all counter decrements together: two memory round trips per cell however many
+// receivers it has.  Returns the receivers whose counter this thread took to zero: they are complete.
 template <class ACC>
-__global__ __launch_bounds__(NTHR) void k_mfd_round(ACC a, const uint32_t *__restrict__ list, uint32_t nlist,
-                                                    uint32_t *pending, double *acc, uint32_t *next_list,
-                                                    uint32_t *next_count, int w, int h) {
-  __shared__ uint32_t buf[MBUF][NTHR];
-  __shared__ uint32_t wtot[NTHR / 64];
-  __shared__ uint32_t bbase;
-  const uint32_t i = blockIdx.x * NTHR + threadIdx.x;
-  uint32_t nb = 0;
-  if (i < nlist) {
-    uint32_t c = list[i];
-    double v = acc[c];   // completed in an earlier launch (or a source): final
-    for (;;) {
-      const int x = (int)(c % (uint32_t)w), y = (int)(c / (uint32_t)w);
-      if (x == 0 || y == 0 || x == w - 1 || y == h - 1) break;   // edge cells never pass flow on (FM_*: :49-50)
-      if (nb + 8 > MBUF) { buf[nb++][threadIdx.x] = c; break; }
-      float p[8];
-      bool nd[8];
+struct AccStep {
+  ACC a;
+  uint32_t *pending;
+  double *acc;
+  int w, h;
+  __device__ __forceinline__ int width() const { return w; }
+  __device__ __forceinline__ uint32_t operator()(uint32_t c, bool from_list) const {
+    // the total: final since an earlier launch (or a source), or just completed: then read at the memory side
+    const double v = from_list ? acc[c] : atomicAdd(&acc[c], 0.0);
+    const int x = (int)(c % (uint32_t)w), y = (int)(c / (uint32_t)w);
+    if (x == 0 || y == 0 || x == w - 1 || y == h - 1) return 0;   // edge cells never pass flow on (FM_*: :49-50)
+    float p[8];
+    bool nd[8];
 #pragma unroll
-      for (int n = 1; n <= 8; n++) p[n - 1] = a.share(c, n);
+    for (int n = 1; n <= 8; n++) p[n - 1] = a.share(c, n);
 #pragma unroll
-      for (int n = 1; n <= 8; n++)   // flow_accumulation_generic.hpp:81-86
-        nd[n - 1] = (p[n - 1] > 0) ? a.nodata((uint64_t)(y + mdy(n)) * w + (x + mdx(n))) : true;
-      double prev = 0;
+    for (int n = 1; n <= 8; n++)   // flow_accumulation_generic.hpp:81-86
+      nd[n - 1] = (p[n - 1] > 0) ? a.nodata((uint64_t)(y + mdy(n)) * w + (x + mdx(n))) : true;
+    double prev = 0;
 #pragma unroll
-      for (int n = 1; n <= 8; n++)
-        if (!nd[n - 1]) prev += atomicAdd(&acc[(uint64_t)(y + mdy(n)) * w + (x + mdx(n))], (double)p[n - 1] * v);   // :87
-      // every add has returned (= was performed at the memory side) before any counter is decremented
-      asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
-      uint32_t old[8];
+    for (int n = 1; n <= 8; n++)
+      if (!nd[n - 1]) prev += atomicAdd(&acc[(uint64_t)(y + mdy(n)) * w + (x + mdx(n))], (double)p[n - 1] * v);   // :87
+    // every add has returned (= was performed at the memory side) before any counter is decremented
+    asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
+    uint32_t old[8];
 #pragma unroll
-      for (int n = 1; n <= 8; n++)
-        if (!nd[n - 1])
-          old[n - 1] = __hip_atomic_fetch_sub(&pending[(uint64_t)(y + mdy(n)) * w + (x + mdx(n))], 1u, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_AGENT);
-      uint32_t cont = 0xFFFFFFFFu;
+    for (int n = 1; n <= 8; n++)
+      if (!nd[n - 1])
+        old[n - 1] = __hip_atomic_fetch_sub(&pending[(uint64_t)(y + mdy(n)) * w + (x + mdx(n))], 1u, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t done = 0;
 #pragma unroll
-      for (int n = 1; n <= 8; n++) {
-        if (nd[n - 1] || old[n - 1] != 1) continue;
-        const uint32_t r = (uint32_t)(y + mdy(n)) * (uint32_t)w + (uint32_t)(x + mdx(n));   // r is complete
-        if (cont == 0xFFFFFFFFu) cont = r;          // continue inline with the first one,
-        else buf[nb++][threadIdx.x] = r;            // the others are for the next round
-      }
-      if (cont == 0xFFFFFFFFu) break;
-      c = cont;
-      v = atomicAdd(&acc[c], 0.0);                  // final total, read at the memory side
-    }
+    for (int n = 1; n <= 8; n++)
+      if (!nd[n - 1] && old[n - 1] == 1u) done |= 1u << (n - 1);
+    return done;
   }
-  // block-wide exclusive prefix of nb, one counter add per block
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t incl = nb;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wtot[wv] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t tot = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    bbase = tot ? atomicAdd(next_count, tot) : 0;
-  }
-  __syncthreads();
-  uint32_t off = bbase + incl - nb;
-  for (int k = 0; k < wv; k++) off += wtot[k];
-  for (uint32_t k = 0; k < nb; k++) next_list[off + k] = buf[k][threadIdx.x];
-}
+};
 
 template <class ACC>
 __global__ __launch_bounds__(NTHR) void k_mfd_nodata(ACC a, double *acc, uint64_t n) {
@@ -361,146 +327,24 @@ __global__ __launch_bounds__(NTHR) void k_mfd_nodata(ACC a, double *acc, uint64_
     if (a.nodata(c)) acc[c] = -1.0;                                     // ACCUM_NO_DATA, :95-97
 }
 
-// The same step with the round's by-products consumed where they arise (r04f).  In k_mfd_round a cell completed "on the
-// side" waits for the next launch, and a launch lasts as long as its longest inline chain: at S3 where every cell drains,
-// 2614 launches of 2.8 ms.  Here a wavefront keeps a STACK of such cells in LDS: a lane whose chain has ended takes the
-// next cell from it in the same trip of the loop, so a launch ends when everything reachable from its list is done --
-// except what a full stack spills to the next launch's list.  All lanes of a wavefront run the loop together (ballots
-// decide), the stack pointer is wave-uniform, LDS operations of one wavefront execute in order: no barriers.
-constexpr int WCAP = 1536;   // entries of a wavefront's stack (4 x 6 KB of LDS per block)
-constexpr uint32_t NOCELL = 0xFFFFFFFFu;
-template <class ACC>
-__global__ __launch_bounds__(NTHR) void k_mfd_stack(ACC a, const uint32_t *__restrict__ list, uint32_t nlist,
-                                                    uint32_t *pending, double *acc, uint32_t *next_list,
-                                                    uint32_t *next_count, int w, int h) {
-  __shared__ uint32_t stack[NTHR / 64][WCAP];
-  volatile uint32_t *const st = stack[threadIdx.x >> 6];
-  const int lane = threadIdx.x & 63;
-  uint32_t sp = 0;   // (wave-uniform)
-  const uint32_t i = blockIdx.x * NTHR + threadIdx.x;
-  uint32_t c = i < nlist ? list[i] : NOCELL;
-  double v = c != NOCELL ? acc[c] : 0.0;   // completed in an earlier launch (or a source): final
-  for (;;) {
-    const unsigned long long idle = __builtin_amdgcn_ballot_w64(c == NOCELL);
-    if (idle == ~0ull && sp == 0) break;
-    if (idle != 0ull && sp != 0) {   // idle lanes take the top of the stack
-      const uint32_t k = min((uint32_t)__popcll(idle), sp);
-      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-      if (c == NOCELL && rank < k) {
-        c = st[sp - 1u - rank];
-        v = atomicAdd(&acc[c], 0.0);       // its final total, read at the memory side
-      }
-      sp -= k;
-    }
-    uint32_t oth[8];
-    bool isoth[8];
-#pragma unroll
-    for (int n = 0; n < 8; n++) { oth[n] = 0; isoth[n] = false; }
-    uint32_t no = 0;
-    if (c != NOCELL) {
-      const int x = (int)(c % (uint32_t)w), y = (int)(c / (uint32_t)w);
-      uint32_t cont = NOCELL;
-      if (!(x == 0 || y == 0 || x == w - 1 || y == h - 1)) {   // edge cells never pass flow on (FM_*: :49-50)
-        float p[8];
-        bool nd[8];
-#pragma unroll
-        for (int n = 1; n <= 8; n++) p[n - 1] = a.share(c, n);
-#pragma unroll
-        for (int n = 1; n <= 8; n++)   // flow_accumulation_generic.hpp:81-86
-          nd[n - 1] = (p[n - 1] > 0) ? a.nodata((uint64_t)(y + mdy(n)) * w + (x + mdx(n))) : true;
-        double prev = 0;
-#pragma unroll
-        for (int n = 1; n <= 8; n++)
-          if (!nd[n - 1]) prev += atomicAdd(&acc[(uint64_t)(y + mdy(n)) * w + (x + mdx(n))], (double)p[n - 1] * v);   // :87
-        // every add has returned (= was performed at the memory side) before any counter is decremented
-        asm volatile("s_waitcnt vmcnt(0)" ::"v"(prev) : "memory");
-        uint32_t old[8];
-#pragma unroll
-        for (int n = 1; n <= 8; n++)
-          if (!nd[n - 1])
-            old[n - 1] = __hip_atomic_fetch_sub(&pending[(uint64_t)(y + mdy(n)) * w + (x + mdx(n))], 1u, __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int n = 1; n <= 8; n++) {
-          if (nd[n - 1] || old[n - 1] != 1) continue;
-          const uint32_t r = (uint32_t)(y + mdy(n)) * (uint32_t)w + (uint32_t)(x + mdx(n));   // r is complete
-          if (cont == NOCELL) cont = r;                       // continue inline with the first one,
-          else { oth[n - 1] = r; isoth[n - 1] = true; no++; }  // the others go on the stack
-        }
-      }
-      c = cont;
-      if (c != NOCELL) v = atomicAdd(&acc[c], 0.0);           // final total, read at the memory side
-    }
-    if (__builtin_amdgcn_ballot_w64(no != 0u) != 0ull) {   // push the step's by-products: one prefix over the lanes
-      uint32_t incl = no;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-      }
-      const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-      uint32_t pos = incl - no;
-      if (sp + total <= (uint32_t)WCAP) {
-#pragma unroll
-        for (int n = 0; n < 8; n++)
-          if (isoth[n]) st[sp + pos++] = oth[n];
-        sp += total;
-      } else {   // the stack cannot take them: the next launch's list
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(next_count, total);
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-#pragma unroll
-        for (int n = 0; n < 8; n++)
-          if (isoth[n]) next_list[base + pos++] = oth[n];
-      }
-    }
-  }
-}
-
 static uint32_t g_mfd_rounds = 0;
 
 template <class ACC>
 static void mfd_accumulate(ACC a, int w, int h, double *d_acc, hipStream_t s) {
   const uint64_t n = (uint64_t)w * h;
   Workspace &ws = Workspace::get();
-  uint32_t *hw = ws.host_words();
   uint32_t *pending = ws.buf<uint32_t>("mfd.pending", n);
   uint8_t *ready = ws.buf<uint8_t>("mfd.ready", n);
-  uint32_t *list = ws.buf<uint32_t>("mfd.list", n);
-  const uint32_t nblk = (uint32_t)((n + CPB - 1) / CPB);
-  uint32_t *counts = ws.buf<uint32_t>("mfd.counts", (size_t)nblk + 1);
   RD_LAUNCH("mfd.init", (k_mfd_init<ACC>), dim3(sgrid(n)), dim3(NTHR), 0, s, a, pending, ready, w, h);
   g_mfd_rounds = 0;
-  // the sources, once, by flag compaction; afterwards every round appends its successor list itself
-  RD_LAUNCH("mfd.ready_count", k_rdy_count, dim3(nblk), dim3(NTHR), 0, s, (const uint8_t *)ready, n, counts);
-  RD_LAUNCH("mfd.ready_scan", k_rdy_scan, dim3(1), dim3(1024), 0, s, counts, nblk, counts + nblk);
-  RD_HIP(hipMemcpyAsync(hw, counts + nblk, 4, hipMemcpyDeviceToHost, s));
-  RD_HIP(hipStreamSynchronize(s));
-  uint32_t nl = hw[0];
-  if (nl) RD_LAUNCH("mfd.ready_fill", k_rdy_fill, dim3(nblk), dim3(NTHR), 0, s, ready, n, (const uint32_t *)counts, list);
-  uint32_t *list2 = ws.buf<uint32_t>("mfd.list2", n);
-  uint32_t *ctr = counts + nblk;
-  // Long lists go through k_mfd_round (their by-products are processed next launch, densely packed: a wavefront that
-  // works off its own by-products runs at a few active lanes -- S3's filled DEM, 223 launches: 256 ms, one stacked launch
-  // 492); once a list is short the launches are what costs (S3 where every cell drains: 2614 launches, 7.2 s) and
-  // k_mfd_stack finishes everything that is left.  RDGPU_MFD_STACK_BELOW sets the list length of the switch (0: never).
+  // Long lists go through the buffer kernel (their by-products are processed next launch, densely packed: a wavefront
+  // that works off its own by-products runs at a few active lanes -- S3's filled DEM, 223 launches: 256 ms, one stacked
+  // launch 492); once a list is short the launches are what costs (S3 where every cell drains: 2614 launches, 7.2 s) and
+  // the stack kernel finishes everything that is left.  RDGPU_MFD_STACK_BELOW sets the list length of the switch (0: never).
   const char *se = getenv("RDGPU_MFD_STACK_BELOW");
   const uint32_t stack_below = se ? (uint32_t)strtoul(se, nullptr, 10) : (1u << 22);
-  while (nl) {
-    const bool stacked = nl < stack_below;
-    RD_HIP(hipMemsetAsync(ctr, 0, sizeof(uint32_t), s));
-    if (stacked)
-      RD_LAUNCH("mfd.round", (k_mfd_stack<ACC>), dim3((nl + NTHR - 1) / NTHR), dim3(NTHR), 0, s, a, (const uint32_t *)list, nl,
-                pending, d_acc, list2, ctr, w, h);
-    else
-      RD_LAUNCH("mfd.round", (k_mfd_round<ACC>), dim3((nl + NTHR - 1) / NTHR), dim3(NTHR), 0, s, a, (const uint32_t *)list, nl,
-                pending, d_acc, list2, ctr, w, h);
-    RD_HIP(hipMemcpyAsync(hw, ctr, 4, hipMemcpyDeviceToHost, s));
-    RD_HIP(hipStreamSynchronize(s));
-    nl = hw[0];
-    std::swap(list, list2);
-    if (++g_mfd_rounds > (1u << 26)) throw Error(RDGPU_ERR_HIP, "rdgpu flow accumulation did not terminate");
-  }
+  g_mfd_rounds = worklist_run(ready, n, AccStep<ACC>{a, pending, d_acc, w, h}, "mfd.round", "mfd.round", stack_below,
+                              "rdgpu flow accumulation did not terminate", s);
   RD_LAUNCH("mfd.nodata", (k_mfd_nodata<ACC>), dim3(sgrid(n)), dim3(NTHR), 0, s, a, d_acc, n);
 }
 

@@ -10,9 +10,9 @@
 // DECIDED cells.  Its thread decrements the counter of every donor of its cell with a returning agent-scope atomic; the
 // thread that takes a counter to zero is the only one that ever computes that donor: it reads the state and the values
 // of the donor's receivers, combines them in the fixed order n = 1..8, publishes the donor and continues inline with
-// it.  Further donors it completed in the same step go to the wavefront's LDS stack (k_dist_stack) or to the next
-// launch's list (k_dist_round).  Nothing waits: a cycle of positive shares leaves its counters above zero, the lists run
-// empty and the finalize gives those cells out_nodata.
+// it.  Further donors it completed in the same step go to the wavefront's LDS stack or to the next launch's list: the
+// work list is the accumulation's (mfd_worklist.hpp).  Nothing waits: a cycle of positive shares leaves its counters
+// above zero, the lists run empty and the finalize gives those cells out_nodata.
 //
 // Visibility between workgroups (per-XCD L2s are not coherent, a CU's L1 is never refreshed by another CU's stores): a
 // cell's values and state are published with relaxed agent-scope atomic stores (write-through, at most 8 B each); the
@@ -20,7 +20,7 @@
 // value in the work-list kernels is a relaxed agent-scope atomic load, which bypasses the L1.  A reader only ever looks
 // at a cell after the decrement that followed that cell's drain, so it needs no fence.  The output planes themselves
 // hold the values while the lists run.
-#include "mfd_shared.hpp"
+#include "mfd_worklist.hpp"
 
 #include <cmath>
 
@@ -181,104 +181,16 @@ __device__ __forceinline__ uint32_t dist_step(const ACC &a, const DistArgs &g, u
   }
   return done;
 }
-__device__ __forceinline__ uint32_t nbr_cell(uint32_t c, int m, int w) {
-  return (uint32_t)((int)c + mdy(m) * w + mdx(m));
-}
 
-// Every thread takes one decided cell of the launch's list and continues inline with the first donor it completes; the
-// others go into the thread's LDS buffer and from there to the next launch's list (one counter add per block).  A thread
-// whose buffer could not take a worst case (8 completions) hands its current cell over to the next launch unprocessed.
-constexpr int DBUF = 20;
+// the work list's step (mfd_worklist.hpp); a cell's state and values are read at the memory side wherever it comes from
 template <class ACC>
-__global__ __launch_bounds__(NTHR) void k_dist_round(ACC a, DistArgs g, const uint32_t *__restrict__ list, uint32_t nlist,
-                                                     uint32_t *st, uint32_t *next_list, uint32_t *next_count) {
-  __shared__ uint32_t buf[DBUF][NTHR];
-  __shared__ uint32_t wtot[NTHR / 64];
-  __shared__ uint32_t bbase;
-  const uint32_t i = blockIdx.x * NTHR + threadIdx.x;
-  uint32_t nb = 0;
-  if (i < nlist) {
-    uint32_t c = list[i];
-    for (;;) {
-      if (nb + 8 > DBUF) { buf[nb++][threadIdx.x] = c; break; }
-      uint32_t done = dist_step<ACC>(a, g, st, c);
-      if (!done) break;
-      const uint32_t c0 = c;
-      c = nbr_cell(c0, __builtin_ctz(done) + 1, g.w);
-      for (done &= done - 1u; done; done &= done - 1u) buf[nb++][threadIdx.x] = nbr_cell(c0, __builtin_ctz(done) + 1, g.w);
-    }
-  }
-  // block-wide exclusive prefix of nb, one counter add per block
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t incl = nb;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wtot[wv] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t tot = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    bbase = tot ? atomicAdd(next_count, tot) : 0;
-  }
-  __syncthreads();
-  uint32_t off = bbase + incl - nb;
-  for (int k = 0; k < wv; k++) off += wtot[k];
-  for (uint32_t k = 0; k < nb; k++) next_list[off + k] = buf[k][threadIdx.x];
-}
-
-// The same step with the by-products consumed where they arise, as k_mfd_stack does: a wavefront keeps a stack of decided
-// cells in LDS, a lane whose chain has ended takes the next one from it, and what a full stack cannot take goes to the
-// next launch's list.  The stack pointer is wave-uniform, LDS operations of one wavefront execute in order: no barriers.
-constexpr int DCAP = 1536;   // entries of a wavefront's stack (4 x 6 KB of LDS per block)
-constexpr uint32_t NOCELL = 0xFFFFFFFFu;
-template <class ACC>
-__global__ __launch_bounds__(NTHR) void k_dist_stack(ACC a, DistArgs g, const uint32_t *__restrict__ list, uint32_t nlist,
-                                                     uint32_t *st, uint32_t *next_list, uint32_t *next_count) {
-  __shared__ uint32_t stack[NTHR / 64][DCAP];
-  volatile uint32_t *const sk = stack[threadIdx.x >> 6];
-  const int lane = threadIdx.x & 63;
-  uint32_t sp = 0;   // (wave-uniform)
-  const uint32_t i = blockIdx.x * NTHR + threadIdx.x;
-  uint32_t c = i < nlist ? list[i] : NOCELL;
-  for (;;) {
-    const unsigned long long idle = __builtin_amdgcn_ballot_w64(c == NOCELL);
-    if (idle == ~0ull && sp == 0) break;
-    if (idle != 0ull && sp != 0) {   // idle lanes take the top of the stack
-      const uint32_t k = min((uint32_t)__popcll(idle), sp);
-      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-      if (c == NOCELL && rank < k) c = sk[sp - 1u - rank];
-      sp -= k;
-    }
-    uint32_t oth = 0, c0 = c;
-    if (c != NOCELL) {
-      const uint32_t done = dist_step<ACC>(a, g, st, c);
-      c = done ? nbr_cell(c0, __builtin_ctz(done) + 1, g.w) : NOCELL;   // continue inline with the first one,
-      oth = done & (done - 1u);                                         // the others go on the stack
-    }
-    const uint32_t no = (uint32_t)__popc(oth);
-    if (__builtin_amdgcn_ballot_w64(no != 0u) != 0ull) {   // push the step's by-products: one prefix over the lanes
-      uint32_t incl = no;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-      }
-      const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-      uint32_t pos = incl - no;
-      if (sp + total <= (uint32_t)DCAP) {
-        for (; oth; oth &= oth - 1u) sk[sp + pos++] = nbr_cell(c0, __builtin_ctz(oth) + 1, g.w);
-        sp += total;
-      } else {   // the stack cannot take them: the next launch's list
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(next_count, total);
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        for (; oth; oth &= oth - 1u) next_list[base + pos++] = nbr_cell(c0, __builtin_ctz(oth) + 1, g.w);
-      }
-    }
-  }
-}
+struct DistStep {
+  ACC a;
+  DistArgs g;
+  uint32_t *st;
+  __device__ __forceinline__ int width() const { return g.w; }
+  __device__ __forceinline__ uint32_t operator()(uint32_t c, bool) const { return dist_step<ACC>(a, g, st, c); }
+};
 
 __global__ __launch_bounds__(NTHR) void k_dist_finalize(const uint32_t *__restrict__ st, double *dist, double *drop,
                                                         double out_nodata, uint64_t n) {
@@ -313,14 +225,8 @@ static void mfd_distance(ACC a, int w, int h, const uint8_t *d_chan, const doubl
                          double *d_drop, double out_nodata, hipStream_t s) {
   const uint64_t n = (uint64_t)w * h;
   Workspace &ws = Workspace::get();
-  uint32_t *hw = ws.host_words();
   uint32_t *st = ws.buf<uint32_t>("mfd.pending", n);
   uint8_t *ready = ws.buf<uint8_t>("mfd.ready", n);
-  uint32_t *list = ws.buf<uint32_t>("mfd.list", n);
-  uint32_t *list2 = ws.buf<uint32_t>("mfd.list2", n);
-  const uint32_t nblk = (uint32_t)((n + CPB - 1) / CPB);
-  uint32_t *counts = ws.buf<uint32_t>("mfd.counts", (size_t)nblk + 1);
-  uint32_t *ctr = counts + nblk;
   DistArgs g;
   g.chan = d_chan;
   g.elev = d_drop ? d_elev : nullptr;
@@ -335,35 +241,16 @@ static void mfd_distance(ACC a, int w, int h, const uint8_t *d_chan, const doubl
   g.h = h;
   g_dist_rounds = 0;
   RD_LAUNCH("mfddist.init", (k_dist_init<ACC>), dim3(sgrid(n)), dim3(NTHR), 0, s, a, g, st, ready);
-  RD_LAUNCH("mfddist.ready_count", k_rdy_count, dim3(nblk), dim3(NTHR), 0, s, (const uint8_t *)ready, n, counts);
-  RD_LAUNCH("mfddist.ready_scan", k_rdy_scan, dim3(1), dim3(1024), 0, s, counts, nblk, ctr);
-  RD_HIP(hipMemcpyAsync(hw, ctr, 4, hipMemcpyDeviceToHost, s));
-  RD_HIP(hipStreamSynchronize(s));
-  uint32_t nl = hw[0];
-  if (nl) RD_LAUNCH("mfddist.ready_fill", k_rdy_fill, dim3(nblk), dim3(NTHR), 0, s, ready, n, (const uint32_t *)counts, list);
-  // Long lists go through k_dist_round (their by-products are processed next launch, densely packed), short ones through
-  // k_dist_stack, which finishes what is reachable from its list in one launch.  RDGPU_MFD_DISTANCE_STACK_BELOW sets the
+  // Long lists go through the buffer kernel (their by-products are processed next launch, densely packed), short ones through
+  // the stack kernel, which finishes what is reachable from its list in one launch.  RDGPU_MFD_DISTANCE_STACK_BELOW sets the
   // list length of the switch (0: never the stack; 4294967295: always).  Where every cell drains, channels at >= 100 cells
   // (dist + drop; ms at 6000^2 / 16000^2 / 40000^2): never 77 / 261 / 1103, 2^20 16.5 / 132 / 858, 2^22 16.5 / 112 / 797,
   // 2^24 38 / 118 / 746, 2^26 38 / 116 / 795-810, always 38 / 271 / 1696 -- a first list of stop cells that goes to the stack
   // kernel, and any wavefront that works off its own by-products, runs at a few active lanes.
   const char *se = getenv("RDGPU_MFD_DISTANCE_STACK_BELOW");
   const uint32_t stack_below = se ? (uint32_t)strtoul(se, nullptr, 10) : (1u << 22);
-  while (nl) {
-    const bool stacked = nl < stack_below;
-    RD_HIP(hipMemsetAsync(ctr, 0, sizeof(uint32_t), s));
-    if (stacked)
-      RD_LAUNCH("mfddist.stack", (k_dist_stack<ACC>), dim3((nl + NTHR - 1) / NTHR), dim3(NTHR), 0, s, a, g, (const uint32_t *)list,
-                nl, st, list2, ctr);
-    else
-      RD_LAUNCH("mfddist.round", (k_dist_round<ACC>), dim3((nl + NTHR - 1) / NTHR), dim3(NTHR), 0, s, a, g, (const uint32_t *)list,
-                nl, st, list2, ctr);
-    RD_HIP(hipMemcpyAsync(hw, ctr, 4, hipMemcpyDeviceToHost, s));
-    RD_HIP(hipStreamSynchronize(s));
-    nl = hw[0];
-    std::swap(list, list2);
-    if (++g_dist_rounds > (1u << 26)) throw Error(RDGPU_ERR_HIP, "rdgpu mfd distance did not terminate");
-  }
+  g_dist_rounds = worklist_run(ready, n, DistStep<ACC>{a, g, st}, "mfddist.round", "mfddist.stack", stack_below,
+                               "rdgpu mfd distance did not terminate", s);
   RD_LAUNCH("mfddist.finalize", k_dist_finalize, dim3(sgrid(n)), dim3(NTHR), 0, s, (const uint32_t *)st, d_dist, d_drop,
             out_nodata, n);
 }

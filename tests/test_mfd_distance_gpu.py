@@ -32,7 +32,7 @@ STATS = ("ave", "min", "max")
 COMBOS = [(s, t) for s in STATS for t in (True, False)]
 SENT = 77.0
 ENV = "RDGPU_MFD_DISTANCE_STACK_BELOW"
-STACK_BELOW = [None, "0", "4294967295"]      # the default; always k_dist_round; always k_dist_stack
+STACK_BELOW = [None, "0", "4294967295"]      # the default; always k_wl_buffer; always k_wl_stack
 MODE = {None: "default", "0": "round", "4294967295": "stack"}
 _CACHE = {}
 
@@ -328,7 +328,7 @@ HAND = {
     "fractions": lambda: (fractions(), None),
 }
 
-# Launch counts that follow from DCAP = 1536 (entries of a wavefront's stack) and DBUF = 20 (entries of a thread's buffer),
+# Launch counts that follow from WL_CAP = 1536 (entries of a wavefront's stack) and WL_BUF = 20 (entries of a thread's buffer),
 # by (raster, forced kernel).  The first list is the 64 (8, 128) trunk heads in row-major order: one lane each.
 #  stack, 64 trunks of 40: every step of the wavefront pushes 64 side chains and no lane is idle before the trunks end, so
 #    the stack (1536) is full after 24 of the 39 steps and the later steps spill: a second launch.  8 trunks: 56 idle lanes

@@ -1,16 +1,16 @@
-"""GPU tests of the generic accumulation's work list (csrc/mfd.hip: k_mfd_stack, k_mfd_round) on dependency graphs handed
+"""GPU tests of the generic accumulation's work list (csrc/mfd_worklist.hpp: k_wl_stack, k_wl_buffer) on dependency graphs handed
 to it directly as proportion rasters, so that the paths a fractal DEM does not reach are PROVEN to run:
 
-  * the spill of k_mfd_stack (a wavefront's LDS stack of WCAP = 1536 cells is full: by-products go to the next launch),
-  * the hand-over of k_mfd_round (a thread's LDS buffer of MBUF = 20 cannot take 8 more: the current cell goes to the
+  * the spill of k_wl_stack (a wavefront's LDS stack of WL_CAP = 1536 cells is full: by-products go to the next launch),
+  * the hand-over of k_wl_buffer (a thread's LDS buffer of WL_BUF = 20 cannot take 8 more: the current cell goes to the
     next launch unprocessed),
   * the pop of idle lanes (min(popcount(idle), sp) entries, ranked by mbcnt), eight donors completing one cell at the same
     moment, pushes of several cells by one lane, cells on the raster's edge, NoData receivers, a cycle,
   * the compact D-infinity accessor (DinfAcc) against the nine-float one (PropsAcc) on the same proportions,
   * the device entries rdgpu_flow_accumulation_dev_f64 and rdgpu_fa_mfd_dev_* on the caller's stream.
 
-Which path ran is read from the launch count (rd.flow_accumulation_rounds()); the bounds asserted on it follow from WCAP
-and MBUF (see EXPECT_ROUNDS), not from a measurement.  All graphs carry shares of 1.0 and are forests (hubs: sums of nine
+Which path ran is read from the launch count (rd.flow_accumulation_rounds()); the bounds asserted on it follow from WL_CAP
+and WL_BUF (see EXPECT_ROUNDS), not from a measurement.  All graphs carry shares of 1.0 and are forests (hubs: sums of nine
 integers), so every value is a small integer, the order of summation cannot matter and the comparison is exact.
 
 Proportions layout [h, w, 9]: slot 0 is the marker (-2 NoData, 0 has flow, -1 no flow), slots 1..8 the shares (-1 none) to
@@ -29,7 +29,7 @@ DX = (0, -1, -1, 0, 1, 1, 1, 0, -1)
 DY = (0, 0, -1, -1, -1, 0, 1, 1, 1)
 LEFT, UP, RIGHT, DOWN = 1, 3, 5, 7
 
-STACK_BELOW = [None, "0", "4000000000"]      # the default; always k_mfd_round; always k_mfd_stack
+STACK_BELOW = [None, "0", "4000000000"]      # the default; always k_wl_buffer; always k_wl_stack
 MODE = {None: "default", "0": "round", "4000000000": "stack"}
 
 
@@ -122,7 +122,7 @@ def hubs(size=150):
 
 def stars(k=8, pitch=7):
     """A lattice of sources that feed all eight neighbours, each the head of a straight outward ray of 2 more cells: one
-    lane pushes 7 cells at once (the per-lane prefix with no > 1; nb = 7 after one step of k_mfd_round)."""
+    lane pushes 7 cells at once (the per-lane prefix with no > 1; nb = 7 after one step of k_wl_buffer)."""
     p = blank(k * pitch + 2, k * pitch + 2)
     for j in range(k):
         for i in range(k):
@@ -151,7 +151,7 @@ RASTERS = {
     "comb_control": lambda: comb([40] * 8),                                  # 34 x 42: 56 idle lanes pop, nothing spills
     "comb_two_waves": lambda: comb([40] * 128),                              # two wavefronts of one block, a stack each
     "comb_ragged": lambda: comb([20 + (7 * i) % 61 for i in range(64)]),     # lanes go idle at different steps
-    "comb_short": lambda: comb([12] * 64),                                   # 11 pushes per thread fit in MBUF
+    "comb_short": lambda: comb([12] * 64),                                   # 11 pushes per thread fit in WL_BUF
     "comb_ns": comb_ns,
     "comb_to_edges": lambda: comb([40] * 64, to_edges=True),
     "comb_nodata": lambda: comb([40] * 64, nodata_heads=True),
@@ -160,7 +160,7 @@ RASTERS = {
     "cycle": cycle,
 }
 
-# Launch counts that follow from WCAP = 1536 and MBUF = 20 (op, bound), by (raster, forced schedule):
+# Launch counts that follow from WL_CAP = 1536 and WL_BUF = 20 (op, bound), by (raster, forced schedule):
 #  stack, 64 trunks of 40: every step of the wavefront pushes 64 side heads (51 or 52 in comb_nodata, 39 steps: > 1536 in
 #    all) and no lane is idle before the trunks end, so the stack is full after 24 steps and the later steps spill: a
 #    second launch.  8 trunks: 56 idle lanes pop what 8 push; 64 trunks of 12: 64 x 11 = 704 entries: one launch.

@@ -712,6 +712,53 @@ RDGPU_DECL_MFD(f32, float)
 RDGPU_DECL_MFD(f64, double)
 RDGPU_DECL_MFD(i8, int8_t)
 #undef RDGPU_DECL_MFD
+/* ---- D-infinity across flats ----------------------------------------------------------------------
+ * FM_Tarboton gives a cell without a descending facet NO_FLOW, so on a filled DEM the D-infinity products stop at
+ * every lake surface.  The _flats entries route such cells over Barnes' flat mask WITHOUT altering the DEM.  No
+ * reference function returns this (its resolve_flats_barnes_dinf works on the angle raster, where flow due east and
+ * NO_FLOW are both 0.0); the rule is defined here:
+ *   1. the proportions start as rdgpu_fm_tarboton_<T>'s;
+ *   2. d8 = rdgpu_d8_flowdirs(z), (flat_mask, labels) = rdgpu_flat_resolution_d8's mask path on (z, d8); NoData
+ *      neighbours count by their value, as there;
+ *   3. a cell c is PATCHED iff d8(c) == NO_FLOW and labels(c) != 0 (such a cell is interior);
+ *   4. its 3 x 3 window of flat_mask, every neighbour with another label replaced by a NoData sentinel, goes through
+ *      FM_Tarboton's cell rule (flowmet/Tarboton1997.hpp:75-141: 1e-7 thresholds, facets n = 1..8); the result
+ *      replaces the cell's shares;
+ *   5. where no facet descends, share 1 goes to the first n in 1..8 whose neighbour has the same label and a
+ *      strictly smaller mask value;
+ *   6. where there is none either, the cell stays NO_FLOW (counted in unresolved_cells).
+ * Nothing else changes: cells with a gradient, flats without an outlet, edge cells and cells whose descending
+ * facets all touch NoData are FM_Tarboton's.  Every patched share points at a smaller mask value: no cycles.
+ * rdgpu_fm_tarboton_flats_<T>   the 9-float layout of rdgpu_fm_tarboton_<T>.
+ * rdgpu_fa_tarboton_flats_<T>   rdgpu_fa_tarboton_<T> over these proportions; accum in/out, the 36 B/cell array is
+ *                               never materialised.
+ * (rdgpu_dinf_distance_down_flats_<T>: with the distance entries below.)
+ * At most 0x7FFF0000 cells (the flat resolution's limit).  The _dev forms are ordered on hip_stream but wait for it
+ * where the flat resolution reads its counts back.  Scratch: rdgpu_fa_tarboton's plus the flat resolution's plus one
+ * byte per cell.
+ * rdgpu_dinf_flats_get_stats: the counts of the calling thread's last _flats call (any of the entries); waits for that
+ * call's stream.  All zero before the first call. */
+typedef struct rdgpu_dinf_flats_stats {
+  uint64_t noflow_cells;     /* interior data cells FM_Tarboton leaves without flow */
+  uint64_t patched_cells;    /* cells patched under rule 3 */
+  uint64_t fallback_cells;   /* of those, served by rule 5 */
+  uint64_t unresolved_cells; /* patched but still without flow, rule 6 */
+} rdgpu_dinf_flats_stats;
+int rdgpu_dinf_flats_get_stats(rdgpu_dinf_flats_stats *out);
+#define RDGPU_DECL_MFD_FLATS(SUF, T)                                                                            \
+  int rdgpu_fm_tarboton_flats_##SUF(const T *dem, T nodata, int width, int height, float *props9);              \
+  int rdgpu_fm_tarboton_flats_dev_##SUF(const T *d_dem, T nodata, int width, int height, float *d_props9, void *hip_stream); \
+  int rdgpu_fa_tarboton_flats_##SUF(const T *dem, T nodata, int width, int height, double *accum);              \
+  int rdgpu_fa_tarboton_flats_dev_##SUF(const T *d_dem, T nodata, int width, int height, double *d_accum, void *hip_stream);
+RDGPU_DECL_MFD_FLATS(u8, uint8_t)
+RDGPU_DECL_MFD_FLATS(i8, int8_t)
+RDGPU_DECL_MFD_FLATS(u16, uint16_t)
+RDGPU_DECL_MFD_FLATS(i16, int16_t)
+RDGPU_DECL_MFD_FLATS(u32, uint32_t)
+RDGPU_DECL_MFD_FLATS(i32, int32_t)
+RDGPU_DECL_MFD_FLATS(f32, float)
+RDGPU_DECL_MFD_FLATS(f64, double)
+#undef RDGPU_DECL_MFD_FLATS
 /* FM_Holmgren(x) / FM_Freeman(x) / FM_Quinn / FM_D4 proportions and the matching FA_* accumulations
  * (flowmet/Holmgren1994.hpp:14, Freeman1991.hpp:14, Quinn1991.hpp:13, OCallaghan1984.hpp:86;
  * methods/flow_accumulation.hpp:18-20,28).  method: 0 Holmgren, 1 Freeman, 2 Quinn, 3 D4; xparam is the
@@ -1215,6 +1262,8 @@ RDGPU_DECL_DEPR(u64, uint64_t)  /* RDGPU_ERR_UNSUPPORTED */
  * pointers and are ordered on hip_stream without synchronising it.
  * rdgpu_dinf_distance_down_<T> takes a DEM: the proportions are FM_Tarboton's in compact form (5 bytes per cell, the
  * array is never materialised) and the elevations are the DEM's.  T: u8 i8 i16 u16 i32 u32 f32 f64.
+ * rdgpu_dinf_distance_down_flats_<T> is the same over the proportions of rdgpu_fm_tarboton_flats_<T> ("D-infinity across
+ * flats" above): same arguments, same statistics, same strict rule; at most 0x7FFF0000 cells.
  * rdgpu_mfd_distance_rounds: the work-list launches of the last call.  RDGPU_MFD_DISTANCE_STACK_BELOW: lists shorter
  * than this many cells run in the kernel that keeps its by-products on a per-wavefront stack (default 4194304; 0: never).
  * Scratch (13 bytes per cell, shared with the accumulation; 8 more for drop from a DEM that is not float64) comes from
@@ -1227,22 +1276,22 @@ int rdgpu_mfd_distance_down_dev(const float *d_props9, int width, int height, co
                                 double cell_y, double *d_dist /* nullable */, double *d_drop /* nullable */,
                                 double out_nodata, void *hip_stream);
 int rdgpu_mfd_distance_rounds(uint32_t *rounds);
-#define RDGPU_DECL_DINF_DIST(SUF, T)                                                                                     \
-  int rdgpu_dinf_distance_down_##SUF(const T *dem, T nodata, int width, int height, const uint8_t *chan /* nullable */,  \
-                                     int stat, int strict, double cell_x, double cell_y, double *dist /* nullable */,    \
-                                     double *drop /* nullable */, double out_nodata);                                    \
-  int rdgpu_dinf_distance_down_dev_##SUF(const T *d_dem, T nodata, int width, int height,                                \
-                                         const uint8_t *d_chan /* nullable */, int stat, int strict, double cell_x,      \
-                                         double cell_y, double *d_dist /* nullable */, double *d_drop /* nullable */,    \
+#define RDGPU_DECL_DINF_DIST(FL, SUF, T)                                                                                  \
+  int rdgpu_dinf_distance_down##FL##_##SUF(const T *dem, T nodata, int width, int height, const uint8_t *chan /* nullable */, \
+                                     int stat, int strict, double cell_x, double cell_y, double *dist /* nullable */,     \
+                                     double *drop /* nullable */, double out_nodata);                                     \
+  int rdgpu_dinf_distance_down##FL##_dev_##SUF(const T *d_dem, T nodata, int width, int height,                           \
+                                         const uint8_t *d_chan /* nullable */, int stat, int strict, double cell_x,       \
+                                         double cell_y, double *d_dist /* nullable */, double *d_drop /* nullable */,     \
                                          double out_nodata, void *hip_stream);
-RDGPU_DECL_DINF_DIST(u8, uint8_t)
-RDGPU_DECL_DINF_DIST(i16, int16_t)
-RDGPU_DECL_DINF_DIST(u16, uint16_t)
-RDGPU_DECL_DINF_DIST(i32, int32_t)
-RDGPU_DECL_DINF_DIST(u32, uint32_t)
-RDGPU_DECL_DINF_DIST(f32, float)
-RDGPU_DECL_DINF_DIST(f64, double)
-RDGPU_DECL_DINF_DIST(i8, int8_t)
+RDGPU_DECL_DINF_DIST(, u8, uint8_t) RDGPU_DECL_DINF_DIST(_flats, u8, uint8_t)
+RDGPU_DECL_DINF_DIST(, i16, int16_t) RDGPU_DECL_DINF_DIST(_flats, i16, int16_t)
+RDGPU_DECL_DINF_DIST(, u16, uint16_t) RDGPU_DECL_DINF_DIST(_flats, u16, uint16_t)
+RDGPU_DECL_DINF_DIST(, i32, int32_t) RDGPU_DECL_DINF_DIST(_flats, i32, int32_t)
+RDGPU_DECL_DINF_DIST(, u32, uint32_t) RDGPU_DECL_DINF_DIST(_flats, u32, uint32_t)
+RDGPU_DECL_DINF_DIST(, f32, float) RDGPU_DECL_DINF_DIST(_flats, f32, float)
+RDGPU_DECL_DINF_DIST(, f64, double) RDGPU_DECL_DINF_DIST(_flats, f64, double)
+RDGPU_DECL_DINF_DIST(, i8, int8_t) RDGPU_DECL_DINF_DIST(_flats, i8, int8_t)
 #undef RDGPU_DECL_DINF_DIST
 
 /* ---- synthetic input (test/bench input generator) ----------- */

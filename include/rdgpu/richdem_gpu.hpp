@@ -87,6 +87,18 @@ RDGPU_SHIM_STENCIL(i8, int8_t)
 RDGPU_SHIM_STENCIL64(i64, int64_t)
 RDGPU_SHIM_STENCIL64(u64, uint64_t)
 #undef RDGPU_SHIM_STENCIL64
+// D-infinity across flats (rdgpu.h "D-infinity across flats"): the D-infinity family's eight element types
+#define RDGPU_SHIM_DINF_FLATS(SUF, T)                                                                      \
+  inline int c_fm_dinf_flats(const T *p, T nd, int w, int h, float *o) { return rdgpu_fm_tarboton_flats_##SUF(p, nd, w, h, o); } \
+  inline int c_fa_dinf_flats(const T *p, T nd, int w, int h, double *a) { return rdgpu_fa_tarboton_flats_##SUF(p, nd, w, h, a); }
+RDGPU_SHIM_DINF_FLATS(u8, uint8_t) RDGPU_SHIM_DINF_FLATS(i8, int8_t) RDGPU_SHIM_DINF_FLATS(u16, uint16_t)
+RDGPU_SHIM_DINF_FLATS(i16, int16_t) RDGPU_SHIM_DINF_FLATS(u32, uint32_t) RDGPU_SHIM_DINF_FLATS(i32, int32_t)
+RDGPU_SHIM_DINF_FLATS(f32, float) RDGPU_SHIM_DINF_FLATS(f64, double)
+#undef RDGPU_SHIM_DINF_FLATS
+template <class T>
+int c_fm_dinf_flats(const T *, T, int, int, float *) { unsupported("FM_Tarboton_flats"); }
+template <class T>
+int c_fa_dinf_flats(const T *, T, int, int, double *) { unsupported("FA_Tarboton_flats"); }
 template <class T>
 int c_flowdirs(const T *, T, int, int, uint8_t *) { unsupported("d8_flow_directions"); }
 template <class T>
@@ -530,6 +542,20 @@ void FA_Tarboton(const E &elevations, G &accum) {
 }
 template <class E, class G>
 void FA_Dinfinity(const E &elevations, G &accum) { FA_Tarboton(elevations, accum); }
+// FA_Tarboton with the cells of drainable flats routed over Barnes' flat mask (no reference counterpart; the rule is in
+// rdgpu.h, "D-infinity across flats").  The DEM is not altered.
+template <class E, class G>
+void FA_Tarboton_flats(const E &elevations, G &accum) {
+  using T = detail::elem_t<E>;
+  accum.setNoData((detail::elem_t<G>)-1);
+  if (accum.width() != elevations.width() || accum.height() != elevations.height())
+    throw std::runtime_error("Accumulation array must have same dimensions as proportions array!");
+  if (elevations.width() == 0 || elevations.height() == 0) return;
+  detail::with_double_accum(accum, [&](double *a) {
+    detail::check(detail::c_fa_dinf_flats((const T *)elevations.data(), elevations.noData(), elevations.width(), elevations.height(), a),
+                  "FA_Tarboton_flats");
+  });
+}
 
 // FA_D8 for a caller that built `accum` as an array of ones itself (apps/rd_flow_accumulation.cpp:13: Array2D<double>
 // accum(dem, 1)) and says so: rdgpu::FA_D8(dem, accum, rdgpu::unit_weights).  accum is then output only -- nothing is read
@@ -610,6 +636,13 @@ void FM_Tarboton(const E &elevations, P &props) {
 }
 template <class E, class P>
 void FM_Dinfinity(const E &elevations, P &props) { FM_Tarboton(elevations, props); }
+// FM_Tarboton across flats (rdgpu.h "D-infinity across flats")
+template <class E, class P>
+void FM_Tarboton_flats(const E &elevations, P &props) {
+  using T = detail::elem_t<E>;
+  detail::fm_into(elevations, props, [](const T *p, T nd, int w, int h, float *o) { return detail::c_fm_dinf_flats(p, nd, w, h, o); },
+                  "FM_Tarboton_flats");
+}
 namespace detail {
 template <class E, class P>
 void fm_mfd(const E &elevations, P &props, int method, double xparam, const char *who) {
@@ -883,6 +916,10 @@ namespace detail {
   inline int c_dinf_dist(const T *z, T nd, int w, int h, const uint8_t *c, int st, int strict, double cx, double cy, double *d, \
                          double *r, double ond) {                                                                           \
     return rdgpu_dinf_distance_down_##SUF(z, nd, w, h, c, st, strict, cx, cy, d, r, ond);                                   \
+  }                                                                                                                         \
+  inline int c_dinf_dist_flats(const T *z, T nd, int w, int h, const uint8_t *c, int st, int strict, double cx, double cy,  \
+                               double *d, double *r, double ond) {                                                          \
+    return rdgpu_dinf_distance_down_flats_##SUF(z, nd, w, h, c, st, strict, cx, cy, d, r, ond);                             \
   }
 RDGPU_SHIM_DINF_DIST(u8, uint8_t) RDGPU_SHIM_DINF_DIST(i8, int8_t) RDGPU_SHIM_DINF_DIST(u16, uint16_t)
 RDGPU_SHIM_DINF_DIST(i16, int16_t) RDGPU_SHIM_DINF_DIST(u32, uint32_t) RDGPU_SHIM_DINF_DIST(i32, int32_t)
@@ -891,6 +928,10 @@ RDGPU_SHIM_DINF_DIST(f32, float) RDGPU_SHIM_DINF_DIST(f64, double)
 template <class T>
 int c_dinf_dist(const T *, T, int, int, const uint8_t *, int, int, double, double, double *, double *, double) {
   unsupported("DinfDistanceDown");
+}
+template <class T>
+int c_dinf_dist_flats(const T *, T, int, int, const uint8_t *, int, int, double, double, double *, double *, double) {
+  unsupported("DinfDistanceDown_flats");
 }
 template <class G>
 double *dist_plane(G *out, int w, int h, double nodata) {
@@ -942,29 +983,52 @@ void FlowDistanceDown(const P &props, G &dist, double cell_x = 1.0, double cell_
 
 // The same over the D-infinity proportions of a DEM (FM_Tarboton, never materialised), elevations and cell lengths
 // (|geotransform[1]|, |geotransform[5]|) the DEM's; the outputs take the DEM's size, geotransform and projection.
-template <class E, class G, class C>
-void DinfDistanceDown(const E &dem, G *dist, G *drop, const C *channels, const DistanceDownOptions &opt = DistanceDownOptions()) {
-  using T = detail::elem_t<E>;
+namespace detail {
+template <class E, class G, class C, class Fn>
+void dinf_distance_down(const E &dem, G *dist, G *drop, const C *channels, const DistanceDownOptions &opt, Fn entry, const char *who) {
+  using T = elem_t<E>;
   const int w = dem.width(), h = dem.height();
-  if (!dist && !drop) throw std::runtime_error("DinfDistanceDown: no output requested");
+  if (!dist && !drop) throw std::runtime_error(std::string(who) + ": no output requested");
   double cx, cy;
-  detail::cell_lengths(dem, "DinfDistanceDown", cx, cy);
-  const uint8_t *mask = detail::dist_mask(w, h, channels, "DinfDistanceDown");
+  cell_lengths(dem, who, cx, cy);
+  const uint8_t *mask = dist_mask(w, h, channels, who);
   for (G *o : {dist, drop})
     if (o) {
-      static_assert(std::is_same<detail::elem_t<G>, double>::value, "DinfDistanceDown: the output rasters must be double");
+      static_assert(std::is_same<elem_t<G>, double>::value, "DinfDistanceDown: the output rasters must be double");
       o->resize(dem);
       o->setNoData(opt.out_nodata);
     }
   if (w == 0 || h == 0) return;
-  detail::check(detail::c_dinf_dist((const T *)dem.data(), (T)dem.noData(), w, h, mask, (int)opt.stat, opt.strict ? 1 : 0, cx, cy,
-                                    dist ? dist->data() : nullptr, drop ? drop->data() : nullptr, opt.out_nodata),
-                "DinfDistanceDown");
+  check(entry((const T *)dem.data(), (T)dem.noData(), w, h, mask, (int)opt.stat, opt.strict ? 1 : 0, cx, cy,
+              dist ? dist->data() : nullptr, drop ? drop->data() : nullptr, opt.out_nodata), who);
+}
+}  // namespace detail
+template <class E, class G, class C>
+void DinfDistanceDown(const E &dem, G *dist, G *drop, const C *channels, const DistanceDownOptions &opt = DistanceDownOptions()) {
+  using T = detail::elem_t<E>;
+  detail::dinf_distance_down(dem, dist, drop, channels, opt,
+                             [](const T *z, T nd, int w, int h, const uint8_t *c, int st, int strict, double cx, double cy, double *d,
+                                double *r, double ond) { return detail::c_dinf_dist(z, nd, w, h, c, st, strict, cx, cy, d, r, ond); },
+                             "DinfDistanceDown");
 }
 // height above the drainage reached over the D-infinity proportions: the drop down to the channel mask
 template <class E, class G, class C>
 void DinfHand(const E &dem, G &hand, const C &channels, const DistanceDownOptions &opt = DistanceDownOptions()) {
   DinfDistanceDown(dem, static_cast<G *>(nullptr), &hand, &channels, opt);
+}
+// Both over the proportions of FM_Tarboton_flats: the drainable flats of the DEM pass flow on (rdgpu.h "D-infinity across
+// flats"); same arguments, statistics and strict rule.
+template <class E, class G, class C>
+void DinfDistanceDown_flats(const E &dem, G *dist, G *drop, const C *channels, const DistanceDownOptions &opt = DistanceDownOptions()) {
+  using T = detail::elem_t<E>;
+  detail::dinf_distance_down(dem, dist, drop, channels, opt,
+                             [](const T *z, T nd, int w, int h, const uint8_t *c, int st, int strict, double cx, double cy, double *d,
+                                double *r, double ond) { return detail::c_dinf_dist_flats(z, nd, w, h, c, st, strict, cx, cy, d, r, ond); },
+                             "DinfDistanceDown_flats");
+}
+template <class E, class G, class C>
+void DinfHand_flats(const E &dem, G &hand, const C &channels, const DistanceDownOptions &opt = DistanceDownOptions()) {
+  DinfDistanceDown_flats(dem, static_cast<G *>(nullptr), &hand, &channels, opt);
 }
 
 // ---- longest upstream flow path on the D8 forest (no reference counterpart; the definition is in rdgpu.h) -----------

@@ -390,10 +390,21 @@ def _method(who: str, method, exponent):
     return kind, code, float(exponent) if (exponent is not None and method in _NEEDS_EXPONENT) else 1.0
 
 
-def FlowProportions(dem: np.ndarray, method: str = "Dinf", nodata=-9999, exponent=None) -> np.ndarray:
+def _flats_kind(who: str, method, kind: str, resolve_flats: bool) -> str:
+    """the C-ABI family of a D-infinity call: across flats (``resolve_flats``) or plain; every other method refuses it"""
+    if not resolve_flats:
+        return kind
+    if kind != "tarboton":
+        raise RdgpuError(f'{who}: resolve_flats=True is available for "Dinf" / "Tarboton" only, not for method "{method}"')
+    return "tarboton_flats"
+
+
+def FlowProportions(dem: np.ndarray, method: str = "Dinf", nodata=-9999, exponent=None, *, resolve_flats: bool = False) -> np.ndarray:
     """[h, w, 9] float32 flow proportions (reference ``rd.FlowProportions`` -> FM_Tarboton / FM_D8 /
-    FM_Holmgren / FM_Freeman / FM_Quinn / FM_D4, flowmet/*.hpp)."""
+    FM_Holmgren / FM_Freeman / FM_Quinn / FM_D4, flowmet/*.hpp).  resolve_flats ("Dinf" / "Tarboton" only): the cells of
+    drainable flats are routed over Barnes' flat mask (fm_tarboton_flats)."""
     kind, code, xp = _method("FlowProportions", method, exponent)
+    kind = _flats_kind("FlowProportions", method, kind, resolve_flats)
     dem, s = _elev(dem, "FlowProportions", mfd=kind != "d8")
     h, w = dem.shape
     out = np.empty((h, w, 9), np.float32)
@@ -401,8 +412,7 @@ def FlowProportions(dem: np.ndarray, method: str = "Dinf", nodata=-9999, exponen
     if kind == "mfd":
         check(getattr(lib(), f"rdgpu_fm_mfd_{s}")(pd, _scalar(s, nodata), w, h, code, ctypes.c_double(xp), po), "rdgpu_fm_mfd")
     else:
-        check(getattr(lib(), f"rdgpu_fm_d8_{s}" if kind == "d8" else f"rdgpu_fm_tarboton_{s}")(pd, _scalar(s, nodata), w, h, po),
-              "rdgpu_fm_" + kind)
+        check(getattr(lib(), f"rdgpu_fm_{kind}_{s}")(pd, _scalar(s, nodata), w, h, po), "rdgpu_fm_" + kind)
     return out
 
 
@@ -424,10 +434,11 @@ def FlowAccumFromProps(props: np.ndarray, weights: np.ndarray | None = None) -> 
     return acc
 
 
-def flow_accumulation_into(dem: np.ndarray, method, nodata, acc: np.ndarray, exponent=None) -> None:
+def flow_accumulation_into(dem: np.ndarray, method, nodata, acc: np.ndarray, exponent=None, *, resolve_flats: bool = False) -> None:
     """FA_<method>(dem, acc): acc (float64, C-contiguous, dem's shape) holds the flow generated per cell on
-    entry and the accumulation on return (methods/flow_accumulation.hpp:16-28)."""
+    entry and the accumulation on return (methods/flow_accumulation.hpp:16-28).  resolve_flats: as FlowProportions."""
     kind, code, xp = _method("FlowAccumulation", method, exponent)
+    kind = _flats_kind("FlowAccumulation", method, kind, resolve_flats)
     dem, s = _elev(dem, "FlowAccumulation", mfd=kind != "d8")
     h, w = dem.shape
     if acc.shape != dem.shape:                     # flow_accumulation_generic.hpp:42-43
@@ -438,18 +449,19 @@ def flow_accumulation_into(dem: np.ndarray, method, nodata, acc: np.ndarray, exp
     if kind == "mfd":
         check(getattr(lib(), f"rdgpu_fa_mfd_{s}")(pd, _scalar(s, nodata), w, h, code, ctypes.c_double(xp), pa), "rdgpu_fa_mfd")
     else:
-        check(getattr(lib(), f"rdgpu_fa_d8_{s}" if kind == "d8" else f"rdgpu_fa_tarboton_{s}")(pd, _scalar(s, nodata), w, h, pa),
-              "rdgpu_fa_" + kind)
+        check(getattr(lib(), f"rdgpu_fa_{kind}_{s}")(pd, _scalar(s, nodata), w, h, pa), "rdgpu_fa_" + kind)
 
 
-def FlowAccumulation(dem: np.ndarray, method: str = "D8", nodata=-9999, weights: np.ndarray | None = None, exponent=None):
+def FlowAccumulation(dem: np.ndarray, method: str = "D8", nodata=-9999, weights: np.ndarray | None = None, exponent=None, *,
+                     resolve_flats: bool = False):
     """Flow accumulation (reference ``rd.FlowAccumulation(dem, method, exponent, weights)``,
     wrappers/pyrichdem/richdem/__init__.py:490-597 -> FA_D8 etc., methods/flow_accumulation.hpp:16-28).
-    Returns float64 accumulation; NoData cells get -1."""
+    Returns float64 accumulation; NoData cells get -1.  resolve_flats: as FlowProportions."""
     if not isinstance(dem, np.ndarray) or dem.ndim != 2:
         raise RdgpuError("FlowAccumulation: expected a 2-D numpy array")
     if weights is None:
         kind, _, _ = _method("FlowAccumulation", method, exponent)
+        _flats_kind("FlowAccumulation", method, kind, resolve_flats)
         if kind == "d8":                           # every cell generates 1 (__init__.py:560-563) and THIS code knows it:
             d, s = _elev(dem, "FlowAccumulation", mfd=False)   # the unit-weights entry neither reads nor uploads an array of ones
             acc = np.empty(d.shape, np.float64)
@@ -461,7 +473,7 @@ def FlowAccumulation(dem: np.ndarray, method: str = "D8", nodata=-9999, weights:
         if weights.shape != dem.shape:             # flow_accumulation_generic.hpp:42-43
             raise RdgpuError("Accumulation array must have same dimensions as proportions array!")
         acc = np.ascontiguousarray(weights, dtype=np.float64).copy()
-    flow_accumulation_into(dem, method, nodata, acc, exponent)
+    flow_accumulation_into(dem, method, nodata, acc, exponent, resolve_flats=resolve_flats)
     return acc
 
 
@@ -1692,26 +1704,40 @@ def mfd_distance_down(props: np.ndarray, chan: np.ndarray | None = None, elev: n
     return out
 
 
-def dinf_distance_down(dem: np.ndarray, nodata, chan: np.ndarray | None = None, stat="ave", strict: bool = True, cell=(1.0, 1.0),
-                       out_nodata: float = -1.0, want=("dist",)) -> dict:
-    """mfd_distance_down over the D-infinity proportions of dem (FM_Tarboton, never materialised), elevations the DEM's."""
-    who = "dinf_distance_down"
+def _dinf_distance_down(who, dem, nodata, chan, stat, strict, cell, out_nodata, want) -> dict:
     dem, s = _elev(dem, who, mfd=True)
     h, w = dem.shape
     chan = _mask2d(chan, (h, w), who)
     want = _dist_want(want, who)
     cx, cy = _cell2(cell, who)
     out = _dist_planes(want, h, w)
-    check(getattr(lib(), f"rdgpu_dinf_distance_down_{s}")(_ptr(dem), _scalar(s, nodata), w, h, _ptr(chan), _dist_stat(stat, who),
-                                                          int(bool(strict)), cx, cy, _ptr(out.get("dist")), _ptr(out.get("drop")),
-                                                          ctypes.c_double(out_nodata)), "rdgpu_dinf_distance_down")
+    check(getattr(lib(), f"rdgpu_{who}_{s}")(_ptr(dem), _scalar(s, nodata), w, h, _ptr(chan), _dist_stat(stat, who), int(bool(strict)),
+                                             cx, cy, _ptr(out.get("dist")), _ptr(out.get("drop")), ctypes.c_double(out_nodata)),
+          "rdgpu_" + who)
     return out
+
+
+def dinf_distance_down(dem: np.ndarray, nodata, chan: np.ndarray | None = None, stat="ave", strict: bool = True, cell=(1.0, 1.0),
+                       out_nodata: float = -1.0, want=("dist",)) -> dict:
+    """mfd_distance_down over the D-infinity proportions of dem (FM_Tarboton, never materialised), elevations the DEM's."""
+    return _dinf_distance_down("dinf_distance_down", dem, nodata, chan, stat, strict, cell, out_nodata, want)
+
+
+def dinf_distance_down_flats(dem: np.ndarray, nodata, chan: np.ndarray | None = None, stat="ave", strict: bool = True,
+                             cell=(1.0, 1.0), out_nodata: float = -1.0, want=("dist",)) -> dict:
+    """dinf_distance_down over the proportions of fm_tarboton_flats: the drainable flats of dem pass flow on."""
+    return _dinf_distance_down("dinf_distance_down_flats", dem, nodata, chan, stat, strict, cell, out_nodata, want)
 
 
 def dinf_hand(dem: np.ndarray, nodata, chan: np.ndarray, stat="ave", strict: bool = True, out_nodata: float = -9999.0) -> np.ndarray:
     """float64 raster: height above the drainage reached over the D-infinity proportions of dem -- the "drop" plane of
     dinf_distance_down with the channel mask chan.  Not clamped."""
     return dinf_distance_down(dem, nodata, chan, stat, strict, (1.0, 1.0), out_nodata, want=("drop",))["drop"]
+
+
+def dinf_hand_flats(dem: np.ndarray, nodata, chan: np.ndarray, stat="ave", strict: bool = True, out_nodata: float = -9999.0) -> np.ndarray:
+    """dinf_hand over the proportions of fm_tarboton_flats."""
+    return dinf_distance_down_flats(dem, nodata, chan, stat, strict, (1.0, 1.0), out_nodata, want=("drop",))["drop"]
 
 
 def mfd_distance_rounds() -> int:
@@ -1754,27 +1780,94 @@ def mfd_distance_down_dev(props, chan=None, elev=None, stat="ave", strict: bool 
           "rdgpu_mfd_distance_down_dev")
 
 
-def dinf_distance_down_dev(dem, nodata, chan=None, stat="ave", strict: bool = True, cell=(1.0, 1.0), out_nodata: float = -1.0,
-                           dist=None, drop=None) -> None:
-    """The planes given (float64 CUDA tensors) <- dinf_distance_down of dem (CUDA tensor of any element type torch has of
-    int8 .. uint32, float32, float64), on torch's current stream.  At least one plane must be given."""
+def _dinf_distance_down_dev(who, entry, dem, nodata, chan, stat, strict, cell, out_nodata, dist, drop) -> None:
     import torch
 
-    who = "dinf_distance_down_dev"
     h, w = _dev2d(dem, who)
     s = _torch_mfd_suffix(dem, who)
     if dist is None and drop is None:
         raise RdgpuError(f"{who}: no output requested")
     cx, cy = _cell2(cell, who)
-    check(getattr(lib(), f"rdgpu_dinf_distance_down_dev_{s}")(ctypes.c_void_p(dem.data_ptr()), _scalar(s, nodata), w, h,
-                                                              _dev_mask(chan, (h, w), who), _dist_stat(stat, who),
-                                                              int(bool(strict)), cx, cy,
-                                                              _dev_plane(dist, (h, w), torch.float64, who),
-                                                              _dev_plane(drop, (h, w), torch.float64, who),
-                                                              ctypes.c_double(out_nodata), _stream_ptr()),
-          "rdgpu_dinf_distance_down_dev")
+    check(getattr(lib(), f"{entry}_{s}")(ctypes.c_void_p(dem.data_ptr()), _scalar(s, nodata), w, h, _dev_mask(chan, (h, w), who),
+                                         _dist_stat(stat, who), int(bool(strict)), cx, cy,
+                                         _dev_plane(dist, (h, w), torch.float64, who), _dev_plane(drop, (h, w), torch.float64, who),
+                                         ctypes.c_double(out_nodata), _stream_ptr()), entry)
+
+
+def dinf_distance_down_dev(dem, nodata, chan=None, stat="ave", strict: bool = True, cell=(1.0, 1.0), out_nodata: float = -1.0,
+                           dist=None, drop=None) -> None:
+    """The planes given (float64 CUDA tensors) <- dinf_distance_down of dem (CUDA tensor of any element type torch has of
+    int8 .. uint32, float32, float64), on torch's current stream.  At least one plane must be given."""
+    _dinf_distance_down_dev("dinf_distance_down_dev", "rdgpu_dinf_distance_down_dev", dem, nodata, chan, stat, strict, cell,
+                            out_nodata, dist, drop)
+
+
+def dinf_distance_down_flats_dev(dem, nodata, chan=None, stat="ave", strict: bool = True, cell=(1.0, 1.0), out_nodata: float = -1.0,
+                                 dist=None, drop=None) -> None:
+    """dinf_distance_down_dev over the proportions of fm_tarboton_flats."""
+    _dinf_distance_down_dev("dinf_distance_down_flats_dev", "rdgpu_dinf_distance_down_flats_dev", dem, nodata, chan, stat, strict,
+                            cell, out_nodata, dist, drop)
 
 
 def dinf_hand_dev(dem, nodata, chan, out, stat="ave", strict: bool = True, out_nodata: float = -9999.0) -> None:
     """out (float64 CUDA tensor) <- dinf_hand of dem and the uint8 CUDA channel mask chan."""
     dinf_distance_down_dev(dem, nodata, chan, stat, strict, (1.0, 1.0), out_nodata, drop=out)
+
+
+def dinf_hand_flats_dev(dem, nodata, chan, out, stat="ave", strict: bool = True, out_nodata: float = -9999.0) -> None:
+    """out (float64 CUDA tensor) <- dinf_hand_flats of dem and the uint8 CUDA channel mask chan."""
+    dinf_distance_down_flats_dev(dem, nodata, chan, stat, strict, (1.0, 1.0), out_nodata, drop=out)
+
+
+# ---- D-infinity across flats (include/rdgpu.h "D-infinity across flats") ---------------------------------------
+class _DinfFlatsStats(ctypes.Structure):
+    _fields_ = [("noflow_cells", ctypes.c_uint64), ("patched_cells", ctypes.c_uint64), ("fallback_cells", ctypes.c_uint64),
+                ("unresolved_cells", ctypes.c_uint64)]
+
+
+def dinf_flats_stats() -> dict:
+    """The counts of this thread's last *_flats call (rdgpu_dinf_flats_get_stats; waits for that call's stream)."""
+    st = _DinfFlatsStats()
+    check(lib().rdgpu_dinf_flats_get_stats(ctypes.byref(st)), "rdgpu_dinf_flats_get_stats")
+    return {k: int(getattr(st, k)) for k, _ in _DinfFlatsStats._fields_}
+
+
+def fm_tarboton_flats(dem: np.ndarray, nodata) -> np.ndarray:
+    """[h, w, 9] float32: FM_Tarboton's proportions with the cells of drainable flats routed over Barnes' flat mask.  The
+    DEM is not altered."""
+    return FlowProportions(dem, "Dinf", nodata=nodata, resolve_flats=True)
+
+
+def fa_tarboton_flats(dem: np.ndarray, nodata, weights: np.ndarray | None = None) -> np.ndarray:
+    """float64 accumulation over the proportions of fm_tarboton_flats (never materialised); NoData cells get -1."""
+    return FlowAccumulation(dem, "Dinf", nodata=nodata, weights=weights, resolve_flats=True)
+
+
+def fm_tarboton_flats_dev(dem, nodata, props9) -> None:
+    """props9 (contiguous float32 CUDA tensor [h, w, 9]) <- fm_tarboton_flats of the CUDA tensor dem, on torch's current
+    stream."""
+    import torch
+
+    who = "fm_tarboton_flats_dev"
+    h, w = _dev2d(dem, who)
+    if props9.dtype != torch.float32 or tuple(props9.shape) != (h, w, 9) or not props9.is_contiguous() or not props9.is_cuda:
+        raise RdgpuError(f"{who}: props9 must be a contiguous float32 CUDA tensor [h, w, 9] of the DEM's raster shape")
+    s = _torch_mfd_suffix(dem, who)
+    check(getattr(lib(), f"rdgpu_fm_tarboton_flats_dev_{s}")(ctypes.c_void_p(dem.data_ptr()), _scalar(s, nodata), w, h,
+                                                             ctypes.c_void_p(props9.data_ptr()), _stream_ptr()),
+          "rdgpu_fm_tarboton_flats_dev")
+
+
+def fa_tarboton_flats_dev(dem, nodata, accum) -> None:
+    """fa_tarboton_dev over the proportions of fm_tarboton_flats: accum (float64 CUDA tensor) in: the cells' weights, out:
+    the accumulation."""
+    import torch
+
+    who = "fa_tarboton_flats_dev"
+    h, w = _dev2d(dem, who)
+    if accum.dtype != torch.float64 or tuple(accum.shape) != (h, w) or not accum.is_contiguous() or not accum.is_cuda:
+        raise RdgpuError(f"{who}: accum must be a contiguous float64 CUDA tensor of the DEM's shape")
+    s = _torch_mfd_suffix(dem, who)
+    check(getattr(lib(), f"rdgpu_fa_tarboton_flats_dev_{s}")(ctypes.c_void_p(dem.data_ptr()), _scalar(s, nodata), w, h,
+                                                             ctypes.c_void_p(accum.data_ptr()), _stream_ptr()),
+          "rdgpu_fa_tarboton_flats_dev")

@@ -24,6 +24,7 @@
 //   * a NO_FLOW cell is in a labelled (drainable) flat  <=>  the towards-BFS reaches it.
 // Labels (union-find roots) are only needed for flat_height[label] = the deepest away level per flat.
 #include "common.hpp"
+#include "flats.hpp"
 #include "flowdirs.hpp"
 
 #include <algorithm>
@@ -2158,8 +2159,8 @@ static uint32_t finish_static(const StaticAway &st, int32_t *D, int nrounds, int
 // Computes flat_mask (M) for the DEM; d_dirs must hold d8_flow_directions output.
 // Returns device pointers (workspace) to M, L, fh through the out parameters (L, fh: null where no flat has an outlet).
 template <class T>
-static void resolve_flats_device(const T *d_z, const uint8_t *d_dirs, int w, int h, int32_t **outM, uint32_t **outL,
-                                 int32_t **outFh, hipStream_t s) {
+void resolve_flats_device(const T *d_z, const uint8_t *d_dirs, int w, int h, int32_t **outM, uint32_t **outL,
+                          int32_t **outFh, hipStream_t s) {
   const uint64_t n = (uint64_t)w * h;
   Workspace &ws = Workspace::get();
   int32_t *M = ws.buf<int32_t>("flats.mask", n);
@@ -2997,6 +2998,11 @@ static void resolve_flats_epsilon_host(T *dem, T nodata, int w, int h) {
 #define RD_INST(T) template void flat_resolution_device<T>(const T *, T, int, int, uint8_t *, hipStream_t);
 RD_INST(uint8_t) RD_INST(int16_t) RD_INST(uint16_t) RD_INST(int32_t) RD_INST(uint32_t) RD_INST(float) RD_INST(double)
 RD_INST(int8_t) RD_INST(int64_t) RD_INST(uint64_t)
+#undef RD_INST
+// the mask and the flat partition for the D-infinity family's element types (flats.hpp; mfd.hip: k_tarboton_flats)
+#define RD_INST(T) \
+  template void resolve_flats_device<T>(const T *, const uint8_t *, int, int, int32_t **, uint32_t **, int32_t **, hipStream_t);
+RD_INST(uint8_t) RD_INST(int8_t) RD_INST(uint16_t) RD_INST(int16_t) RD_INST(uint32_t) RD_INST(int32_t) RD_INST(float) RD_INST(double)
 #undef RD_INST
 
 }  // namespace rdgpu

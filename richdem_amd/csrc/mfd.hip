@@ -8,6 +8,8 @@
 //                                 (methods/flow_accumulation_generic.hpp:33-100) for any proportions array
 //  * rdgpu_fa_tarboton_*          replaces FA_Tarboton / FA_Dinfinity (methods/flow_accumulation.hpp:16-17)
 //                                 without materialising the 36 B/cell array: 5 B/cell (receiver, share)
+//  * rdgpu_fm_tarboton_flats_*    the same two with the cells of drainable flats patched from Barnes' flat mask
+//    rdgpu_fa_tarboton_flats_*    (k_tarboton_flats; no reference counterpart, DESIGN.md "D-infinity across flats")
 //
 // The slope/angle arithmetic is done in double with atan2/sqrt exactly as written in the reference
 // (-ffp-contract=off: no FMA contraction); device libm may differ from glibc in the last ulp of atan2, so
@@ -18,10 +20,13 @@
 // pending-donor count; the receivers it completed are the work list's to continue with (mfd_worklist.hpp).
 // f64 sums in a different order than the reference's FIFO: exact for integer-valued flows, f64 rounding
 // otherwise.
+#include "flats.hpp"
+#include "flowdirs.hpp"
 #include "mfd_worklist.hpp"
 
-namespace rdgpu {
+#include <climits>
 
+namespace rdgpu {
 
 // ------------------------------------------------------------------------------------------
 // D-infinity per cell, on the 3 x 3 window of elevations (rows y-1, y, y+1; columns x-1, x, x+1).
@@ -251,6 +256,109 @@ __global__ __launch_bounds__(NTHR) void k_tarboton_props(const uint8_t *__restri
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// D-infinity across flats (DESIGN.md "D-infinity across flats"): the cells FM_Tarboton leaves without flow inside a
+// drainable flat get their receivers from Barnes' flat mask instead of the elevations.  Runs over k_tarboton's tiles after
+// k_tarboton, the D8 directions and resolve_flats_device (flats.hpp), and writes the patched cells only.
+//   patched: d8 == NO_FLOW and the cell's flat has a low edge (label != 0) -- such a cell is interior and has rcv == 0;
+//   its window: the 3 x 3 mask values, every neighbour of another flat (or of none) replaced by FLAT_OTHER, which goes to
+//   tarboton_cell as the NoData value: the facet rule, thresholds and facet order are FM_Tarboton's;
+//   no descending facet: everything to the first neighbour n = 1..8 of the same flat with a smaller mask value;
+//   none either: the cell stays without flow and is counted.
+// A tile whose interior data cells all have a receiver costs its rcv bytes: one block-wide vote, then the block leaves.
+// ------------------------------------------------------------------------------------------
+constexpr int32_t FLAT_OTHER = INT32_MIN;   // flat_mask values are >= 0
+enum { FC_NOFLOW = 0, FC_PATCHED = 1, FC_FALLBACK = 2, FC_UNRESOLVED = 3, FC_N = 4 };
+
+__global__ __launch_bounds__(NTHR) void k_tarboton_flats(uint8_t *__restrict__ rcv, float *__restrict__ sh1,
+                                                         float *__restrict__ sh2, const uint8_t *__restrict__ d8,
+                                                         const int32_t *__restrict__ M, const uint32_t *__restrict__ L,
+                                                         const int32_t *__restrict__ fh, int w, int h, uint32_t tilesX,
+                                                         uint32_t ntiles, unsigned long long *counts) {
+  __shared__ int32_t sm[DLH_ * DLW_];    // flat_mask with a one-cell halo
+  __shared__ uint32_t sg[DLH_ * DLW_];   // the group: L + 1 where the cell's flat has a low edge, else 0 (k_flat_labels_out)
+  __shared__ uint32_t scnt[FC_N];
+  const uint32_t t = xcd_tile(blockIdx.x, ntiles);
+  if (t >= ntiles) return;
+  const int x0 = (int)(t % tilesX) * DTW, y0 = (int)(t / tilesX) * DTH;
+  const int lx = threadIdx.x & (DTW - 1), yb = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * (DTH / 4);
+  const int gx = x0 + lx;
+  if (threadIdx.x < FC_N) scnt[threadIdx.x] = 0;
+  uint32_t open = 0;   // bit j: the thread's cell of row yb + j is an interior data cell without flow
+  if (gx >= 1 && gx < w - 1) {
+#pragma unroll
+    for (int j = 0; j < DTH / 4; j++) {
+      const int gy = y0 + yb + j;
+      if (gy >= 1 && gy < h - 1 && rcv[(size_t)gy * w + gx] == 0) open |= 1u << j;
+    }
+  }
+  if (!__syncthreads_or(open != 0)) return;
+  uint32_t cnt[FC_N] = {(uint32_t)__builtin_popcount(open), 0, 0, 0};
+  if (L) {   // (null: no flat of the raster has an outlet -- nothing to patch, the cells are counted)
+    constexpr int IPT = (DLH_ * DLW_ + NTHR - 1) / NTHR;
+    int32_t mv[IPT];
+    uint32_t lv[IPT];
+#pragma unroll
+    for (int r = 0; r < IPT; r++) {   // clamped addresses: a patched cell is interior, its window lies inside the raster
+      const int i = min((int)threadIdx.x + r * NTHR, DLH_ * DLW_ - 1);
+      const int ly = i / DLW_, sx = i - ly * DLW_;
+      const size_t c = (size_t)min(max(y0 - 1 + ly, 0), h - 1) * w + min(max(x0 - 1 + sx, 0), w - 1);
+      mv[r] = M[c];
+      lv[r] = L[c];
+    }
+#pragma unroll
+    for (int r = 0; r < IPT; r++) lv[r] = fh[lv[r]] >= 0 ? lv[r] + 1u : 0u;
+#pragma unroll
+    for (int r = 0; r < IPT; r++) {
+      const int i = (int)threadIdx.x + r * NTHR;
+      if (i < DLH_ * DLW_) { sm[i] = mv[r]; sg[i] = lv[r]; }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t rest = open; rest; rest &= rest - 1u) {
+      const int j = __builtin_ctz(rest);
+      const size_t c = (size_t)(y0 + yb + j) * w + gx;
+      const int li = (yb + j + 1) * DLW_ + lx + 1;
+      const uint32_t g0 = sg[li];
+      if (g0 == 0 || d8[c] != 0) continue;
+      cnt[FC_PATCHED]++;
+      int32_t win[3][3];
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int e = 0; e < 3; e++) {
+          const int k = li + (r - 1) * DLW_ + (e - 1);
+          win[r][e] = sg[k] == g0 ? sm[k] : FLAT_OTHER;
+        }
+      int r = 0;
+      float p = 0.0f, q = 0.0f;
+      tarboton_cell<int32_t>(win, FLAT_OTHER, r, p, q);
+      if (r == 0) {
+#pragma unroll
+        for (int n = 8; n >= 1; n--) {   // (descending: the first n in 1..8 wins)
+          const int32_t v = win[1 + mdy(n)][1 + mdx(n)];
+          if (v != FLAT_OTHER && v < win[1][1]) r = n;
+        }
+        if (r == 0) { cnt[FC_UNRESOLVED]++; continue; }
+        p = 1.0f;
+        cnt[FC_FALLBACK]++;
+      }
+      rcv[c] = (uint8_t)r;
+      sh1[c] = p;
+      sh2[c] = q;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < FC_N; k++) {   // per wavefront, per block, one atomic per block and counter
+    uint32_t v = cnt[k];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&scnt[k], v);
+  }
+  __syncthreads();
+  if (threadIdx.x < FC_N && scnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)scnt[threadIdx.x]);
+}
+
 constexpr uint32_t PEND_NODATA = 0xFFFFFFFFu;
 
 // deps, flow_accumulation_generic.hpp:47-58 (donors are interior cells only), + the initial ready flags :61-64
@@ -475,6 +583,48 @@ template DinfAcc tarboton_device<int32_t>(const int32_t *, int32_t, int, int, hi
 template DinfAcc tarboton_device<float>(const float *, float, int, int, hipStream_t);
 template DinfAcc tarboton_device<double>(const double *, double, int, int, hipStream_t);
 
+// the counts of the calling thread's last tarboton_flats_device: copied to pinned words of the thread's own on the call's stream
+struct FlatsCounts {
+  unsigned long long *host = nullptr;
+  hipStream_t stream = nullptr;
+  int device = 0;
+  bool pending = false;
+};
+static thread_local FlatsCounts g_flats_counts;
+
+template <class T>
+DinfAcc tarboton_flats_device(const T *d_z, T nodata, int w, int h, hipStream_t s) {
+  const uint64_t n = (uint64_t)w * h;
+  const DinfAcc a = tarboton_device<T>(d_z, nodata, w, h, s);
+  Workspace &ws = Workspace::get();
+  uint8_t *d8 = ws.buf<uint8_t>("mfd.flats_d8", n);
+  flowdirs_device<T>(d_z, nodata, w, h, d8, MODE_D8, s);
+  int32_t *M, *fh;
+  uint32_t *L;
+  resolve_flats_device<T>(d_z, d8, w, h, &M, &L, &fh, s);
+  unsigned long long *counts = ws.buf<unsigned long long>("mfd.flats_counts", FC_N);
+  RD_HIP(hipMemsetAsync(counts, 0, FC_N * sizeof(unsigned long long), s));
+  const uint32_t dtilesX = (w + DTW - 1) / DTW, dntiles = dtilesX * ((h + DTH - 1) / DTH);
+  RD_LAUNCH("mfd.tarboton_flats", k_tarboton_flats, dim3(xcd_grid(dntiles)), dim3(NTHR), 0, s, const_cast<uint8_t *>(a.rcv),
+            const_cast<float *>(a.sh1), const_cast<float *>(a.sh2), (const uint8_t *)d8, (const int32_t *)M, (const uint32_t *)L,
+            (const int32_t *)fh, w, h, dtilesX, dntiles, counts);
+  FlatsCounts &fc = g_flats_counts;
+  if (!fc.host) RD_HIP(hipHostMalloc((void **)&fc.host, FC_N * sizeof(unsigned long long), hipHostMallocDefault));
+  RD_HIP(hipGetDevice(&fc.device));
+  fc.stream = s;
+  fc.pending = true;
+  RD_HIP(hipMemcpyAsync(fc.host, counts, FC_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  return a;
+}
+template DinfAcc tarboton_flats_device<uint8_t>(const uint8_t *, uint8_t, int, int, hipStream_t);   // (mfd_distance.hip)
+template DinfAcc tarboton_flats_device<int8_t>(const int8_t *, int8_t, int, int, hipStream_t);
+template DinfAcc tarboton_flats_device<uint16_t>(const uint16_t *, uint16_t, int, int, hipStream_t);
+template DinfAcc tarboton_flats_device<int16_t>(const int16_t *, int16_t, int, int, hipStream_t);
+template DinfAcc tarboton_flats_device<uint32_t>(const uint32_t *, uint32_t, int, int, hipStream_t);
+template DinfAcc tarboton_flats_device<int32_t>(const int32_t *, int32_t, int, int, hipStream_t);
+template DinfAcc tarboton_flats_device<float>(const float *, float, int, int, hipStream_t);
+template DinfAcc tarboton_flats_device<double>(const double *, double, int, int, hipStream_t);
+
 }  // namespace rdgpu
 
 using namespace rdgpu;
@@ -548,7 +698,87 @@ RD_MFD_API(f32, float)
 RD_MFD_API(f64, double)
 RD_MFD_API(i8, int8_t)
 
-#define RD_MFD2_API(SUF, T)                                                                                     \
+// D-infinity across flats: FM_Tarboton / FA_Tarboton with the cells of drainable flats patched from the flat mask
+#define RD_MFD_FLATS_API(SUF, T)                                                                                \
+  extern "C" int rdgpu_fm_tarboton_flats_dev_##SUF(const T *d_dem, T nodata, int w, int h, float *d_props9, void *st) { \
+    return guarded([&] {                                                                                        \
+      if (!d_dem || !d_props9) throw Error(RDGPU_ERR_ARG, "rdgpu_fm_tarboton_flats: null pointer");             \
+      check_dims(w, h, "rdgpu_fm_tarboton_flats", FLATS_MAX_CELLS);                                             \
+      const DinfAcc a = tarboton_flats_device<T>(d_dem, nodata, w, h, (hipStream_t)st);                         \
+      const uint64_t n = (uint64_t)w * h;                                                                       \
+      RD_LAUNCH("mfd.tarboton_props", k_tarboton_props, dim3(sgrid(n)), dim3(NTHR), 0, (hipStream_t)st, a.rcv, a.sh1, \
+                a.sh2, d_props9, n);                                                                            \
+    });                                                                                                         \
+  }                                                                                                             \
+  extern "C" int rdgpu_fm_tarboton_flats_##SUF(const T *dem, T nodata, int w, int h, float *props9) {           \
+    return guarded([&] {                                                                                        \
+      if (!dem || !props9) throw Error(RDGPU_ERR_ARG, "rdgpu_fm_tarboton_flats: null pointer");                 \
+      check_dims(w, h, "rdgpu_fm_tarboton_flats", FLATS_MAX_CELLS);                                             \
+      T *d;                                                                                                     \
+      host_dem<T>(dem, w, h, &d);                                                                               \
+      const DinfAcc a = tarboton_flats_device<T>(d, nodata, w, h, nullptr);                                     \
+      const uint64_t n = (uint64_t)w * h;                                                                       \
+      float *p = Workspace::get().buf<float>("host.props", n * 9);                                              \
+      RD_LAUNCH("mfd.tarboton_props", k_tarboton_props, dim3(sgrid(n)), dim3(NTHR), 0, (hipStream_t) nullptr, a.rcv, a.sh1, \
+                a.sh2, p, n);                                                                                   \
+      RD_HIP(hipMemcpy(props9, p, n * 36, hipMemcpyDeviceToHost));                                              \
+    });                                                                                                         \
+  }                                                                                                             \
+  extern "C" int rdgpu_fa_tarboton_flats_dev_##SUF(const T *d_dem, T nodata, int w, int h, double *d_accum, void *st) { \
+    return guarded([&] {                                                                                        \
+      if (!d_dem || !d_accum) throw Error(RDGPU_ERR_ARG, "rdgpu_fa_tarboton_flats: null pointer");              \
+      check_dims(w, h, "rdgpu_fa_tarboton_flats", FLATS_MAX_CELLS);                                             \
+      const DinfAcc a = tarboton_flats_device<T>(d_dem, nodata, w, h, (hipStream_t)st);                         \
+      mfd_accumulate<DinfAcc>(a, w, h, d_accum, (hipStream_t)st);                                               \
+    });                                                                                                         \
+  }                                                                                                             \
+  extern "C" int rdgpu_fa_tarboton_flats_##SUF(const T *dem, T nodata, int w, int h, double *accum) {           \
+    return guarded([&] {                                                                                        \
+      if (!dem || !accum) throw Error(RDGPU_ERR_ARG, "rdgpu_fa_tarboton_flats: null pointer");                  \
+      check_dims(w, h, "rdgpu_fa_tarboton_flats", FLATS_MAX_CELLS);                                             \
+      T *d;                                                                                                     \
+      host_dem<T>(dem, w, h, &d);                                                                               \
+      const size_t n = (size_t)w * h;                                                                           \
+      double *da = Workspace::get().buf<double>("host.area", n);                                                \
+      RD_HIP(hipMemcpy(da, accum, n * 8, hipMemcpyHostToDevice));                                               \
+      const DinfAcc a = tarboton_flats_device<T>(d, nodata, w, h, nullptr);                                     \
+      mfd_accumulate<DinfAcc>(a, w, h, da, nullptr);                                                            \
+      RD_HIP(hipStreamSynchronize(nullptr));                                                                    \
+      RD_HIP(hipMemcpy(accum, da, n * 8, hipMemcpyDeviceToHost));                                               \
+    });                                                                                                         \
+  }
+RD_MFD_FLATS_API(u8, uint8_t)
+RD_MFD_FLATS_API(i8, int8_t)
+RD_MFD_FLATS_API(u16, uint16_t)
+RD_MFD_FLATS_API(i16, int16_t)
+RD_MFD_FLATS_API(u32, uint32_t)
+RD_MFD_FLATS_API(i32, int32_t)
+RD_MFD_FLATS_API(f32, float)
+RD_MFD_FLATS_API(f64, double)
+
+extern "C" int rdgpu_dinf_flats_get_stats(rdgpu_dinf_flats_stats *out) {
+  return guarded([&] {
+    if (!out) throw Error(RDGPU_ERR_ARG, "rdgpu_dinf_flats_get_stats: null pointer");
+    *out = rdgpu_dinf_flats_stats{0, 0, 0, 0};
+    FlatsCounts &fc = g_flats_counts;
+    if (!fc.host) return;   // no call on this thread yet
+    if (fc.pending) {
+      int cur = 0;
+      RD_HIP(hipGetDevice(&cur));
+      if (cur != fc.device) RD_HIP(hipSetDevice(fc.device));
+      const hipError_t e = hipStreamSynchronize(fc.stream);
+      if (cur != fc.device) (void)hipSetDevice(cur);
+      RD_HIP(e);
+      fc.pending = false;
+    }
+    out->noflow_cells = fc.host[FC_NOFLOW];
+    out->patched_cells = fc.host[FC_PATCHED];
+    out->fallback_cells = fc.host[FC_FALLBACK];
+    out->unresolved_cells = fc.host[FC_UNRESOLVED];
+  });
+}
+
+#define RD_MFD2_API(SUF, T)                                                                                    \
   extern "C" int rdgpu_fm_mfd_dev_##SUF(const T *d_dem, T nodata, int w, int h, int method, double xparam,      \
                                         float *d_props9, void *st) {                                            \
     return guarded([&] {                                                                                        \

@@ -2,6 +2,7 @@
 //
 //  * rdgpu_mfd_distance_down[_dev]          any 9-float proportions array (PropsAcc)
 //  * rdgpu_dinf_distance_down[_dev]_<T>     D-infinity from a DEM in compact form (DinfAcc, 5 B/cell), elevations the DEM's
+//  * rdgpu_dinf_distance_down_flats[_dev]_<T>  the same with the cells of drainable flats patched from the flat mask (mfd.hip)
 //  * rdgpu_mfd_distance_rounds              work-list launches of the last call
 //
 // include/rdgpu.h states the definition.  The graph is the accumulation's (mfd.hip) run the other way: a cell is final
@@ -210,8 +211,8 @@ struct DistParams {
 };
 
 static void check_args(const char *who, int w, int h, bool have_elev, int stat, double cx, double cy, const void *dist,
-                       const void *drop) {
-  check_dims(w, h, who);
+                       const void *drop, uint64_t max_cells = 0xFFFF0000ull) {
+  check_dims(w, h, who, max_cells);
   if (!dist && !drop) throw Error(RDGPU_ERR_ARG, std::string(who) + ": no output requested");
   if (drop && !have_elev) throw Error(RDGPU_ERR_ARG, std::string(who) + ": drop needs the elevations");
   if (stat < 0 || stat > 2) throw Error(RDGPU_ERR_ARG, std::string(who) + ": stat must be 0 (average), 1 (minimum) or 2 (maximum)");
@@ -325,41 +326,49 @@ extern "C" int rdgpu_mfd_distance_rounds(uint32_t *rounds) {
   return RDGPU_OK;
 }
 
-#define RD_DINF_DIST_API(SUF, T)                                                                                          \
-  extern "C" int rdgpu_dinf_distance_down_dev_##SUF(const T *d_dem, T nodata, int w, int h, const uint8_t *d_chan, int stat, \
+#define RD_DINF_DIST_API(FL, ACCESSOR, MAXC, SUF, T)                                                                      \
+  extern "C" int rdgpu_dinf_distance_down##FL##_dev_##SUF(const T *d_dem, T nodata, int w, int h, const uint8_t *d_chan, int stat, \
                                                     int strict, double cell_x, double cell_y, double *d_dist, double *d_drop, \
                                                     double out_nodata, void *st) {                                        \
     return guarded([&] {                                                                                                  \
-      if (!d_dem) throw Error(RDGPU_ERR_ARG, "rdgpu_dinf_distance_down: null pointer");                                   \
-      check_args("rdgpu_dinf_distance_down", w, h, true, stat, cell_x, cell_y, d_dist, d_drop);                           \
-      const DinfAcc a = tarboton_device<T>(d_dem, nodata, w, h, (hipStream_t)st);                                         \
+      if (!d_dem) throw Error(RDGPU_ERR_ARG, "rdgpu_dinf_distance_down" #FL ": null pointer");                            \
+      check_args("rdgpu_dinf_distance_down" #FL, w, h, true, stat, cell_x, cell_y, d_dist, d_drop, MAXC);                 \
+      const DinfAcc a = ACCESSOR<T>(d_dem, nodata, w, h, (hipStream_t)st);                                                \
       const double *e = d_drop ? elev_plane<T>(d_dem, (uint64_t)w * h, (hipStream_t)st) : nullptr;                        \
       mfd_distance<DinfAcc>(a, w, h, d_chan, e, DistParams{stat, strict, cell_x, cell_y}, d_dist, d_drop, out_nodata,     \
                             (hipStream_t)st);                                                                             \
     });                                                                                                                   \
   }                                                                                                                       \
-  extern "C" int rdgpu_dinf_distance_down_##SUF(const T *dem, T nodata, int w, int h, const uint8_t *chan, int stat,      \
+  extern "C" int rdgpu_dinf_distance_down##FL##_##SUF(const T *dem, T nodata, int w, int h, const uint8_t *chan, int stat, \
                                                 int strict, double cell_x, double cell_y, double *dist, double *drop,     \
                                                 double out_nodata) {                                                      \
     return guarded([&] {                                                                                                  \
-      if (!dem) throw Error(RDGPU_ERR_ARG, "rdgpu_dinf_distance_down: null pointer");                                     \
-      check_args("rdgpu_dinf_distance_down", w, h, true, stat, cell_x, cell_y, dist, drop);                               \
+      if (!dem) throw Error(RDGPU_ERR_ARG, "rdgpu_dinf_distance_down" #FL ": null pointer");                              \
+      check_args("rdgpu_dinf_distance_down" #FL, w, h, true, stat, cell_x, cell_y, dist, drop, MAXC);                     \
       const size_t n = (size_t)w * h;                                                                                     \
       T *d;                                                                                                               \
       host_dem<T>(dem, w, h, &d);                                                                                         \
       const HostPlanes hp(chan, dist != nullptr, drop != nullptr, n);                                                     \
-      const DinfAcc a = tarboton_device<T>(d, nodata, w, h, nullptr);                                                     \
+      const DinfAcc a = ACCESSOR<T>(d, nodata, w, h, nullptr);                                                            \
       const double *e = drop ? elev_plane<T>(d, n, nullptr) : nullptr;                                                    \
       mfd_distance<DinfAcc>(a, w, h, hp.chan, e, DistParams{stat, strict, cell_x, cell_y}, hp.dist, hp.drop, out_nodata,  \
                             nullptr);                                                                                     \
       hp.fetch(dist, drop, n);                                                                                            \
     });                                                                                                                   \
   }
-RD_DINF_DIST_API(u8, uint8_t)
-RD_DINF_DIST_API(i16, int16_t)
-RD_DINF_DIST_API(u16, uint16_t)
-RD_DINF_DIST_API(i32, int32_t)
-RD_DINF_DIST_API(u32, uint32_t)
-RD_DINF_DIST_API(f32, float)
-RD_DINF_DIST_API(f64, double)
-RD_DINF_DIST_API(i8, int8_t)
+RD_DINF_DIST_API(, tarboton_device, 0xFFFF0000ull, u8, uint8_t)
+RD_DINF_DIST_API(_flats, tarboton_flats_device, FLATS_MAX_CELLS, u8, uint8_t)
+RD_DINF_DIST_API(, tarboton_device, 0xFFFF0000ull, i16, int16_t)
+RD_DINF_DIST_API(_flats, tarboton_flats_device, FLATS_MAX_CELLS, i16, int16_t)
+RD_DINF_DIST_API(, tarboton_device, 0xFFFF0000ull, u16, uint16_t)
+RD_DINF_DIST_API(_flats, tarboton_flats_device, FLATS_MAX_CELLS, u16, uint16_t)
+RD_DINF_DIST_API(, tarboton_device, 0xFFFF0000ull, i32, int32_t)
+RD_DINF_DIST_API(_flats, tarboton_flats_device, FLATS_MAX_CELLS, i32, int32_t)
+RD_DINF_DIST_API(, tarboton_device, 0xFFFF0000ull, u32, uint32_t)
+RD_DINF_DIST_API(_flats, tarboton_flats_device, FLATS_MAX_CELLS, u32, uint32_t)
+RD_DINF_DIST_API(, tarboton_device, 0xFFFF0000ull, f32, float)
+RD_DINF_DIST_API(_flats, tarboton_flats_device, FLATS_MAX_CELLS, f32, float)
+RD_DINF_DIST_API(, tarboton_device, 0xFFFF0000ull, f64, double)
+RD_DINF_DIST_API(_flats, tarboton_flats_device, FLATS_MAX_CELLS, f64, double)
+RD_DINF_DIST_API(, tarboton_device, 0xFFFF0000ull, i8, int8_t)
+RD_DINF_DIST_API(_flats, tarboton_flats_device, FLATS_MAX_CELLS, i8, int8_t)

@@ -40,10 +40,17 @@ struct DinfAcc {    // compact D-infinity form
 template <class T>
 DinfAcc tarboton_device(const T *d_z, T nodata, int w, int h, hipStream_t s);
 
-static inline void check_dims(int w, int h, const char *who) {
+// The same planes with the cells of drainable flats patched from Barnes' flat mask (mfd.hip: k_tarboton_flats; the rule is
+// in DESIGN.md): tarboton_device, d8 directions and resolve_flats_device (flats.hpp) run first.  Synchronises s (the flat
+// resolution reads counts back).  The four counts of rdgpu_dinf_flats_get_stats are this call's.
+template <class T>
+DinfAcc tarboton_flats_device(const T *d_z, T nodata, int w, int h, hipStream_t s);
+
+static inline void check_dims(int w, int h, const char *who, uint64_t max_cells = 0xFFFF0000ull) {
   if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, std::string(who) + ": width and height must be positive");
-  if ((uint64_t)w * (uint64_t)h > 0xFFFF0000ull) throw Error(RDGPU_ERR_ARG, std::string(who) + ": raster too large");
+  if ((uint64_t)w * (uint64_t)h > max_cells) throw Error(RDGPU_ERR_ARG, std::string(who) + ": raster too large");
 }
+constexpr uint64_t FLATS_MAX_CELLS = 0x7FFF0000ull;   // the flat resolution's limit: the smaller of the two engines'
 
 template <class T>
 static void host_dem(const T *dem, int w, int h, T **d) {

@@ -154,45 +154,50 @@ def _accum_array(like, weights, in_place: bool):
     return accum
 
 
-def FlowAccumulation(dem, method=None, exponent=None, weights=None, in_place: bool = False, nodata=None):
+def FlowAccumulation(dem, method=None, exponent=None, weights=None, in_place: bool = False, nodata=None, *,
+                     resolve_flats: bool = False):
     """Flow accumulation by ``method`` (reference __init__.py:490-597).  Methods: D8 / OCallaghanD8, D4 /
     OCallaghanD4, Dinf / Tarboton, Quinn, Holmgren(E), Freeman(E); the randomised Rho8/Rho4 family is refused.
-    Returns the accumulation rdarray (a view of ``weights`` when ``in_place``)."""
+    Returns the accumulation rdarray (a view of ``weights`` when ``in_place``).  resolve_flats (not in the reference;
+    Dinf / Tarboton only, RdgpuError otherwise): drainable flats pass flow on over Barnes' flat mask, the DEM is not
+    altered."""
     if type(dem) is not rdarray:
         if isinstance(dem, np.ndarray) and type(dem) is np.ndarray:
-            return _api.FlowAccumulation(dem, method="D8" if method is None else method,
-                                         nodata=-9999 if nodata is None else nodata, weights=weights, exponent=exponent)
+            return _api.FlowAccumulation(dem, method="D8" if method is None else method, nodata=-9999 if nodata is None else nodata,
+                                         weights=weights, exponent=exponent, resolve_flats=resolve_flats)
         raise Exception("A richdem.rdarray or numpy.ndarray is required!")
     accum = _accum_array(dem, weights, in_place)
     _add_analysis(accum, "FlowAccumulation(dem, method={method}, exponent={exponent}, weights={weights}, in_place={in_place})".format(
         method=method, exponent=exponent, weights="None" if weights is None else "weights", in_place=in_place))
     try:
-        _api._method("FlowAccumulation", method, exponent)
+        kind, _, _ = _api._method("FlowAccumulation", method, exponent)
     except RdgpuError as e:
         raise Exception(str(e)) from None
+    _api._flats_kind("FlowAccumulation", method, kind, resolve_flats)
     acc = _plain(accum)
     if acc.flags["C_CONTIGUOUS"]:
-        _api.flow_accumulation_into(_plain(dem), method, _nodata_of(dem), acc, exponent)
+        _api.flow_accumulation_into(_plain(dem), method, _nodata_of(dem), acc, exponent, resolve_flats=resolve_flats)
     else:
         tmp = np.ascontiguousarray(acc)
-        _api.flow_accumulation_into(_plain(dem), method, _nodata_of(dem), tmp, exponent)
+        _api.flow_accumulation_into(_plain(dem), method, _nodata_of(dem), tmp, exponent, resolve_flats=resolve_flats)
         acc[...] = tmp
     accum.no_data = -1.0     # copyFromWrapped: accum.setNoData(ACCUM_NO_DATA), flow_accumulation_generic.hpp:40
     return accum
 
 
-def FlowProportions(dem, method=None, exponent=None, nodata=None):
-    """Flow proportions [h, w, 9] by ``method`` (reference __init__.py:650-732)."""
+def FlowProportions(dem, method=None, exponent=None, nodata=None, *, resolve_flats: bool = False):
+    """Flow proportions [h, w, 9] by ``method`` (reference __init__.py:650-732).  resolve_flats: as FlowAccumulation."""
     if type(dem) is not rdarray:
         if isinstance(dem, np.ndarray) and type(dem) is np.ndarray:
-            return _api.FlowProportions(dem, method="Dinf" if method is None else method,
-                                        nodata=-9999 if nodata is None else nodata, exponent=exponent)
+            return _api.FlowProportions(dem, method="Dinf" if method is None else method, nodata=-9999 if nodata is None else nodata,
+                                        exponent=exponent, resolve_flats=resolve_flats)
         raise Exception("A richdem.rdarray or numpy.ndarray is required!")
     try:
-        _api._method("FlowProportions", method, exponent)
+        kind, _, _ = _api._method("FlowProportions", method, exponent)
     except RdgpuError as e:
         raise Exception(str(e)) from None
-    props = _api.FlowProportions(_plain(dem), method=method, nodata=_nodata_of(dem), exponent=exponent)
+    _api._flats_kind("FlowProportions", method, kind, resolve_flats)
+    props = _api.FlowProportions(_plain(dem), method=method, nodata=_nodata_of(dem), exponent=exponent, resolve_flats=resolve_flats)
     fprops = rd3array(props, meta_obj=dem, no_data=-2)
     _add_analysis(fprops, f"FlowProportions(dem, method={method}, exponent={exponent})")
     fprops.no_data = -2.0

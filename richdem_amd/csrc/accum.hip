@@ -905,10 +905,15 @@ __global__ __launch_bounds__(NTHR) void k_acc_nodata_f64(const uint8_t *__restri
 // ---- drivers --------------------------------------------------------------------------------
 static inline uint32_t sgrid(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + NTHR - 1) / NTHR, 256u * 32u); }
 
+// the argument checks of an entry's two doors (host pointers, device pointers): thrown before anything is staged
+static void accum_check_args(const void *in, const void *out, int w, int h, const char *who) {
+  if (!in || !out) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
+  check_forest_dims(w, h, who);
+}
+
 template <class A>
 void d8_flow_accum_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, A *d_area, hipStream_t s) {
-  if (!d_dirs || !d_area) throw Error(RDGPU_ERR_ARG, "rdgpu_d8_flow_accum: null pointer");
-  check_forest_dims(w, h, "rdgpu_d8_flow_accum");
+  accum_check_args(d_dirs, d_area, w, h, "rdgpu_d8_flow_accum");
   const uint64_t n = (uint64_t)w * h;
   const char *env = getenv("RDGPU_ACCUM_LINKS");   // =0: the raster-wide walk (what the row-block shards run); A/B and tests
   if (!(env && env[0] == '0')) {
@@ -1026,8 +1031,7 @@ void flow_accum_f64_device(const uint8_t *d_dirs, int w, int h, double *d_acc, h
 // neither read (k_acc_not_all_ones: 12.8 GB at S3) nor, on the host path, uploaded (12.8 GB over PCIe)
 template <class T>
 void fa_d8_device(const T *d_z, T nodata, int w, int h, double *d_acc, hipStream_t s, bool unit_weights = false) {
-  if (!d_z || !d_acc) throw Error(RDGPU_ERR_ARG, "rdgpu_fa_d8: null pointer");
-  check_forest_dims(w, h, "rdgpu_fa_d8");
+  accum_check_args(d_z, d_acc, w, h, "rdgpu_fa_d8");
   Workspace &ws = Workspace::get();
   uint8_t *dirs = ws.buf<uint8_t>("accum.fmdirs", (size_t)w * h);
   // the one read of the weights runs on the side stream while the directions are made on the caller's
@@ -1054,29 +1058,24 @@ void fa_d8_device(const T *d_z, T nodata, int w, int h, double *d_acc, hipStream
 
 template <class A>
 static void d8_flow_accum_host(const uint8_t *dirs, uint8_t nodata, int w, int h, A *area) {
-  if (!dirs || !area) throw Error(RDGPU_ERR_ARG, "rdgpu_d8_flow_accum: null pointer");
-  check_forest_dims(w, h, "rdgpu_d8_flow_accum");
+  accum_check_args(dirs, area, w, h, "rdgpu_d8_flow_accum");
   const size_t n = (size_t)w * h;
-  uint8_t *dd = Workspace::get().buf<uint8_t>("host.dirs", n);
-  A *da = Workspace::get().buf<A>("host.area", n);
-  RD_HIP(hipMemcpy(dd, dirs, n, hipMemcpyHostToDevice));
+  HostStage st;
+  const uint8_t *dd = st.in("host.dirs", dirs, n);
+  A *da = st.out("host.area", area, n);
   d8_flow_accum_device<A>(dd, nodata, w, h, da, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(area, da, n * sizeof(A), hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 template <class T>
 static void fa_d8_host(const T *dem, T nodata, int w, int h, double *accum, bool unit_weights = false) {
-  if (!dem || !accum) throw Error(RDGPU_ERR_ARG, "rdgpu_fa_d8: null pointer");
-  check_forest_dims(w, h, "rdgpu_fa_d8");
+  accum_check_args(dem, accum, w, h, "rdgpu_fa_d8");
   const size_t n = (size_t)w * h;
-  T *d = Workspace::get().buf<T>("host.dem", n);
-  double *da = Workspace::get().buf<double>("host.area", n);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
-  if (!unit_weights) RD_HIP(hipMemcpy(da, accum, n * sizeof(double), hipMemcpyHostToDevice));
+  HostStage st;
+  const T *d = st.in("host.dem", dem, n);
+  double *da = st.inout("host.area", accum, n, !unit_weights);   // (declared ones: output only, no upload)
   fa_d8_device<T>(d, nodata, w, h, da, nullptr, unit_weights);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(accum, da, n * sizeof(double), hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1513,17 +1512,16 @@ __global__ __launch_bounds__(256) void k_fm_props(const uint8_t *__restrict__ di
 
 template <class T>
 static void fm_d8_host(const T *dem, T nodata, int w, int h, float *props9) {
-  if (!dem || !props9) throw rdgpu::Error(RDGPU_ERR_ARG, "rdgpu_fm_d8: null pointer");
-  rdgpu::check_forest_dims(w, h, "rdgpu_fm_d8");
+  rdgpu::accum_check_args(dem, props9, w, h, "rdgpu_fm_d8");
   const size_t n = (size_t)w * h;
-  T *d = rdgpu::Workspace::get().buf<T>("host.dem", n);
+  rdgpu::HostStage st;
+  const T *d = st.in("host.dem", dem, n);
   uint8_t *dirs = rdgpu::Workspace::get().buf<uint8_t>("accum.fmdirs", n);
-  float *p = rdgpu::Workspace::get().buf<float>("host.props", n * 9);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
+  float *p = st.out("host.props", props9, n * 9);
   rdgpu::flowdirs_device<T>(d, nodata, w, h, dirs, rdgpu::MODE_FM, nullptr);
   RD_LAUNCH("accum.fm_props", k_fm_props, dim3(rdgpu::sgrid(n)), dim3(256), 0, (hipStream_t) nullptr, (const uint8_t *)dirs, p,
             (uint64_t)n);
-  RD_HIP(hipMemcpy(props9, p, n * 36, hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 #define RD_FA_API(SUF, T)                                                                                    \

@@ -276,15 +276,12 @@ static void weighted_host(const uint8_t *dirs, uint8_t nodata, const W *weights,
   typedef typename AwSum<W>::S S;
   aw_check_args(dirs, weights, sum, w, h, who);
   const size_t n = (size_t)w * h;
-  Workspace &ws = Workspace::get();
-  uint8_t *dd = ws.buf<uint8_t>("host.dirs", n);
-  W *dw = ws.buf<W>("host.accum_weighted.weights", n);
-  S *ds = ws.buf<S>("host.accum_weighted.sum", n);
-  RD_HIP(hipMemcpy(dd, dirs, n, hipMemcpyHostToDevice));
-  RD_HIP(hipMemcpy(dw, weights, n * sizeof(W), hipMemcpyHostToDevice));
+  HostStage st;
+  const uint8_t *dd = st.in("host.dirs", dirs, n);
+  const W *dw = st.in("host.accum_weighted.weights", weights, n);
+  S *ds = st.out("host.accum_weighted.sum", sum, n);
   weighted_device<W>(dd, nodata, dw, weight_nodata, w, h, ds, sum_nodata, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(sum, ds, n * sizeof(S), hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 static void tlen_check_args(const void *dirs, int w, int h, double cx, double cy, const void *steps, const void *length,
@@ -317,15 +314,12 @@ static void tlen_host(const uint8_t *dirs, uint8_t nodata, int w, int h, double 
                       double length_nodata, const char *who) {
   tlen_check_args(dirs, w, h, cx, cy, steps, length, who);
   const size_t n = (size_t)w * h;
-  Workspace &ws = Workspace::get();
-  uint8_t *dd = ws.buf<uint8_t>("host.dirs", n);
-  uint32_t *dst = steps ? ws.buf<uint32_t>("host.accum_weighted.steps", 3 * n) : nullptr;
-  double *dl = length ? ws.buf<double>("host.accum_weighted.length", n) : nullptr;
-  RD_HIP(hipMemcpy(dd, dirs, n, hipMemcpyHostToDevice));
+  HostStage st;
+  const uint8_t *dd = st.in("host.dirs", dirs, n);
+  uint32_t *dst = st.out("host.accum_weighted.steps", steps, 3 * n);
+  double *dl = st.out("host.accum_weighted.length", length, n);
   tlen_device(dd, nodata, w, h, cx, cy, dst, dl, length_nodata, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  if (steps) RD_HIP(hipMemcpy(steps, dst, 3 * n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (length) RD_HIP(hipMemcpy(length, dl, n * sizeof(double), hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 }  // namespace rdgpu

@@ -140,6 +140,60 @@ private:
 };
 
 // ------------------------------------------------------------------------------------------
+// One host-pointer call: the caller's arrays up into the workspace's named buffers, the device driver on the null stream,
+// the results down.  Every host entry point is "check arguments, stage, run the driver its _dev twin runs, finish()".
+// The copies are blocking hipMemcpy from / to the caller's pageable memory (registering the caller's buffer loses:
+// bench.py, end_to_end_host).  Names and element counts are the caller's: "host.dem", "host.dirs", "host.area",
+// "host.props" and "host.terrain" are shared between entries so that the pool does not hold one raster per product.
+// Nothing is copied down unless finish() is reached: a driver that throws leaves the caller's arrays untouched.
+// ------------------------------------------------------------------------------------------
+class HostStage {
+public:
+  // an input: uploaded now.  A null host pointer (an optional plane left out) takes no buffer and gives null.
+  template <class T>
+  T *in(const char *name, const T *host, size_t count) {
+    if (!host) return nullptr;
+    T *d = ws_.buf<T>(name, count);
+    RD_HIP(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return d;
+  }
+  // an output: copied down by finish().  Null as for in().
+  template <class T>
+  T *out(const char *name, T *host, size_t count) {
+    return inout(name, host, count, false);
+  }
+  // an array that is both, in ONE buffer; upload = false where the driver writes every element before it reads any
+  template <class T>
+  T *inout(const char *name, T *host, size_t count, bool upload = true) {
+    if (!host) return nullptr;
+    T *d = ws_.buf<T>(name, count);
+    if (upload) RD_HIP(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
+    down_.push_back({host, d, count * sizeof(T)});
+    return d;
+  }
+  // waits for the null stream, then downloads the outputs in the order they were registered
+  void finish() {
+    RD_HIP(hipStreamSynchronize(nullptr));
+    for (const Down &d : down_) RD_HIP(hipMemcpy(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost));
+    down_.clear();
+  }
+  // after finish(): a download whose length is only known then (a table cut to the count read back)
+  template <class T>
+  void fetch(T *host, const T *dev, size_t count) {
+    if (count) RD_HIP(hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost));
+  }
+
+private:
+  struct Down {
+    void *host;
+    const void *dev;
+    size_t bytes;
+  };
+  Workspace &ws_ = Workspace::get();
+  std::vector<Down> down_;
+};
+
+// ------------------------------------------------------------------------------------------
 // one host thread per device (the single-process multi-device entry points)
 // ------------------------------------------------------------------------------------------
 struct DeviceGuard {   // the worker's device: current + locked for the scope

@@ -276,19 +276,15 @@ static void depressions_host(const T *dem, int w, int h, int topology, int32_t *
                              uint32_t capacity, uint32_t *count) {
   check_depr_args(dem, w, h, topology, table, capacity, count);
   const size_t n = (size_t)w * h;
-  Workspace &ws = Workspace::get();
-  T *d = ws.buf<T>("depr.host.dem", n);
-  int32_t *dl = labels ? ws.buf<int32_t>("depr.host.labels", n) : nullptr;
+  HostStage st;
+  const T *d = st.in("depr.host.dem", dem, n);
+  uint32_t *dc = st.out("depr.host.count", count, 1);
+  int32_t *dl = st.out("depr.host.labels", labels, n);
   const uint32_t cap = (uint32_t)std::min<uint64_t>(capacity, n);   // (there are fewer depressions than cells)
-  rdgpu_depression *dt = cap ? ws.buf<rdgpu_depression>("depr.host.table", cap) : nullptr;
-  uint32_t *dc = ws.buf<uint32_t>("depr.host.count", 1);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
+  rdgpu_depression *dt = cap ? Workspace::get().buf<rdgpu_depression>("depr.host.table", cap) : nullptr;   // (fetched: cut to the count)
   depressions_device<T>(d, w, h, topology, dl, dt, cap, dc, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(count, dc, sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (labels) RD_HIP(hipMemcpy(labels, dl, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  const uint32_t wrote = std::min(*count, cap);
-  if (wrote) RD_HIP(hipMemcpy(table, dt, (size_t)wrote * sizeof(rdgpu_depression), hipMemcpyDeviceToHost));
+  st.finish();
+  st.fetch(table, dt, std::min(*count, cap));
 }
 
 }  // namespace rdgpu

@@ -623,12 +623,16 @@ static void run(T *d_z, T nodata, const T *d_W, int w, int h, hipStream_t s) {
 static int fill_plain(float *p, int w, int h, int topo, hipStream_t s) { return rdgpu_fill_dev_f32(p, w, h, topo, s); }
 static int fill_plain(double *p, int w, int h, int topo, hipStream_t s) { return rdgpu_fill_dev_f64(p, w, h, topo, s); }
 
-template <class T>
-static void fill_epsilon_device(T *d_z, T nodata, int w, int h, int topology, hipStream_t s) {
-  if (!d_z) throw Error(RDGPU_ERR_ARG, "rdgpu_fill_epsilon: null DEM pointer");
+static void check_args(const void *z, int w, int h, int topology) {
+  if (!z) throw Error(RDGPU_ERR_ARG, "rdgpu_fill_epsilon: null DEM pointer");
   if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_fill_epsilon: width and height must be positive");
   if (topology != 8 && topology != 4) throw Error(RDGPU_ERR_ARG, "rdgpu_fill_epsilon: topology must be 8 or 4");
   if ((uint64_t)w * (uint64_t)h > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, "rdgpu_fill_epsilon: raster too large");
+}
+
+template <class T>
+static void fill_epsilon_device(T *d_z, T nodata, int w, int h, int topology, hipStream_t s) {
+  check_args(d_z, w, h, topology);
   if (w <= 2 || h <= 2) return;   // every cell is a border cell
   const size_t n = (size_t)w * h;
   T *W = Workspace::get().buf<T>("eps.W", n);
@@ -640,14 +644,11 @@ static void fill_epsilon_device(T *d_z, T nodata, int w, int h, int topology, hi
 
 template <class T>
 static void fill_epsilon_host(T *dem, T nodata, int w, int h, int topology) {
-  if (!dem) throw Error(RDGPU_ERR_ARG, "rdgpu_fill_epsilon: null DEM pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_fill_epsilon: width and height must be positive");
-  const size_t bytes = (size_t)w * h * sizeof(T);
-  T *d = Workspace::get().buf<T>("host.dem", (size_t)w * h);
-  RD_HIP(hipMemcpy(d, dem, bytes, hipMemcpyHostToDevice));
+  check_args(dem, w, h, topology);
+  HostStage st;
+  T *d = st.inout("host.dem", dem, (size_t)w * h);
   fill_epsilon_device<T>(d, nodata, w, h, topology, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(dem, d, bytes, hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 }  // namespace eps
@@ -900,12 +901,16 @@ static void run(T *d_z, T nodata, const T *d_W, int w, int h, int32_t *d_labels,
   RD_LAUNCH("shed.apply", k_ws_apply, dim3(sgrid), dim3(NT), 0, s, (const uint32_t *)link, d_labels, n);
 }
 
-template <class T>
-static void watersheds_device(T *d_z, T nodata, int w, int h, int topology, int alter, int32_t *d_labels, hipStream_t s) {
-  if (!d_z || !d_labels) throw Error(RDGPU_ERR_ARG, "rdgpu_watersheds: null pointer");
+static void check_args(const void *z, const void *labels, int w, int h, int topology) {
+  if (!z || !labels) throw Error(RDGPU_ERR_ARG, "rdgpu_watersheds: null pointer");
   if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_watersheds: width and height must be positive");
   if (topology != 8 && topology != 4) throw Error(RDGPU_ERR_ARG, "rdgpu_watersheds: topology must be 8 or 4");
   if ((uint64_t)w * (uint64_t)h > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, "rdgpu_watersheds: raster too large");
+}
+
+template <class T>
+static void watersheds_device(T *d_z, T nodata, int w, int h, int topology, int alter, int32_t *d_labels, hipStream_t s) {
+  check_args(d_z, d_labels, w, h, topology);
   const size_t n = (size_t)w * h;
   T *W = Workspace::get().buf<T>("eps.W", n);
   RD_HIP(hipMemcpyAsync(W, d_z, n * sizeof(T), hipMemcpyDeviceToDevice, s));
@@ -917,16 +922,13 @@ static void watersheds_device(T *d_z, T nodata, int w, int h, int topology, int 
 
 template <class T>
 static void watersheds_host(T *dem, T nodata, int w, int h, int topology, int alter, int32_t *labels) {
-  if (!dem || !labels) throw Error(RDGPU_ERR_ARG, "rdgpu_watersheds: null pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_watersheds: width and height must be positive");
+  check_args(dem, labels, w, h, topology);
   const size_t n = (size_t)w * h;
-  T *d = Workspace::get().buf<T>("host.dem", n);
-  int32_t *dl = Workspace::get().buf<int32_t>("host.labels", n);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
+  HostStage st;
+  int32_t *dl = st.out("host.labels", labels, n);
+  T *d = alter ? st.inout("host.dem", dem, n) : const_cast<T *>(st.in("host.dem", dem, n));   // altered: the filled DEM comes back
   watersheds_device<T>(d, nodata, w, h, topology, alter, dl, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(labels, dl, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (alter) RD_HIP(hipMemcpy(dem, d, n * sizeof(T), hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 }  // namespace shed

@@ -186,17 +186,13 @@ static void extreme_host(const uint8_t *dirs, uint8_t nodata, const T *values, T
                          uint32_t *at_cell, const char *who) {
   ex_check_args(dirs, values, w, h, which, extreme, at_cell, who);
   const size_t n = (size_t)w * h;
-  Workspace &ws = Workspace::get();
-  uint8_t *dd = ws.buf<uint8_t>("host.dirs", n);
-  T *dv = ws.buf<T>("host.extreme.values", n);
-  T *de = extreme ? ws.buf<T>("host.extreme.extreme", n) : nullptr;
-  uint32_t *da = at_cell ? ws.buf<uint32_t>("host.extreme.at_cell", n) : nullptr;
-  RD_HIP(hipMemcpy(dd, dirs, n, hipMemcpyHostToDevice));
-  RD_HIP(hipMemcpy(dv, values, n * sizeof(T), hipMemcpyHostToDevice));
+  HostStage st;
+  const uint8_t *dd = st.in("host.dirs", dirs, n);
+  const T *dv = st.in("host.extreme.values", values, n);
+  T *de = st.out("host.extreme.extreme", extreme, n);
+  uint32_t *da = st.out("host.extreme.at_cell", at_cell, n);
   extreme_device<T>(dd, nodata, dv, value_nodata, w, h, which, de, da, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  if (extreme) RD_HIP(hipMemcpy(extreme, de, n * sizeof(T), hipMemcpyDeviceToHost));
-  if (at_cell) RD_HIP(hipMemcpy(at_cell, da, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 }  // namespace rdgpu

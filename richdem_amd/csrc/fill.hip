@@ -1723,10 +1723,14 @@ __global__ __launch_bounds__(NTHR) void k_pit_mask(const T *__restrict__ z, T no
   }
 }
 
+static void check_pit_mask_args(const void *z, int w, int h, int topology, const void *mask) {
+  check_fill_args(z, w, h, topology);
+  if (!mask) throw Error(RDGPU_ERR_ARG, "rdgpu_pit_mask: null mask pointer");
+}
+
 template <class T>
 static void pit_mask_device(const T *d_z, T nodata, int w, int h, int topology, uint8_t *d_mask, hipStream_t s) {
-  check_fill_args(d_z, w, h, topology);
-  if (!d_mask) throw Error(RDGPU_ERR_ARG, "rdgpu_pit_mask: null mask pointer");
+  check_pit_mask_args(d_z, w, h, topology, d_mask);
   FillBuffers fb;
   BufAlloc ws_alloc{false, nullptr};
   if (topology == 8) fill_local_phase<T, 8>(d_z, w, h, 0, 0, ws_alloc, fb, s);
@@ -1738,15 +1742,13 @@ static void pit_mask_device(const T *d_z, T nodata, int w, int h, int topology, 
 
 template <class T>
 static void pit_mask_host(const T *dem, T nodata, int w, int h, int topology, uint8_t *mask) {
-  check_fill_args(dem, w, h, topology);
-  if (!mask) throw Error(RDGPU_ERR_ARG, "rdgpu_pit_mask: null mask pointer");
+  check_pit_mask_args(dem, w, h, topology, mask);
   const size_t n = (size_t)w * h;
-  T *d = Workspace::get().buf<T>("host.dem", n);
-  uint8_t *dm = Workspace::get().buf<uint8_t>("host.dirs", n);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
+  HostStage st;
+  const T *d = st.in("host.dem", dem, n);
+  uint8_t *dm = st.out("host.dirs", mask, n);
   pit_mask_device<T>(d, nodata, w, h, topology, dm, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(mask, dm, n, hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2010,12 +2012,10 @@ static void fill_max_dep_device(T *d_z, int w, int h, int topology, uint64_t max
 template <class T>
 static void fill_max_dep_host(T *dem, int w, int h, int topology, uint64_t max_dep) {
   check_fill_args(dem, w, h, topology);
-  const size_t bytes = (size_t)w * h * sizeof(T);
-  T *d = Workspace::get().buf<T>("host.dem", (size_t)w * h);
-  RD_HIP(hipMemcpy(d, dem, bytes, hipMemcpyHostToDevice));
+  HostStage st;
+  T *d = st.inout("host.dem", dem, (size_t)w * h);
   fill_max_dep_device<T>(d, w, h, topology, max_dep, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(dem, d, bytes, hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 // ==========================================================================================================
@@ -3655,12 +3655,10 @@ static void fill_outlets_device(T *d_z, const uint8_t *d_outlet, const uint8_t *
 template <class T>
 static void fill_host(T *dem, int w, int h, int topology) {
   check_fill_args(dem, w, h, topology);
-  const size_t bytes = (size_t)w * h * sizeof(T);
-  T *d = Workspace::get().buf<T>("host.dem", (size_t)w * h);
-  RD_HIP(hipMemcpy(d, dem, bytes, hipMemcpyHostToDevice));
+  HostStage st;
+  T *d = st.inout("host.dem", dem, (size_t)w * h);
   fill_device<T>(d, w, h, topology, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(dem, d, bytes, hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 }  // namespace rdgpu

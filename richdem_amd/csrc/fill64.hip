@@ -245,26 +245,30 @@ static void wei2018_64_device(T *d_z, T nodata, int w, int h, hipStream_t s) {
             (const uint64_t *)r.uniq, n);
 }
 
-// host-pointer forms: H2D, the device form, D2H of what the call produces
+// host-pointer forms: the DEM staged (copied back where the call alters it), fn(stage, device DEM) stages the call's other
+// arrays and runs the device form
 template <class T, class F>
 static void with_device_copy(T *dem, int w, int h, bool copy_back, F &&fn) {
   if (!dem) throw Error(RDGPU_ERR_ARG, "rdgpu: null DEM pointer");
   if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu: width and height must be positive");
   const size_t n = (size_t)w * h;
-  T *d = Workspace::get().buf<T>("host.dem64", n);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
-  fn(d);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  if (copy_back) RD_HIP(hipMemcpy(dem, d, n * sizeof(T), hipMemcpyDeviceToHost));
+  HostStage st;
+  T *d = copy_back ? st.inout("host.dem64", dem, n) : const_cast<T *>(st.in("host.dem64", dem, n));
+  fn(st, d);
+  st.finish();
+}
+
+static void check_fill64_args(const void *z, int w, int h, int topology) {
+  if (!z) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: null DEM pointer");
+  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: width and height must be positive");
+  if (topology != 8 && topology != 4) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: topology must be 8 or 4");
+  if ((uint64_t)w * h > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: raster has more than 2^31-65536 cells");
 }
 
 template <class T>
 static void fill64_device(T *d_z, int w, int h, int topology, hipStream_t s) {
-  if (!d_z) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: null DEM pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: width and height must be positive");
-  if (topology != 8 && topology != 4) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: topology must be 8 or 4");
+  check_fill64_args(d_z, w, h, topology);
   const uint64_t n = (uint64_t)w * h;
-  if (n > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: raster has more than 2^31-65536 cells");
   Workspace &ws = Workspace::get();
   uint32_t *hw = ws.host_words();
   uint32_t *flag = ws.buf<uint32_t>("fill64.flag", 4);
@@ -295,14 +299,11 @@ static void fill64_device(T *d_z, int w, int h, int topology, hipStream_t s) {
 
 template <class T>
 static void fill64_host(T *dem, int w, int h, int topology) {
-  if (!dem) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: null DEM pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_fill: width and height must be positive");
-  const size_t n = (size_t)w * h;
-  T *d = Workspace::get().buf<T>("host.dem64", n);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
+  check_fill64_args(dem, w, h, topology);
+  HostStage st;
+  T *d = st.inout("host.dem64", dem, (size_t)w * h);
   fill64_device<T>(d, w, h, topology, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(dem, d, n * sizeof(T), hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 }  // namespace rdgpu
@@ -326,7 +327,8 @@ RD_FILL64_API(u64, uint64_t)
   }                                                                                                                    \
   extern "C" int rdgpu_fill_max_dep_##SUF(T *dem, int w, int h, int topology, uint64_t max_dep_size) {                 \
     return guarded([&] {                                                                                               \
-      with_device_copy<T>(dem, w, h, true, [&](T *d) { fill_max_dep64_device<T>(d, w, h, topology, max_dep_size, nullptr); }); \
+      with_device_copy<T>(dem, w, h, true,                                                                             \
+                          [&](HostStage &, T *d) { fill_max_dep64_device<T>(d, w, h, topology, max_dep_size, nullptr); }); \
     });                                                                                                                \
   }                                                                                                                    \
   extern "C" int rdgpu_pit_mask_dev_##SUF(const T *d_dem, T nodata, int w, int h, int topology, uint8_t *d_mask, void *stream) { \
@@ -335,11 +337,8 @@ RD_FILL64_API(u64, uint64_t)
   extern "C" int rdgpu_pit_mask_##SUF(const T *dem, T nodata, int w, int h, int topology, uint8_t *mask) {             \
     return guarded([&] {                                                                                               \
       if (!mask) throw Error(RDGPU_ERR_ARG, "rdgpu_pit_mask: null pointer");                                           \
-      with_device_copy<T>(const_cast<T *>(dem), w, h, false, [&](T *d) {                                               \
-        uint8_t *dm = Workspace::get().buf<uint8_t>("host.mask64", (size_t)w * h);                                     \
-        pit_mask64_device<T>(d, nodata, w, h, topology, dm, nullptr);                                                  \
-        RD_HIP(hipStreamSynchronize(nullptr));                                                                         \
-        RD_HIP(hipMemcpy(mask, dm, (size_t)w * h, hipMemcpyDeviceToHost));                                             \
+      with_device_copy<T>(const_cast<T *>(dem), w, h, false, [&](HostStage &st, T *d) {                                \
+        pit_mask64_device<T>(d, nodata, w, h, topology, st.out("host.mask64", mask, (size_t)w * h), nullptr);          \
       });                                                                                                              \
     });                                                                                                                \
   }                                                                                                                    \
@@ -350,11 +349,8 @@ RD_FILL64_API(u64, uint64_t)
   extern "C" int rdgpu_watersheds_##SUF(T *dem, T nodata, int w, int h, int topology, int alter, int32_t *labels) {    \
     return guarded([&] {                                                                                               \
       if (!labels) throw Error(RDGPU_ERR_ARG, "rdgpu_watersheds: null pointer");                                       \
-      with_device_copy<T>(dem, w, h, alter != 0, [&](T *d) {                                                           \
-        int32_t *dl = Workspace::get().buf<int32_t>("host.labels64", (size_t)w * h);                                   \
-        watersheds64_device<T>(d, nodata, w, h, topology, alter, dl, nullptr);                                         \
-        RD_HIP(hipStreamSynchronize(nullptr));                                                                         \
-        RD_HIP(hipMemcpy(labels, dl, (size_t)w * h * sizeof(int32_t), hipMemcpyDeviceToHost));                         \
+      with_device_copy<T>(dem, w, h, alter != 0, [&](HostStage &st, T *d) {                                            \
+        watersheds64_device<T>(d, nodata, w, h, topology, alter, st.out("host.labels64", labels, (size_t)w * h), nullptr); \
       });                                                                                                              \
     });                                                                                                                \
   }
@@ -369,11 +365,8 @@ RD_F2_64_API(u64, uint64_t)
   extern "C" int rdgpu_pf_flowdirs_##SUF(const T *dem, T nodata, int w, int h, uint8_t *dirs) {                        \
     return guarded([&] {                                                                                               \
       if (!dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_pf_flowdirs: null pointer");                                        \
-      with_device_copy<T>(const_cast<T *>(dem), w, h, false, [&](T *d) {                                               \
-        uint8_t *dd = Workspace::get().buf<uint8_t>("host.mask64", (size_t)w * h);                                     \
-        pf_flowdirs64_device<T>(d, nodata, w, h, dd, nullptr);                                                         \
-        RD_HIP(hipStreamSynchronize(nullptr));                                                                         \
-        RD_HIP(hipMemcpy(dirs, dd, (size_t)w * h, hipMemcpyDeviceToHost));                                             \
+      with_device_copy<T>(const_cast<T *>(dem), w, h, false, [&](HostStage &st, T *d) {                                \
+        pf_flowdirs64_device<T>(d, nodata, w, h, st.out("host.mask64", dirs, (size_t)w * h), nullptr);                 \
       });                                                                                                              \
     });                                                                                                                \
   }
@@ -386,7 +379,7 @@ RD_PFD64_API(u64, uint64_t)
     return guarded([&] { wei2018_64_device<T>(d_dem, nodata, w, h, (hipStream_t)stream); });                           \
   }                                                                                                                    \
   extern "C" int rdgpu_fill_wei2018_##SUF(T *dem, T nodata, int w, int h) {                                            \
-    return guarded([&] { with_device_copy<T>(dem, w, h, true, [&](T *d) { wei2018_64_device<T>(d, nodata, w, h, nullptr); }); }); \
+    return guarded([&] { with_device_copy<T>(dem, w, h, true, [&](HostStage &, T *d) { wei2018_64_device<T>(d, nodata, w, h, nullptr); }); }); \
   }
 RD_WEI64_API(f64, double)
 RD_WEI64_API(i64, int64_t)

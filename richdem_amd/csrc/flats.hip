@@ -2286,6 +2286,13 @@ static void epsilon_levels_device(const T *d_z, T nodata, int w, int h, int32_t 
   *outA = A;
 }
 
+// the argument checks of an entry's two doors (host pointers, device pointers): thrown before anything is staged
+static void flats_check_args(bool pointers, int w, int h, const char *who) {
+  if (!pointers) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
+  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, std::string(who) + ": width and height must be positive");
+  if ((uint64_t)w * (uint64_t)h > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, std::string(who) + ": raster too large");
+}
+
 static thread_local bool g_planes_overflowed = false;   // (flat_resolution_device: this call repeats a plane search that overflowed)
 static thread_local uint32_t g_plane_repeats = 0;       // (rdgpu_flat_get_async_stats: the last directions-only call did)
 // A level beyond 16 bits: once more, on ints (the last pass has not run, or left dirs alone: it holds what the classification
@@ -2308,9 +2315,7 @@ static void launch_dirs_qp(const BitsScratch &bt, const BitsScratch &ba, int hav
 }
 template <class T>
 void flat_resolution_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, hipStream_t s) {
-  if (!d_z || !d_dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8: null pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8: width and height must be positive");
-  if ((uint64_t)w * (uint64_t)h > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8: raster too large");
+  flats_check_args(d_z && d_dirs, w, h, "rdgpu_flat_resolution_d8");
   // directions only: the two level fields suffice, no labels and no flat heights; d8_flow_directions is part of the
   // classification pass (k_dirs_classify)
   const uint64_t n = (uint64_t)w * h;
@@ -2412,18 +2417,15 @@ void flat_resolution_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dir
 
 template <class T>
 static void flat_resolution_host(const T *dem, T nodata, int w, int h, uint8_t *dirs, int32_t *mask, int32_t *labels) {
-  if (!dem || !dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8: null pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8: width and height must be positive");
-  if ((uint64_t)w * (uint64_t)h > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8: raster too large");
+  flats_check_args(dem && dirs, w, h, "rdgpu_flat_resolution_d8");
   const size_t n = (size_t)w * h;
-  T *d = Workspace::get().buf<T>("host.dem", n);
-  uint8_t *dd = Workspace::get().buf<uint8_t>("host.dirs", n);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
+  HostStage st;
+  const T *d = st.in("host.dem", dem, n);
+  uint8_t *dd = st.out("host.dirs", dirs, n);
   hipStream_t s = nullptr;
   if (!mask && !labels) {   // directions only: the path without labels and flat heights
     flat_resolution_device<T>(d, nodata, w, h, dd, s);
-    RD_HIP(hipStreamSynchronize(s));
-    RD_HIP(hipMemcpy(dirs, dd, n, hipMemcpyDeviceToHost));
+    st.finish();
     return;
   }
   flowdirs_device<T>(d, nodata, w, h, dd, MODE_D8, s);
@@ -2431,19 +2433,17 @@ static void flat_resolution_host(const T *dem, T nodata, int w, int h, uint8_t *
   uint32_t *L;
   resolve_flats_device<T>(d, dd, w, h, &M, &L, &fh, s);
   if (L) launch_masked_dirs<T>(d, M, dd, w, h, s);
-  RD_HIP(hipStreamSynchronize(s));
-  RD_HIP(hipMemcpy(dirs, dd, n, hipMemcpyDeviceToHost));
-  if (mask) RD_HIP(hipMemcpy(mask, M, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (labels) {
-    if (L) {
-      int32_t *lo = Workspace::get().buf<int32_t>("host.labels", n);
-      RD_LAUNCH("flats.labels_out", k_flat_labels_out, dim3(sgrid(n)), dim3(NTHR), 0, s, L, fh, lo, (uint64_t)n);
-      RD_HIP(hipStreamSynchronize(s));
-      RD_HIP(hipMemcpy(labels, lo, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    } else {
-      memset(labels, 0, n * sizeof(int32_t));
-    }
+  st.finish();
+  if (mask) st.fetch(mask, (const int32_t *)M, n);   // (the mask lives in the driver's own buffer)
+  if (!labels) return;
+  if (!L) {   // no flats
+    memset(labels, 0, n * sizeof(int32_t));
+    return;
   }
+  // second phase: the labels in the numbering the entry returns, made after the first downloads
+  int32_t *lo = st.out("host.labels", labels, n);
+  RD_LAUNCH("flats.labels_out", k_flat_labels_out, dim3(sgrid(n)), dim3(NTHR), 0, s, L, fh, lo, (uint64_t)n);
+  st.finish();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2507,9 +2507,7 @@ __global__ __launch_bounds__(NTHR) void k_flat_alter(T *z, const int32_t *__rest
 
 template <class T>
 void flat_resolution_alter_device(T *d_z, T nodata, int w, int h, uint8_t *d_dirs, hipStream_t s) {
-  if (!d_z || !d_dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8_alter: null pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8_alter: width and height must be positive");
-  if ((uint64_t)w * (uint64_t)h > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8_alter: raster too large");
+  flats_check_args(d_z && d_dirs, w, h, "rdgpu_flat_resolution_d8_alter");
   flowdirs_device<T>(d_z, nodata, w, h, d_dirs, MODE_D8, s);
   int32_t *M, *fh;
   uint32_t *L;
@@ -2522,16 +2520,13 @@ void flat_resolution_alter_device(T *d_z, T nodata, int w, int h, uint8_t *d_dir
 
 template <class T>
 static void flat_resolution_alter_host(T *dem, T nodata, int w, int h, uint8_t *dirs) {
-  if (!dem || !dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8_alter: null pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_flat_resolution_d8_alter: width and height must be positive");
+  flats_check_args(dem && dirs, w, h, "rdgpu_flat_resolution_d8_alter");
   const size_t n = (size_t)w * h;
-  T *d = Workspace::get().buf<T>("host.dem", n);
-  uint8_t *dd = Workspace::get().buf<uint8_t>("host.dirs", n);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
+  HostStage st;
+  uint8_t *dd = st.out("host.dirs", dirs, n);
+  T *d = st.inout("host.dem", dem, n);   // the DEM is altered in place
   flat_resolution_alter_device<T>(d, nodata, w, h, dd, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(dirs, dd, n, hipMemcpyDeviceToHost));
-  RD_HIP(hipMemcpy(dem, d, n * sizeof(T), hipMemcpyDeviceToHost));   // the DEM is altered in place
+  st.finish();
 }
 
 
@@ -2966,9 +2961,7 @@ __global__ __launch_bounds__(NTHR) void k_flat_epsilon4(T *z, const int32_t *__r
 
 template <class T>
 void resolve_flats_epsilon_device(T *d_z, T nodata, int w, int h, hipStream_t s) {
-  if (!d_z) throw Error(RDGPU_ERR_ARG, "rdgpu_resolve_flats_epsilon: null pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_resolve_flats_epsilon: width and height must be positive");
-  if ((uint64_t)w * (uint64_t)h > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, "rdgpu_resolve_flats_epsilon: raster too large");
+  flats_check_args(d_z, w, h, "rdgpu_resolve_flats_epsilon");
   int32_t *M, *fh;
   uint32_t *L;
   const int32_t *A;
@@ -2985,14 +2978,12 @@ void resolve_flats_epsilon_device(T *d_z, T nodata, int w, int h, hipStream_t s)
 
 template <class T>
 static void resolve_flats_epsilon_host(T *dem, T nodata, int w, int h) {
-  if (!dem) throw Error(RDGPU_ERR_ARG, "rdgpu_resolve_flats_epsilon: null pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_resolve_flats_epsilon: width and height must be positive");
+  flats_check_args(dem, w, h, "rdgpu_resolve_flats_epsilon");
   const size_t n = (size_t)w * h;
-  T *d = Workspace::get().buf<T>("host.dem", n);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
+  HostStage st;
+  T *d = st.inout("host.dem", dem, n);
   resolve_flats_epsilon_device<T>(d, nodata, w, h, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(dem, d, n * sizeof(T), hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 #define RD_INST(T) template void flat_resolution_device<T>(const T *, T, int, int, uint8_t *, hipStream_t);

@@ -101,10 +101,14 @@ __global__ __launch_bounds__(NTHR) void k_flowdirs(const T *__restrict__ z, T no
   }
 }
 
+static void flowdirs_check_args(const void *z, const void *dirs, int w, int h) {
+  if (!z || !dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_d8_flowdirs: null pointer");
+  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_d8_flowdirs: width and height must be positive");
+}
+
 template <class T>
 void flowdirs_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, int mode, hipStream_t s) {
-  if (!d_z || !d_dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_d8_flowdirs: null pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_d8_flowdirs: width and height must be positive");
+  flowdirs_check_args(d_z, d_dirs, w, h);
   const uint32_t tilesX = (w + TW - 1) / TW, tilesY = (h + TH - 1) / TH, ntiles = tilesX * tilesY;
   if (mode == MODE_D8)
     RD_LAUNCH("flowdirs.d8", (k_flowdirs<T, MODE_D8>), dim3(xcd_grid(ntiles)), dim3(NTHR), 0, s, d_z, nodata, d_dirs,
@@ -121,15 +125,13 @@ RD_INST(int8_t) RD_INST(int64_t) RD_INST(uint64_t)
 
 template <class T>
 static void flowdirs_host(const T *dem, T nodata, int w, int h, uint8_t *dirs) {
-  if (!dem || !dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_d8_flowdirs: null pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_d8_flowdirs: width and height must be positive");
+  flowdirs_check_args(dem, dirs, w, h);
   const size_t n = (size_t)w * h;
-  T *d = Workspace::get().buf<T>("host.dem", n);
-  uint8_t *dd = Workspace::get().buf<uint8_t>("host.dirs", n);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
+  HostStage st;
+  const T *d = st.in("host.dem", dem, n);
+  uint8_t *dd = st.out("host.dirs", dirs, n);
   flowdirs_device<T>(d, nodata, w, h, dd, MODE_D8, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(dirs, dd, n, hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 }  // namespace rdgpu

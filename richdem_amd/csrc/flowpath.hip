@@ -306,11 +306,15 @@ void flow_path_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, const
             d_dist, cx, cy, diag, dist_nodata);
 }
 
+static void hand_check(const void *dirs, const void *dem, const void *hand, int w, int h, const char *who) {
+  fp_check_dims(dirs, w, h, who);
+  if (!dem || !hand) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
+}
+
+// arguments checked by the caller (hand_check)
 template <class T>
 static void hand_device(const uint8_t *d_dirs, uint8_t nodata, const T *d_dem, T dem_nodata, int w, int h, const uint8_t *d_chan,
-                        double *d_hand, double out_nodata, hipStream_t s, const char *who) {
-  fp_check_dims(d_dirs, w, h, who);
-  if (!d_dem || !d_hand) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
+                        double *d_hand, double out_nodata, hipStream_t s) {
   const uint64_t n = (uint64_t)w * h;
   uint32_t *tc = Workspace::get().buf<uint32_t>("flowpath.to_cell", n);
   flow_path_device(d_dirs, nodata, w, h, d_chan, 1.0, 1.0, tc, nullptr, nullptr, 0.0, s);
@@ -323,38 +327,28 @@ static void flow_path_host(const uint8_t *dirs, uint8_t nodata, int w, int h, co
                            uint32_t *to_cell, uint32_t *steps, double *dist, double dist_nodata, const char *who) {
   fp_check_path_args(dirs, w, h, cx, cy, to_cell, steps, dist, who);
   const size_t n = (size_t)w * h;
-  Workspace &ws = Workspace::get();
-  uint8_t *dd = ws.buf<uint8_t>("host.dirs", n);
-  uint8_t *dc = chan ? ws.buf<uint8_t>("host.flowpath.chan", n) : nullptr;
-  uint32_t *dt = to_cell ? ws.buf<uint32_t>("host.flowpath.to_cell", n) : nullptr;
-  uint32_t *dst = steps ? ws.buf<uint32_t>("host.flowpath.steps", 3 * n) : nullptr;
-  double *ddi = dist ? ws.buf<double>("host.flowpath.dist", n) : nullptr;
-  RD_HIP(hipMemcpy(dd, dirs, n, hipMemcpyHostToDevice));
-  if (chan) RD_HIP(hipMemcpy(dc, chan, n, hipMemcpyHostToDevice));
+  HostStage st;
+  const uint8_t *dd = st.in("host.dirs", dirs, n);
+  const uint8_t *dc = st.in("host.flowpath.chan", chan, n);
+  uint32_t *dt = st.out("host.flowpath.to_cell", to_cell, n);
+  uint32_t *dst = st.out("host.flowpath.steps", steps, 3 * n);
+  double *ddi = st.out("host.flowpath.dist", dist, n);
   flow_path_device(dd, nodata, w, h, dc, cx, cy, dt, dst, ddi, dist_nodata, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  if (to_cell) RD_HIP(hipMemcpy(to_cell, dt, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (steps) RD_HIP(hipMemcpy(steps, dst, 3 * n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (dist) RD_HIP(hipMemcpy(dist, ddi, n * sizeof(double), hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 template <class T>
 static void hand_host(const uint8_t *dirs, uint8_t nodata, const T *dem, T dem_nodata, int w, int h, const uint8_t *chan, double *hand,
                       double out_nodata, const char *who) {
-  fp_check_dims(dirs, w, h, who);
-  if (!dem || !hand) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
+  hand_check(dirs, dem, hand, w, h, who);
   const size_t n = (size_t)w * h;
-  Workspace &ws = Workspace::get();
-  uint8_t *dd = ws.buf<uint8_t>("host.dirs", n);
-  uint8_t *dc = chan ? ws.buf<uint8_t>("host.flowpath.chan", n) : nullptr;
-  T *dz = ws.buf<T>("host.flowpath.dem", n);
-  double *dh = ws.buf<double>("host.flowpath.dist", n);
-  RD_HIP(hipMemcpy(dd, dirs, n, hipMemcpyHostToDevice));
-  if (chan) RD_HIP(hipMemcpy(dc, chan, n, hipMemcpyHostToDevice));
-  RD_HIP(hipMemcpy(dz, dem, n * sizeof(T), hipMemcpyHostToDevice));
-  hand_device<T>(dd, nodata, dz, dem_nodata, w, h, dc, dh, out_nodata, nullptr, who);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(hand, dh, n * sizeof(double), hipMemcpyDeviceToHost));
+  HostStage st;
+  const uint8_t *dd = st.in("host.dirs", dirs, n);
+  const uint8_t *dc = st.in("host.flowpath.chan", chan, n);
+  const T *dz = st.in("host.flowpath.dem", dem, n);
+  double *dh = st.out("host.flowpath.dist", hand, n);
+  hand_device<T>(dd, nodata, dz, dem_nodata, w, h, dc, dh, out_nodata, nullptr);
+  st.finish();
 }
 
 }  // namespace rdgpu
@@ -387,8 +381,8 @@ extern "C" int rdgpu_d8_flow_path_dev(const uint8_t *d_dirs, uint8_t dir_nodata,
   extern "C" int rdgpu_d8_hand_dev_##SUF(const uint8_t *d_dirs, uint8_t dir_nodata, const T *d_dem, T dem_nodata, int width,         \
                                          int height, const uint8_t *d_chan, double *d_hand, double out_nodata, void *hip_stream) {   \
     return guarded([&] {                                                                                                             \
-      hand_device<T>(d_dirs, dir_nodata, d_dem, dem_nodata, width, height, d_chan, d_hand, out_nodata, (hipStream_t)hip_stream,      \
-                     "rdgpu_d8_hand_dev_" #SUF);                                                                                     \
+      hand_check(d_dirs, d_dem, d_hand, width, height, "rdgpu_d8_hand_dev_" #SUF);                                                   \
+      hand_device<T>(d_dirs, dir_nodata, d_dem, dem_nodata, width, height, d_chan, d_hand, out_nodata, (hipStream_t)hip_stream);     \
     });                                                                                                                              \
   }
 RD_DEFINE_HAND(i8, int8_t)

@@ -283,19 +283,14 @@ static void longest_host(const uint8_t *dirs, uint8_t nodata, int w, int h, doub
                          double *length, double length_nodata, uint8_t *on_basin_path, const char *who) {
   lp_check_args(dirs, w, h, cx, cy, from_cell, steps, length, on_basin_path, who);
   const size_t n = (size_t)w * h;
-  Workspace &ws = Workspace::get();
-  uint8_t *dd = ws.buf<uint8_t>("host.dirs", n);
-  uint32_t *df = from_cell ? ws.buf<uint32_t>("host.longest.from_cell", n) : nullptr;
-  uint32_t *dst = steps ? ws.buf<uint32_t>("host.longest.steps", 3 * n) : nullptr;
-  double *dl = length ? ws.buf<double>("host.longest.length", n) : nullptr;
-  uint8_t *db = on_basin_path ? ws.buf<uint8_t>("host.longest.on_basin_path", n) : nullptr;
-  RD_HIP(hipMemcpy(dd, dirs, n, hipMemcpyHostToDevice));
+  HostStage st;
+  const uint8_t *dd = st.in("host.dirs", dirs, n);
+  uint32_t *df = st.out("host.longest.from_cell", from_cell, n);
+  uint32_t *dst = st.out("host.longest.steps", steps, 3 * n);
+  double *dl = st.out("host.longest.length", length, n);
+  uint8_t *db = st.out("host.longest.on_basin_path", on_basin_path, n);
   longest_device(dd, nodata, w, h, cx, cy, df, dst, dl, length_nodata, db, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  if (from_cell) RD_HIP(hipMemcpy(from_cell, df, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (steps) RD_HIP(hipMemcpy(steps, dst, 3 * n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (length) RD_HIP(hipMemcpy(length, dl, n * sizeof(double), hipMemcpyDeviceToHost));
-  if (on_basin_path) RD_HIP(hipMemcpy(on_basin_path, db, n, hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 }  // namespace rdgpu

@@ -555,9 +555,13 @@ __global__ __launch_bounds__(NTHR) void k_fm_mfd(const T *__restrict__ z, T noda
   }
 }
 
+static void check_mfd_method(int method) {
+  if (method < 0 || method > 3) throw Error(RDGPU_ERR_ARG, "rdgpu_fm_mfd: method must be 0 (Holmgren), 1 (Freeman), 2 (Quinn) or 3 (D4)");
+}
+
+// arguments checked by the caller (mfd_check_args, check_mfd_method)
 template <class T>
 static void fm_mfd_device(const T *d_z, T nodata, int w, int h, int method, double xparam, float *d_props, hipStream_t s) {
-  if (method < 0 || method > 3) throw Error(RDGPU_ERR_ARG, "rdgpu_fm_mfd: method must be 0 (Holmgren), 1 (Freeman), 2 (Quinn) or 3 (D4)");
   if (method == MFD_QUINN) { method = MFD_HOLMGREN; xparam = 1.0; }
   RD_LAUNCH("mfd.fm_mfd", (k_fm_mfd<T>), dim3(sgrid((uint64_t)w * h)), dim3(NTHR), 0, s, d_z, nodata, d_props, w, h, method, xparam);
 }
@@ -625,6 +629,60 @@ template DinfAcc tarboton_flats_device<int32_t>(const int32_t *, int32_t, int, i
 template DinfAcc tarboton_flats_device<float>(const float *, float, int, int, hipStream_t);
 template DinfAcc tarboton_flats_device<double>(const double *, double, int, int, hipStream_t);
 
+// ------------------------------------------------------------------------------------------
+// The entry points.  Each product has a typed driver on device pointers and a stream; its `_dev` entry runs the driver on the
+// caller's stream, its host entry stages the caller's arrays (HostStage) and runs the same driver on the null stream.
+// ------------------------------------------------------------------------------------------
+static void mfd_check_args(const void *in, const void *out, int w, int h, const char *who, uint64_t max_cells = 0xFFFF0000ull) {
+  if (!in || !out) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
+  check_dims(w, h, who, max_cells);
+}
+
+template <class T>
+static void dinf_flowdirs_device(const T *d_z, T nodata, int w, int h, float *d_out, hipStream_t s) {
+  const uint32_t dtilesX = (w + DTW - 1) / DTW, dntiles = dtilesX * ((h + DTH - 1) / DTH);
+  RD_LAUNCH("mfd.dinf_dirs", (k_dinf_dirs<T>), dim3(xcd_grid(dntiles)), dim3(NTHR), 0, s, d_z, nodata, d_out, w, h, dtilesX, dntiles);
+}
+// tarboton: tarboton_device, or tarboton_flats_device for the `_flats` entries
+template <class T>
+static void fm_tarboton_device(TarbotonFn<T> tarboton, const T *d_z, T nodata, int w, int h, float *d_props9, hipStream_t s) {
+  const DinfAcc a = tarboton(d_z, nodata, w, h, s);
+  const uint64_t n = (uint64_t)w * h;
+  RD_LAUNCH("mfd.tarboton_props", k_tarboton_props, dim3(sgrid(n)), dim3(NTHR), 0, s, a.rcv, a.sh1, a.sh2, d_props9, n);
+}
+template <class T>
+static void fa_tarboton_device(TarbotonFn<T> tarboton, const T *d_z, T nodata, int w, int h, double *d_accum, hipStream_t s) {
+  const DinfAcc a = tarboton(d_z, nodata, w, h, s);
+  mfd_accumulate<DinfAcc>(a, w, h, d_accum, s);
+}
+template <class T>
+static void fa_mfd_device(const T *d_z, T nodata, int w, int h, int method, double xparam, double *d_accum, hipStream_t s) {
+  float *p = Workspace::get().buf<float>("mfd.props", (uint64_t)w * h * 9);
+  fm_mfd_device<T>(d_z, nodata, w, h, method, xparam, p, s);
+  mfd_accumulate<PropsAcc>(PropsAcc{p}, w, h, d_accum, s);
+}
+
+// The host doors.  A DEM up, `per_cell` floats a cell down: run(device DEM, device planes) on the null stream.
+template <class T, class Run>
+static void host_dem_to_f32(const T *dem, int w, int h, const char *out_name, float *out, size_t per_cell, Run &&run) {
+  const size_t n = (size_t)w * h;
+  HostStage st;
+  const T *d = st.in("host.dem", dem, n);
+  float *o = st.out(out_name, out, n * per_cell);
+  run(d, o);
+  st.finish();
+}
+// A DEM up, the accumulation array both ways (the caller's flow generated per cell in, the accumulation out).
+template <class T, class Run>
+static void host_dem_accum(const T *dem, int w, int h, double *accum, Run &&run) {
+  const size_t n = (size_t)w * h;
+  HostStage st;
+  const T *d = st.in("host.dem", dem, n);
+  double *da = st.inout("host.area", accum, n);
+  run(d, da);
+  st.finish();
+}
+
 }  // namespace rdgpu
 
 using namespace rdgpu;
@@ -632,61 +690,37 @@ using namespace rdgpu;
 #define RD_MFD_API(SUF, T)                                                                                      \
   extern "C" int rdgpu_dinf_flowdirs_dev_##SUF(const T *d_dem, T nodata, int w, int h, float *d_out, void *st) { \
     return guarded([&] {                                                                                        \
-      if (!d_dem || !d_out) throw Error(RDGPU_ERR_ARG, "rdgpu_dinf_flowdirs: null pointer");                    \
-      check_dims(w, h, "rdgpu_dinf_flowdirs");                                                                  \
-      const uint32_t dtx_ = (w + DTW - 1) / DTW, dnt_ = dtx_ * ((h + DTH - 1) / DTH);                               \
-      RD_LAUNCH("mfd.dinf_dirs", (k_dinf_dirs<T>), dim3(xcd_grid(dnt_)), dim3(NTHR), 0, (hipStream_t)st,            \
-                d_dem, nodata, d_out, w, h, dtx_, dnt_);                                                        \
+      mfd_check_args(d_dem, d_out, w, h, "rdgpu_dinf_flowdirs");                                                \
+      dinf_flowdirs_device<T>(d_dem, nodata, w, h, d_out, (hipStream_t)st);                                     \
     });                                                                                                         \
   }                                                                                                             \
   extern "C" int rdgpu_dinf_flowdirs_##SUF(const T *dem, T nodata, int w, int h, float *out) {                  \
     return guarded([&] {                                                                                        \
-      if (!dem || !out) throw Error(RDGPU_ERR_ARG, "rdgpu_dinf_flowdirs: null pointer");                        \
-      check_dims(w, h, "rdgpu_dinf_flowdirs");                                                                  \
-      T *d;                                                                                                     \
-      host_dem<T>(dem, w, h, &d);                                                                               \
-      float *o = Workspace::get().buf<float>("host.f32out", (size_t)w * h);                                     \
-      const uint32_t dtx_ = (w + DTW - 1) / DTW, dnt_ = dtx_ * ((h + DTH - 1) / DTH);                               \
-      RD_LAUNCH("mfd.dinf_dirs", (k_dinf_dirs<T>), dim3(xcd_grid(dnt_)), dim3(NTHR), 0, (hipStream_t) nullptr,      \
-                (const T *)d, nodata, o, w, h, dtx_, dnt_);                                                     \
-      RD_HIP(hipMemcpy(out, o, (size_t)w * h * 4, hipMemcpyDeviceToHost));                                      \
+      mfd_check_args(dem, out, w, h, "rdgpu_dinf_flowdirs");                                                    \
+      host_dem_to_f32<T>(dem, w, h, "host.f32out", out, 1,                                                      \
+                         [&](const T *d, float *o) { dinf_flowdirs_device<T>(d, nodata, w, h, o, nullptr); });  \
     });                                                                                                         \
   }                                                                                                             \
   extern "C" int rdgpu_fm_tarboton_##SUF(const T *dem, T nodata, int w, int h, float *props9) {                 \
     return guarded([&] {                                                                                        \
-      if (!dem || !props9) throw Error(RDGPU_ERR_ARG, "rdgpu_fm_tarboton: null pointer");                       \
-      check_dims(w, h, "rdgpu_fm_tarboton");                                                                    \
-      T *d;                                                                                                     \
-      host_dem<T>(dem, w, h, &d);                                                                               \
-      const DinfAcc a = tarboton_device<T>(d, nodata, w, h, nullptr);                                           \
-      const uint64_t n = (uint64_t)w * h;                                                                       \
-      float *p = Workspace::get().buf<float>("host.props", n * 9);                                              \
-      RD_LAUNCH("mfd.tarboton_props", k_tarboton_props, dim3(sgrid(n)), dim3(NTHR), 0, (hipStream_t) nullptr, a.rcv, a.sh1, \
-                a.sh2, p, n);                                                                                   \
-      RD_HIP(hipMemcpy(props9, p, n * 36, hipMemcpyDeviceToHost));                                              \
+      mfd_check_args(dem, props9, w, h, "rdgpu_fm_tarboton");                                                   \
+      host_dem_to_f32<T>(dem, w, h, "host.props", props9, 9, [&](const T *d, float *p) {                        \
+        fm_tarboton_device<T>(tarboton_device<T>, d, nodata, w, h, p, nullptr);                                 \
+      });                                                                                                       \
     });                                                                                                         \
   }                                                                                                             \
   extern "C" int rdgpu_fa_tarboton_dev_##SUF(const T *d_dem, T nodata, int w, int h, double *d_accum, void *st) { \
     return guarded([&] {                                                                                        \
-      if (!d_dem || !d_accum) throw Error(RDGPU_ERR_ARG, "rdgpu_fa_tarboton: null pointer");                    \
-      check_dims(w, h, "rdgpu_fa_tarboton");                                                                    \
-      const DinfAcc a = tarboton_device<T>(d_dem, nodata, w, h, (hipStream_t)st);                               \
-      mfd_accumulate<DinfAcc>(a, w, h, d_accum, (hipStream_t)st);                                               \
+      mfd_check_args(d_dem, d_accum, w, h, "rdgpu_fa_tarboton");                                                \
+      fa_tarboton_device<T>(tarboton_device<T>, d_dem, nodata, w, h, d_accum, (hipStream_t)st);                 \
     });                                                                                                         \
   }                                                                                                             \
   extern "C" int rdgpu_fa_tarboton_##SUF(const T *dem, T nodata, int w, int h, double *accum) {                 \
     return guarded([&] {                                                                                        \
-      if (!dem || !accum) throw Error(RDGPU_ERR_ARG, "rdgpu_fa_tarboton: null pointer");                        \
-      check_dims(w, h, "rdgpu_fa_tarboton");                                                                    \
-      T *d;                                                                                                     \
-      host_dem<T>(dem, w, h, &d);                                                                               \
-      const size_t n = (size_t)w * h;                                                                           \
-      double *da = Workspace::get().buf<double>("host.area", n);                                                \
-      RD_HIP(hipMemcpy(da, accum, n * 8, hipMemcpyHostToDevice));                                               \
-      const DinfAcc a = tarboton_device<T>(d, nodata, w, h, nullptr);                                           \
-      mfd_accumulate<DinfAcc>(a, w, h, da, nullptr);                                                            \
-      RD_HIP(hipStreamSynchronize(nullptr));                                                                    \
-      RD_HIP(hipMemcpy(accum, da, n * 8, hipMemcpyDeviceToHost));                                               \
+      mfd_check_args(dem, accum, w, h, "rdgpu_fa_tarboton");                                                    \
+      host_dem_accum<T>(dem, w, h, accum, [&](const T *d, double *da) {                                         \
+        fa_tarboton_device<T>(tarboton_device<T>, d, nodata, w, h, da, nullptr);                                \
+      });                                                                                                       \
     });                                                                                                         \
   }
 RD_MFD_API(u8, uint8_t)
@@ -702,49 +736,30 @@ RD_MFD_API(i8, int8_t)
 #define RD_MFD_FLATS_API(SUF, T)                                                                                \
   extern "C" int rdgpu_fm_tarboton_flats_dev_##SUF(const T *d_dem, T nodata, int w, int h, float *d_props9, void *st) { \
     return guarded([&] {                                                                                        \
-      if (!d_dem || !d_props9) throw Error(RDGPU_ERR_ARG, "rdgpu_fm_tarboton_flats: null pointer");             \
-      check_dims(w, h, "rdgpu_fm_tarboton_flats", FLATS_MAX_CELLS);                                             \
-      const DinfAcc a = tarboton_flats_device<T>(d_dem, nodata, w, h, (hipStream_t)st);                         \
-      const uint64_t n = (uint64_t)w * h;                                                                       \
-      RD_LAUNCH("mfd.tarboton_props", k_tarboton_props, dim3(sgrid(n)), dim3(NTHR), 0, (hipStream_t)st, a.rcv, a.sh1, \
-                a.sh2, d_props9, n);                                                                            \
+      mfd_check_args(d_dem, d_props9, w, h, "rdgpu_fm_tarboton_flats", FLATS_MAX_CELLS);                        \
+      fm_tarboton_device<T>(tarboton_flats_device<T>, d_dem, nodata, w, h, d_props9, (hipStream_t)st);          \
     });                                                                                                         \
   }                                                                                                             \
   extern "C" int rdgpu_fm_tarboton_flats_##SUF(const T *dem, T nodata, int w, int h, float *props9) {           \
     return guarded([&] {                                                                                        \
-      if (!dem || !props9) throw Error(RDGPU_ERR_ARG, "rdgpu_fm_tarboton_flats: null pointer");                 \
-      check_dims(w, h, "rdgpu_fm_tarboton_flats", FLATS_MAX_CELLS);                                             \
-      T *d;                                                                                                     \
-      host_dem<T>(dem, w, h, &d);                                                                               \
-      const DinfAcc a = tarboton_flats_device<T>(d, nodata, w, h, nullptr);                                     \
-      const uint64_t n = (uint64_t)w * h;                                                                       \
-      float *p = Workspace::get().buf<float>("host.props", n * 9);                                              \
-      RD_LAUNCH("mfd.tarboton_props", k_tarboton_props, dim3(sgrid(n)), dim3(NTHR), 0, (hipStream_t) nullptr, a.rcv, a.sh1, \
-                a.sh2, p, n);                                                                                   \
-      RD_HIP(hipMemcpy(props9, p, n * 36, hipMemcpyDeviceToHost));                                              \
+      mfd_check_args(dem, props9, w, h, "rdgpu_fm_tarboton_flats", FLATS_MAX_CELLS);                            \
+      host_dem_to_f32<T>(dem, w, h, "host.props", props9, 9, [&](const T *d, float *p) {                        \
+        fm_tarboton_device<T>(tarboton_flats_device<T>, d, nodata, w, h, p, nullptr);                           \
+      });                                                                                                       \
     });                                                                                                         \
   }                                                                                                             \
   extern "C" int rdgpu_fa_tarboton_flats_dev_##SUF(const T *d_dem, T nodata, int w, int h, double *d_accum, void *st) { \
     return guarded([&] {                                                                                        \
-      if (!d_dem || !d_accum) throw Error(RDGPU_ERR_ARG, "rdgpu_fa_tarboton_flats: null pointer");              \
-      check_dims(w, h, "rdgpu_fa_tarboton_flats", FLATS_MAX_CELLS);                                             \
-      const DinfAcc a = tarboton_flats_device<T>(d_dem, nodata, w, h, (hipStream_t)st);                         \
-      mfd_accumulate<DinfAcc>(a, w, h, d_accum, (hipStream_t)st);                                               \
+      mfd_check_args(d_dem, d_accum, w, h, "rdgpu_fa_tarboton_flats", FLATS_MAX_CELLS);                         \
+      fa_tarboton_device<T>(tarboton_flats_device<T>, d_dem, nodata, w, h, d_accum, (hipStream_t)st);           \
     });                                                                                                         \
   }                                                                                                             \
   extern "C" int rdgpu_fa_tarboton_flats_##SUF(const T *dem, T nodata, int w, int h, double *accum) {           \
     return guarded([&] {                                                                                        \
-      if (!dem || !accum) throw Error(RDGPU_ERR_ARG, "rdgpu_fa_tarboton_flats: null pointer");                  \
-      check_dims(w, h, "rdgpu_fa_tarboton_flats", FLATS_MAX_CELLS);                                             \
-      T *d;                                                                                                     \
-      host_dem<T>(dem, w, h, &d);                                                                               \
-      const size_t n = (size_t)w * h;                                                                           \
-      double *da = Workspace::get().buf<double>("host.area", n);                                                \
-      RD_HIP(hipMemcpy(da, accum, n * 8, hipMemcpyHostToDevice));                                               \
-      const DinfAcc a = tarboton_flats_device<T>(d, nodata, w, h, nullptr);                                     \
-      mfd_accumulate<DinfAcc>(a, w, h, da, nullptr);                                                            \
-      RD_HIP(hipStreamSynchronize(nullptr));                                                                    \
-      RD_HIP(hipMemcpy(accum, da, n * 8, hipMemcpyDeviceToHost));                                               \
+      mfd_check_args(dem, accum, w, h, "rdgpu_fa_tarboton_flats", FLATS_MAX_CELLS);                             \
+      host_dem_accum<T>(dem, w, h, accum, [&](const T *d, double *da) {                                         \
+        fa_tarboton_device<T>(tarboton_flats_device<T>, d, nodata, w, h, da, nullptr);                          \
+      });                                                                                                       \
     });                                                                                                         \
   }
 RD_MFD_FLATS_API(u8, uint8_t)
@@ -782,49 +797,37 @@ extern "C" int rdgpu_dinf_flats_get_stats(rdgpu_dinf_flats_stats *out) {
   extern "C" int rdgpu_fm_mfd_dev_##SUF(const T *d_dem, T nodata, int w, int h, int method, double xparam,      \
                                         float *d_props9, void *st) {                                            \
     return guarded([&] {                                                                                        \
-      if (!d_dem || !d_props9) throw Error(RDGPU_ERR_ARG, "rdgpu_fm_mfd: null pointer");                        \
-      check_dims(w, h, "rdgpu_fm_mfd");                                                                         \
+      mfd_check_args(d_dem, d_props9, w, h, "rdgpu_fm_mfd");                                                    \
+      check_mfd_method(method);                                                                                 \
       fm_mfd_device<T>(d_dem, nodata, w, h, method, xparam, d_props9, (hipStream_t)st);                         \
     });                                                                                                         \
   }                                                                                                             \
   extern "C" int rdgpu_fm_mfd_##SUF(const T *dem, T nodata, int w, int h, int method, double xparam,            \
                                     float *props9) {                                                            \
     return guarded([&] {                                                                                        \
-      if (!dem || !props9) throw Error(RDGPU_ERR_ARG, "rdgpu_fm_mfd: null pointer");                            \
-      check_dims(w, h, "rdgpu_fm_mfd");                                                                         \
-      T *d;                                                                                                     \
-      host_dem<T>(dem, w, h, &d);                                                                               \
-      const uint64_t n = (uint64_t)w * h;                                                                       \
-      float *p = Workspace::get().buf<float>("host.props", n * 9);                                              \
-      fm_mfd_device<T>(d, nodata, w, h, method, xparam, p, nullptr);                                            \
-      RD_HIP(hipMemcpy(props9, p, n * 36, hipMemcpyDeviceToHost));                                              \
+      mfd_check_args(dem, props9, w, h, "rdgpu_fm_mfd");                                                        \
+      check_mfd_method(method);                                                                                 \
+      host_dem_to_f32<T>(dem, w, h, "host.props", props9, 9, [&](const T *d, float *p) {                        \
+        fm_mfd_device<T>(d, nodata, w, h, method, xparam, p, nullptr);                                          \
+      });                                                                                                       \
     });                                                                                                         \
   }                                                                                                             \
   extern "C" int rdgpu_fa_mfd_dev_##SUF(const T *d_dem, T nodata, int w, int h, int method, double xparam,      \
                                         double *d_accum, void *st) {                                            \
     return guarded([&] {                                                                                        \
-      if (!d_dem || !d_accum) throw Error(RDGPU_ERR_ARG, "rdgpu_fa_mfd: null pointer");                         \
-      check_dims(w, h, "rdgpu_fa_mfd");                                                                         \
-      float *p = Workspace::get().buf<float>("mfd.props", (uint64_t)w * h * 9);                                 \
-      fm_mfd_device<T>(d_dem, nodata, w, h, method, xparam, p, (hipStream_t)st);                                \
-      mfd_accumulate<PropsAcc>(PropsAcc{p}, w, h, d_accum, (hipStream_t)st);                                    \
+      mfd_check_args(d_dem, d_accum, w, h, "rdgpu_fa_mfd");                                                     \
+      check_mfd_method(method);                                                                                 \
+      fa_mfd_device<T>(d_dem, nodata, w, h, method, xparam, d_accum, (hipStream_t)st);                          \
     });                                                                                                         \
   }                                                                                                             \
   extern "C" int rdgpu_fa_mfd_##SUF(const T *dem, T nodata, int w, int h, int method, double xparam,            \
                                     double *accum) {                                                            \
     return guarded([&] {                                                                                        \
-      if (!dem || !accum) throw Error(RDGPU_ERR_ARG, "rdgpu_fa_mfd: null pointer");                             \
-      check_dims(w, h, "rdgpu_fa_mfd");                                                                         \
-      T *d;                                                                                                     \
-      host_dem<T>(dem, w, h, &d);                                                                               \
-      const size_t n = (size_t)w * h;                                                                           \
-      double *da = Workspace::get().buf<double>("host.area", n);                                                \
-      RD_HIP(hipMemcpy(da, accum, n * 8, hipMemcpyHostToDevice));                                               \
-      float *p = Workspace::get().buf<float>("mfd.props", n * 9);                                               \
-      fm_mfd_device<T>(d, nodata, w, h, method, xparam, p, nullptr);                                            \
-      mfd_accumulate<PropsAcc>(PropsAcc{p}, w, h, da, nullptr);                                                 \
-      RD_HIP(hipStreamSynchronize(nullptr));                                                                    \
-      RD_HIP(hipMemcpy(accum, da, n * 8, hipMemcpyDeviceToHost));                                               \
+      mfd_check_args(dem, accum, w, h, "rdgpu_fa_mfd");                                                         \
+      check_mfd_method(method);                                                                                 \
+      host_dem_accum<T>(dem, w, h, accum, [&](const T *d, double *da) {                                         \
+        fa_mfd_device<T>(d, nodata, w, h, method, xparam, da, nullptr);                                         \
+      });                                                                                                       \
     });                                                                                                         \
   }
 RD_MFD2_API(u8, uint8_t)
@@ -839,23 +842,19 @@ RD_MFD2_API(i8, int8_t)
 // FlowAccumulation(const Array3D<float>&, Array2D<double>&), methods/flow_accumulation_generic.hpp:33-100
 extern "C" int rdgpu_flow_accumulation_dev_f64(const float *d_props9, int w, int h, double *d_accum, void *st) {
   return guarded([&] {
-    if (!d_props9 || !d_accum) throw Error(RDGPU_ERR_ARG, "rdgpu_flow_accumulation: null pointer");
-    check_dims(w, h, "rdgpu_flow_accumulation");
+    mfd_check_args(d_props9, d_accum, w, h, "rdgpu_flow_accumulation");
     mfd_accumulate<PropsAcc>(PropsAcc{d_props9}, w, h, d_accum, (hipStream_t)st);
   });
 }
 extern "C" int rdgpu_flow_accumulation_f64(const float *props9, int w, int h, double *accum) {
   return guarded([&] {
-    if (!props9 || !accum) throw Error(RDGPU_ERR_ARG, "rdgpu_flow_accumulation: null pointer");
-    check_dims(w, h, "rdgpu_flow_accumulation");
+    mfd_check_args(props9, accum, w, h, "rdgpu_flow_accumulation");
     const size_t n = (size_t)w * h;
-    float *dp = Workspace::get().buf<float>("host.props", n * 9);
-    double *da = Workspace::get().buf<double>("host.area", n);
-    RD_HIP(hipMemcpy(dp, props9, n * 36, hipMemcpyHostToDevice));
-    RD_HIP(hipMemcpy(da, accum, n * 8, hipMemcpyHostToDevice));
+    HostStage st;
+    const float *dp = st.in("host.props", props9, n * 9);
+    double *da = st.inout("host.area", accum, n);
     mfd_accumulate<PropsAcc>(PropsAcc{dp}, w, h, da, nullptr);
-    RD_HIP(hipStreamSynchronize(nullptr));
-    RD_HIP(hipMemcpy(accum, da, n * 8, hipMemcpyDeviceToHost));
+    st.finish();
   });
 }
 extern "C" int rdgpu_flow_accumulation_rounds(uint32_t *rounds) {

@@ -210,8 +210,10 @@ struct DistParams {
   double cell_x, cell_y;
 };
 
-static void check_args(const char *who, int w, int h, bool have_elev, int stat, double cx, double cy, const void *dist,
+// in: the proportions or the DEM
+static void check_args(const char *who, const void *in, int w, int h, bool have_elev, int stat, double cx, double cy, const void *dist,
                        const void *drop, uint64_t max_cells = 0xFFFF0000ull) {
+  if (!in) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
   check_dims(w, h, who, max_cells);
   if (!dist && !drop) throw Error(RDGPU_ERR_ARG, std::string(who) + ": no output requested");
   if (drop && !have_elev) throw Error(RDGPU_ERR_ARG, std::string(who) + ": drop needs the elevations");
@@ -256,26 +258,6 @@ static void mfd_distance(ACC a, int w, int h, const uint8_t *d_chan, const doubl
             out_nodata, n);
 }
 
-// host planes of a call: device copies of the optional inputs, device planes for the requested outputs
-struct HostPlanes {
-  uint8_t *chan = nullptr;
-  double *dist = nullptr, *drop = nullptr;
-  HostPlanes(const uint8_t *h_chan, bool want_dist, bool want_drop, size_t n) {
-    Workspace &ws = Workspace::get();
-    if (h_chan) {
-      chan = ws.buf<uint8_t>("host.mfddist.chan", n);
-      RD_HIP(hipMemcpy(chan, h_chan, n, hipMemcpyHostToDevice));
-    }
-    if (want_dist) dist = ws.buf<double>("host.mfddist.dist", n);
-    if (want_drop) drop = ws.buf<double>("host.mfddist.drop", n);
-  }
-  void fetch(double *h_dist, double *h_drop, size_t n) const {
-    RD_HIP(hipStreamSynchronize(nullptr));
-    if (h_dist) RD_HIP(hipMemcpy(h_dist, dist, n * 8, hipMemcpyDeviceToHost));
-    if (h_drop) RD_HIP(hipMemcpy(h_drop, drop, n * 8, hipMemcpyDeviceToHost));
-  }
-};
-
 // the elevations of a DEM as doubles (exact for every element type); a float64 DEM is used as it is
 template <class T>
 static const double *elev_plane(const T *d_z, uint64_t n, hipStream_t s) {
@@ -287,6 +269,16 @@ static const double *elev_plane(const T *d_z, uint64_t n, hipStream_t s) {
   }
 }
 
+// the proportions from the DEM (tarboton: with or without the flats patched), then the distances: what the two doors of a DEM
+// entry run, on the caller's stream or on the null stream
+template <class T>
+static void dinf_distance(TarbotonFn<T> tarboton, const T *d_dem, T nodata, int w, int h, const uint8_t *d_chan, const DistParams &pr,
+                          double *d_dist, double *d_drop, double out_nodata, hipStream_t s) {
+  const DinfAcc a = tarboton(d_dem, nodata, w, h, s);
+  const double *e = d_drop ? elev_plane<T>(d_dem, (uint64_t)w * h, s) : nullptr;
+  mfd_distance<DinfAcc>(a, w, h, d_chan, e, pr, d_dist, d_drop, out_nodata, s);
+}
+
 }  // namespace rdgpu
 
 using namespace rdgpu;
@@ -295,8 +287,7 @@ extern "C" int rdgpu_mfd_distance_down_dev(const float *d_props9, int w, int h, 
                                            int stat, int strict, double cell_x, double cell_y, double *d_dist, double *d_drop,
                                            double out_nodata, void *st) {
   return guarded([&] {
-    if (!d_props9) throw Error(RDGPU_ERR_ARG, "rdgpu_mfd_distance_down: null pointer");
-    check_args("rdgpu_mfd_distance_down", w, h, d_elev != nullptr, stat, cell_x, cell_y, d_dist, d_drop);
+    check_args("rdgpu_mfd_distance_down", d_props9, w, h, d_elev != nullptr, stat, cell_x, cell_y, d_dist, d_drop);
     mfd_distance<PropsAcc>(PropsAcc{d_props9}, w, h, d_chan, d_elev, DistParams{stat, strict, cell_x, cell_y}, d_dist, d_drop,
                            out_nodata, (hipStream_t)st);
   });
@@ -304,20 +295,15 @@ extern "C" int rdgpu_mfd_distance_down_dev(const float *d_props9, int w, int h, 
 extern "C" int rdgpu_mfd_distance_down(const float *props9, int w, int h, const uint8_t *chan, const double *elev, int stat,
                                        int strict, double cell_x, double cell_y, double *dist, double *drop, double out_nodata) {
   return guarded([&] {
-    if (!props9) throw Error(RDGPU_ERR_ARG, "rdgpu_mfd_distance_down: null pointer");
-    check_args("rdgpu_mfd_distance_down", w, h, elev != nullptr, stat, cell_x, cell_y, dist, drop);
+    check_args("rdgpu_mfd_distance_down", props9, w, h, elev != nullptr, stat, cell_x, cell_y, dist, drop);
     const size_t n = (size_t)w * h;
-    float *dp = Workspace::get().buf<float>("host.props", n * 9);
-    RD_HIP(hipMemcpy(dp, props9, n * 36, hipMemcpyHostToDevice));
-    double *de = nullptr;
-    if (drop) {
-      de = Workspace::get().buf<double>("host.mfddist.elev", n);
-      RD_HIP(hipMemcpy(de, elev, n * 8, hipMemcpyHostToDevice));
-    }
-    const HostPlanes hp(chan, dist != nullptr, drop != nullptr, n);
-    mfd_distance<PropsAcc>(PropsAcc{dp}, w, h, hp.chan, de, DistParams{stat, strict, cell_x, cell_y}, hp.dist, hp.drop, out_nodata,
-                           nullptr);
-    hp.fetch(dist, drop, n);
+    HostStage hs;
+    const float *dp = hs.in("host.props", props9, n * 9);
+    const double *de = hs.in("host.mfddist.elev", drop ? elev : nullptr, n);   // (read for the drop only)
+    const uint8_t *dc = hs.in("host.mfddist.chan", chan, n);
+    double *dd = hs.out("host.mfddist.dist", dist, n), *dr = hs.out("host.mfddist.drop", drop, n);
+    mfd_distance<PropsAcc>(PropsAcc{dp}, w, h, dc, de, DistParams{stat, strict, cell_x, cell_y}, dd, dr, out_nodata, nullptr);
+    hs.finish();
   });
 }
 extern "C" int rdgpu_mfd_distance_rounds(uint32_t *rounds) {
@@ -331,29 +317,23 @@ extern "C" int rdgpu_mfd_distance_rounds(uint32_t *rounds) {
                                                     int strict, double cell_x, double cell_y, double *d_dist, double *d_drop, \
                                                     double out_nodata, void *st) {                                        \
     return guarded([&] {                                                                                                  \
-      if (!d_dem) throw Error(RDGPU_ERR_ARG, "rdgpu_dinf_distance_down" #FL ": null pointer");                            \
-      check_args("rdgpu_dinf_distance_down" #FL, w, h, true, stat, cell_x, cell_y, d_dist, d_drop, MAXC);                 \
-      const DinfAcc a = ACCESSOR<T>(d_dem, nodata, w, h, (hipStream_t)st);                                                \
-      const double *e = d_drop ? elev_plane<T>(d_dem, (uint64_t)w * h, (hipStream_t)st) : nullptr;                        \
-      mfd_distance<DinfAcc>(a, w, h, d_chan, e, DistParams{stat, strict, cell_x, cell_y}, d_dist, d_drop, out_nodata,     \
-                            (hipStream_t)st);                                                                             \
+      check_args("rdgpu_dinf_distance_down" #FL, d_dem, w, h, true, stat, cell_x, cell_y, d_dist, d_drop, MAXC);          \
+      dinf_distance<T>(ACCESSOR<T>, d_dem, nodata, w, h, d_chan, DistParams{stat, strict, cell_x, cell_y}, d_dist, d_drop, \
+                       out_nodata, (hipStream_t)st);                                                                      \
     });                                                                                                                   \
   }                                                                                                                       \
   extern "C" int rdgpu_dinf_distance_down##FL##_##SUF(const T *dem, T nodata, int w, int h, const uint8_t *chan, int stat, \
                                                 int strict, double cell_x, double cell_y, double *dist, double *drop,     \
                                                 double out_nodata) {                                                      \
     return guarded([&] {                                                                                                  \
-      if (!dem) throw Error(RDGPU_ERR_ARG, "rdgpu_dinf_distance_down" #FL ": null pointer");                              \
-      check_args("rdgpu_dinf_distance_down" #FL, w, h, true, stat, cell_x, cell_y, dist, drop, MAXC);                     \
+      check_args("rdgpu_dinf_distance_down" #FL, dem, w, h, true, stat, cell_x, cell_y, dist, drop, MAXC);                \
       const size_t n = (size_t)w * h;                                                                                     \
-      T *d;                                                                                                               \
-      host_dem<T>(dem, w, h, &d);                                                                                         \
-      const HostPlanes hp(chan, dist != nullptr, drop != nullptr, n);                                                     \
-      const DinfAcc a = ACCESSOR<T>(d, nodata, w, h, nullptr);                                                            \
-      const double *e = drop ? elev_plane<T>(d, n, nullptr) : nullptr;                                                    \
-      mfd_distance<DinfAcc>(a, w, h, hp.chan, e, DistParams{stat, strict, cell_x, cell_y}, hp.dist, hp.drop, out_nodata,  \
-                            nullptr);                                                                                     \
-      hp.fetch(dist, drop, n);                                                                                            \
+      HostStage hs;                                                                                                       \
+      const T *d = hs.in("host.dem", dem, n);                                                                             \
+      const uint8_t *dc = hs.in("host.mfddist.chan", chan, n);                                                            \
+      double *dd = hs.out("host.mfddist.dist", dist, n), *dr = hs.out("host.mfddist.drop", drop, n);                      \
+      dinf_distance<T>(ACCESSOR<T>, d, nodata, w, h, dc, DistParams{stat, strict, cell_x, cell_y}, dd, dr, out_nodata, nullptr); \
+      hs.finish();                                                                                                        \
     });                                                                                                                   \
   }
 RD_DINF_DIST_API(, tarboton_device, 0xFFFF0000ull, u8, uint8_t)

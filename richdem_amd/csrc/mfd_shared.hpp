@@ -52,11 +52,8 @@ static inline void check_dims(int w, int h, const char *who, uint64_t max_cells 
 }
 constexpr uint64_t FLATS_MAX_CELLS = 0x7FFF0000ull;   // the flat resolution's limit: the smaller of the two engines'
 
+// tarboton_device or tarboton_flats_device: what tells an entry point from its `_flats` twin
 template <class T>
-static void host_dem(const T *dem, int w, int h, T **d) {
-  const size_t n = (size_t)w * h;
-  *d = Workspace::get().buf<T>("host.dem", n);
-  RD_HIP(hipMemcpy(*d, dem, n * sizeof(T), hipMemcpyHostToDevice));
-}
+using TarbotonFn = DinfAcc (*)(const T *, T, int, int, hipStream_t);
 
 }  // namespace rdgpu

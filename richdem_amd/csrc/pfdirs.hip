@@ -623,11 +623,15 @@ static void check_rc(int rc) {
   if (rc != 0) throw Error(rc, std::string("rdgpu_pf_flowdirs: ") + rdgpu_last_error());
 }
 
-template <class T>
-void pf_flowdirs_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, hipStream_t s) {
-  if (!d_z || !d_dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_pf_flowdirs: null pointer");
+static void check_args(const void *z, const void *dirs, int w, int h) {
+  if (!z || !dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_pf_flowdirs: null pointer");
   if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_pf_flowdirs: width and height must be positive");
   if ((uint64_t)w * (uint64_t)h > 0x7FFF0000ull) throw Error(RDGPU_ERR_ARG, "rdgpu_pf_flowdirs: raster too large");
+}
+
+template <class T>
+void pf_flowdirs_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, hipStream_t s) {
+  check_args(d_z, d_dirs, w, h);
   const uint64_t n = (uint64_t)w * h;
   Workspace &ws = Workspace::get();
   g_stats = rdgpu_pf_flowdirs_stats{0, 0, 0, 0, 0};
@@ -991,14 +995,13 @@ void pf_flowdirs_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, h
 
 template <class T>
 static void pf_flowdirs_host(const T *dem, T nodata, int w, int h, uint8_t *dirs) {
-  if (!dem || !dirs) throw Error(RDGPU_ERR_ARG, "rdgpu_pf_flowdirs: null pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_pf_flowdirs: width and height must be positive");
+  check_args(dem, dirs, w, h);
   const size_t n = (size_t)w * h;
-  T *d = Workspace::get().buf<T>("host.dem", n);
-  uint8_t *dd = Workspace::get().buf<uint8_t>("host.dirs", n);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
+  HostStage st;
+  const T *d = st.in("host.dem", dem, n);
+  uint8_t *dd = st.out("host.dirs", dirs, n);
   pf_flowdirs_device<T>(d, nodata, w, h, dd, nullptr);
-  RD_HIP(hipMemcpy(dirs, dd, n, hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 }  // namespace pfd

@@ -365,25 +365,18 @@ static void stream_reaches_host(const uint8_t *dirs, uint8_t nodata, int w, int 
                                 const char *who) {
   rc_check_args(dirs, w, h, cx, cy, table, capacity, count, who);
   const size_t n = (size_t)w * h;
-  Workspace &ws = Workspace::get();
-  uint8_t *dd = ws.buf<uint8_t>("host.dirs", n);
-  uint8_t *dc = chan ? ws.buf<uint8_t>("host.reaches.chan", n) : nullptr;
-  uint8_t *dor = order ? ws.buf<uint8_t>("host.reaches.order", n) : nullptr;
-  uint32_t *dr = reach ? ws.buf<uint32_t>("host.reaches.reach", n) : nullptr;
-  uint32_t *dca = catchment ? ws.buf<uint32_t>("host.reaches.catchment", n) : nullptr;
+  HostStage st;
+  const uint8_t *dd = st.in("host.dirs", dirs, n);
+  const uint8_t *dc = st.in("host.reaches.chan", chan, n);
+  const uint8_t *dor = st.in("host.reaches.order", order, n);
+  uint32_t *dn = st.out("host.reaches.count", count, 1);
+  uint32_t *dr = st.out("host.reaches.reach", reach, n);
+  uint32_t *dca = st.out("host.reaches.catchment", catchment, n);
   const uint32_t cap = table ? (uint32_t)std::min<uint64_t>(capacity, n) : 0u;
-  rdgpu_reach *dt = cap ? ws.buf<rdgpu_reach>("host.reaches.table", cap) : nullptr;
-  uint32_t *dn = ws.buf<uint32_t>("host.reaches.count", 1);
-  RD_HIP(hipMemcpy(dd, dirs, n, hipMemcpyHostToDevice));
-  if (chan) RD_HIP(hipMemcpy(dc, chan, n, hipMemcpyHostToDevice));
-  if (order) RD_HIP(hipMemcpy(dor, order, n, hipMemcpyHostToDevice));
+  rdgpu_reach *dt = cap ? Workspace::get().buf<rdgpu_reach>("host.reaches.table", cap) : nullptr;   // (fetched: cut to the count)
   stream_reaches_device(dd, nodata, w, h, dc, dor, cx, cy, dr, dca, dt, cap, dn, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(count, dn, sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (reach) RD_HIP(hipMemcpy(reach, dr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (catchment) RD_HIP(hipMemcpy(catchment, dca, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  const uint32_t wrote = std::min(*count, cap);
-  if (wrote) RD_HIP(hipMemcpy(table, dt, (size_t)wrote * sizeof(rdgpu_reach), hipMemcpyDeviceToHost));
+  st.finish();
+  st.fetch(table, dt, std::min(*count, cap));
 }
 
 }  // namespace rdgpu

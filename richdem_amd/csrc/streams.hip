@@ -290,10 +290,19 @@ __global__ __launch_bounds__(NTHR) void k_so_kinds(const uint8_t *__restrict__ d
 // ---- drivers ----------------------------------------------------------------------------------------------------------
 static thread_local int so_last_levels = 0, so_last_rounds = 0, so_last_launches = 0;
 
-static void stream_order_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, const uint8_t *d_chan, uint8_t *d_order,
-                                hipStream_t s, const char *who) {
-  if (!d_dirs || !d_order) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
+// the argument checks of an entry's two doors (host pointers, device pointers): thrown before anything is staged
+static void so_check_args(bool pointers, int w, int h, const char *who) {
+  if (!pointers) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
   check_forest_dims(w, h, who);
+}
+static void so_check_channels_args(const void *accum, const void *chan, int w, int h, double threshold, const char *who) {
+  so_check_args(accum && chan, w, h, who);
+  if (!std::isfinite(threshold)) throw Error(RDGPU_ERR_ARG, std::string(who) + ": the threshold must be finite");
+}
+
+// arguments checked by the caller (so_check_args), here and in the two drivers below
+static void stream_order_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, const uint8_t *d_chan, uint8_t *d_order,
+                                hipStream_t s) {
   const uint64_t n = (uint64_t)w * h;
   const ForestDims fd(w, h);
   const uint32_t tilesX = fd.tilesX, ntiles = fd.ntiles, nnodes = (uint32_t)fd.nnodes;
@@ -350,20 +359,14 @@ static void stream_order_device(const uint8_t *d_dirs, uint8_t nodata, int w, in
   so_last_launches = launches;
 }
 
-static void channels_device(const double *d_accum, double nodata, double threshold, int w, int h, uint8_t *d_chan, hipStream_t s,
-                            const char *who) {
-  if (!d_accum || !d_chan) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-  check_forest_dims(w, h, who);
-  if (!std::isfinite(threshold)) throw Error(RDGPU_ERR_ARG, std::string(who) + ": the threshold must be finite");
+static void channels_device(const double *d_accum, double nodata, double threshold, int w, int h, uint8_t *d_chan, hipStream_t s) {
   const uint64_t n = (uint64_t)w * h;
   RD_LAUNCH("streams.channels", k_so_channels, dim3((uint32_t)((n + NTHR - 1) / NTHR)), dim3(NTHR), 0, s, d_accum, nodata, threshold,
             n, d_chan);
 }
 
 static void stream_links_device(const uint8_t *d_dirs, uint8_t nodata, int w, int h, const uint8_t *d_chan, const uint8_t *d_order,
-                                uint8_t *d_kind, hipStream_t s, const char *who) {
-  if (!d_dirs || !d_order || !d_kind) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-  check_forest_dims(w, h, who);
+                                uint8_t *d_kind, hipStream_t s) {
   const uint64_t n = (uint64_t)w * h;
   RD_LAUNCH("streams.kinds", k_so_kinds, dim3((uint32_t)((n + NTHR - 1) / NTHR)), dim3(NTHR), 0, s, d_dirs, nodata, w, h, d_chan,
             d_order, d_kind);
@@ -377,25 +380,21 @@ using namespace rdgpu;
 extern "C" int rdgpu_d8_stream_order(const uint8_t *dirs, uint8_t dir_nodata, int width, int height, const uint8_t *chan,
                                      uint8_t *order) {
   return guarded([&] {
-    const char *who = "rdgpu_d8_stream_order";
-    if (!dirs || !order) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-    check_forest_dims(width, height, who);
+    so_check_args(dirs && order, width, height, "rdgpu_d8_stream_order");
     const size_t n = (size_t)width * height;
-    Workspace &ws = Workspace::get();
-    uint8_t *dd = ws.buf<uint8_t>("host.dirs", n);
-    uint8_t *dc = chan ? ws.buf<uint8_t>("host.streams.chan", n) : nullptr;
-    uint8_t *dout = ws.buf<uint8_t>("host.streams.order", n);
-    RD_HIP(hipMemcpy(dd, dirs, n, hipMemcpyHostToDevice));
-    if (chan) RD_HIP(hipMemcpy(dc, chan, n, hipMemcpyHostToDevice));
-    stream_order_device(dd, dir_nodata, width, height, dc, dout, nullptr, who);
-    RD_HIP(hipStreamSynchronize(nullptr));
-    RD_HIP(hipMemcpy(order, dout, n, hipMemcpyDeviceToHost));
+    HostStage st;
+    const uint8_t *dd = st.in("host.dirs", dirs, n);
+    const uint8_t *dc = st.in("host.streams.chan", chan, n);
+    uint8_t *dout = st.out("host.streams.order", order, n);
+    stream_order_device(dd, dir_nodata, width, height, dc, dout, nullptr);
+    st.finish();
   });
 }
 extern "C" int rdgpu_d8_stream_order_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int width, int height, const uint8_t *d_chan,
                                          uint8_t *d_order, void *hip_stream) {
   return guarded([&] {
-    stream_order_device(d_dirs, dir_nodata, width, height, d_chan, d_order, (hipStream_t)hip_stream, "rdgpu_d8_stream_order_dev");
+    so_check_args(d_dirs && d_order, width, height, "rdgpu_d8_stream_order_dev");
+    stream_order_device(d_dirs, dir_nodata, width, height, d_chan, d_order, (hipStream_t)hip_stream);
   });
 }
 extern "C" int rdgpu_d8_stream_order_get_stats(int *levels, int *rounds_per_level, int *launches) {
@@ -408,51 +407,41 @@ extern "C" int rdgpu_d8_stream_order_get_stats(int *levels, int *rounds_per_leve
 extern "C" int rdgpu_d8_channels_f64(const double *accum, double accum_nodata, double threshold, int width, int height,
                                      uint8_t *chan) {
   return guarded([&] {
-    const char *who = "rdgpu_d8_channels_f64";
-    if (!accum || !chan) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-    check_forest_dims(width, height, who);
-    if (!std::isfinite(threshold)) throw Error(RDGPU_ERR_ARG, std::string(who) + ": the threshold must be finite");
+    so_check_channels_args(accum, chan, width, height, threshold, "rdgpu_d8_channels_f64");
     const size_t n = (size_t)width * height;
-    Workspace &ws = Workspace::get();
-    double *da = ws.buf<double>("host.streams.accum", n);
-    uint8_t *dc = ws.buf<uint8_t>("host.streams.chan", n);
-    RD_HIP(hipMemcpy(da, accum, n * sizeof(double), hipMemcpyHostToDevice));
-    channels_device(da, accum_nodata, threshold, width, height, dc, nullptr, who);
-    RD_HIP(hipStreamSynchronize(nullptr));
-    RD_HIP(hipMemcpy(chan, dc, n, hipMemcpyDeviceToHost));
+    HostStage st;
+    const double *da = st.in("host.streams.accum", accum, n);
+    uint8_t *dc = st.out("host.streams.chan", chan, n);
+    channels_device(da, accum_nodata, threshold, width, height, dc, nullptr);
+    st.finish();
   });
 }
 extern "C" int rdgpu_d8_channels_dev_f64(const double *d_accum, double accum_nodata, double threshold, int width, int height,
                                          uint8_t *d_chan, void *hip_stream) {
   return guarded([&] {
-    channels_device(d_accum, accum_nodata, threshold, width, height, d_chan, (hipStream_t)hip_stream, "rdgpu_d8_channels_dev_f64");
+    so_check_channels_args(d_accum, d_chan, width, height, threshold, "rdgpu_d8_channels_dev_f64");
+    channels_device(d_accum, accum_nodata, threshold, width, height, d_chan, (hipStream_t)hip_stream);
   });
 }
 
 extern "C" int rdgpu_d8_stream_links(const uint8_t *dirs, uint8_t dir_nodata, int width, int height, const uint8_t *chan,
                                      const uint8_t *order, uint8_t *kind) {
   return guarded([&] {
-    const char *who = "rdgpu_d8_stream_links";
-    if (!dirs || !order || !kind) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
-    check_forest_dims(width, height, who);
+    so_check_args(dirs && order && kind, width, height, "rdgpu_d8_stream_links");
     const size_t n = (size_t)width * height;
-    Workspace &ws = Workspace::get();
-    uint8_t *dd = ws.buf<uint8_t>("host.dirs", n);
-    uint8_t *dc = chan ? ws.buf<uint8_t>("host.streams.chan", n) : nullptr;
-    uint8_t *dord = ws.buf<uint8_t>("host.streams.order", n);
-    uint8_t *dk = ws.buf<uint8_t>("host.streams.kind", n);
-    RD_HIP(hipMemcpy(dd, dirs, n, hipMemcpyHostToDevice));
-    if (chan) RD_HIP(hipMemcpy(dc, chan, n, hipMemcpyHostToDevice));
-    RD_HIP(hipMemcpy(dord, order, n, hipMemcpyHostToDevice));
-    stream_links_device(dd, dir_nodata, width, height, dc, dord, dk, nullptr, who);
-    RD_HIP(hipStreamSynchronize(nullptr));
-    RD_HIP(hipMemcpy(kind, dk, n, hipMemcpyDeviceToHost));
+    HostStage st;
+    const uint8_t *dd = st.in("host.dirs", dirs, n);
+    const uint8_t *dc = st.in("host.streams.chan", chan, n);
+    const uint8_t *dord = st.in("host.streams.order", order, n);
+    uint8_t *dk = st.out("host.streams.kind", kind, n);
+    stream_links_device(dd, dir_nodata, width, height, dc, dord, dk, nullptr);
+    st.finish();
   });
 }
 extern "C" int rdgpu_d8_stream_links_dev(const uint8_t *d_dirs, uint8_t dir_nodata, int width, int height, const uint8_t *d_chan,
                                          const uint8_t *d_order, uint8_t *d_kind, void *hip_stream) {
   return guarded([&] {
-    stream_links_device(d_dirs, dir_nodata, width, height, d_chan, d_order, d_kind, (hipStream_t)hip_stream,
-                        "rdgpu_d8_stream_links_dev");
+    so_check_args(d_dirs && d_order && d_kind, width, height, "rdgpu_d8_stream_links_dev");
+    stream_links_device(d_dirs, dir_nodata, width, height, d_chan, d_order, d_kind, (hipStream_t)hip_stream);
   });
 }

@@ -222,16 +222,16 @@ void terrain_host(const T *dem, T nodata, int w, int h, double cx, double cy, fl
   check_args(dem, w, h, cx, cy, zscale, mask, outs);
   const size_t n = (size_t)w * h;
   const int k_out = __builtin_popcount(mask);
-  T *d = Workspace::get().buf<T>("host.dem", n);
-  float *dd = Workspace::get().buf<float>("host.terrain", n * k_out);
+  HostStage st;
+  const T *d = st.in("host.dem", dem, n);
+  float *dd = Workspace::get().buf<float>("host.terrain", n * k_out);   // the planes asked for, back to back in one buffer
   float *planes[RDGPU_TA_COUNT] = {};
   for (int k = 0, j = 0; k < RDGPU_TA_COUNT; k++)
     if (mask >> k & 1u) planes[k] = dd + n * (j++);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
   terrain_device<T>(d, nodata, w, h, cx, cy, zscale, mask, planes, out_nodata, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
+  st.finish();
   for (int k = 0; k < RDGPU_TA_COUNT; k++)
-    if (mask >> k & 1u) RD_HIP(hipMemcpy(outs[k], planes[k], n * sizeof(float), hipMemcpyDeviceToHost));
+    if (mask >> k & 1u) st.fetch(outs[k], planes[k], n);
 }
 
 unsigned id_mask(int attribute) {
@@ -241,12 +241,16 @@ unsigned id_mask(int attribute) {
   return 1u << attribute;
 }
 
-void spi_cti_device(const double *d_fa, double fa_nodata, const float *d_slope, float slope_nodata, int w, int h,
-                    double cx, double cy, float *d_out, bool cti, hipStream_t s) {
-  if (!d_fa || !d_slope || !d_out) throw Error(RDGPU_ERR_ARG, "rdgpu_ta_spi / _cti: null pointer");
+void spi_cti_check(const void *fa, const void *slope, const void *out, int w, int h, double cx, double cy) {
+  if (!fa || !slope || !out) throw Error(RDGPU_ERR_ARG, "rdgpu_ta_spi / _cti: null pointer");
   if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_ta_spi / _cti: width and height must be positive");
   if (!std::isfinite(cx) || !std::isfinite(cy) || cx == 0 || cy == 0)
     throw Error(RDGPU_ERR_ARG, "rdgpu_ta_spi / _cti: the cell lengths must be finite and non-zero");
+}
+
+// arguments checked by the caller (spi_cti_check)
+void spi_cti_device(const double *d_fa, double fa_nodata, const float *d_slope, float slope_nodata, int w, int h,
+                    double cx, double cy, float *d_out, bool cti, hipStream_t s) {
   const double area = std::fabs(cx * cy);   // getCellArea (Array2D.hpp:1378-1381)
   const size_t n = (size_t)w * h;
   const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 256u * 32u);
@@ -260,19 +264,14 @@ void spi_cti_device(const double *d_fa, double fa_nodata, const float *d_slope, 
 
 void spi_cti_host(const double *fa, double fa_nodata, const float *slope, float slope_nodata, int w, int h, double cx,
                   double cy, float *out, bool cti) {
-  if (!fa || !slope || !out) throw Error(RDGPU_ERR_ARG, "rdgpu_ta_spi / _cti: null pointer");
-  if (w <= 0 || h <= 0) throw Error(RDGPU_ERR_ARG, "rdgpu_ta_spi / _cti: width and height must be positive");
-  if (!std::isfinite(cx) || !std::isfinite(cy) || cx == 0 || cy == 0)
-    throw Error(RDGPU_ERR_ARG, "rdgpu_ta_spi / _cti: the cell lengths must be finite and non-zero");
+  spi_cti_check(fa, slope, out, w, h, cx, cy);
   const size_t n = (size_t)w * h;
-  double *dfa = Workspace::get().buf<double>("host.ta_fa", n);
-  float *ds = Workspace::get().buf<float>("host.ta_slope", n);
-  float *dout = Workspace::get().buf<float>("host.terrain", n);
-  RD_HIP(hipMemcpy(dfa, fa, n * sizeof(double), hipMemcpyHostToDevice));
-  RD_HIP(hipMemcpy(ds, slope, n * sizeof(float), hipMemcpyHostToDevice));
+  HostStage st;
+  const double *dfa = st.in("host.ta_fa", fa, n);
+  const float *ds = st.in("host.ta_slope", slope, n);
+  float *dout = st.out("host.terrain", out, n);
   spi_cti_device(dfa, fa_nodata, ds, slope_nodata, w, h, cx, cy, dout, cti, nullptr);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(out, dout, n * sizeof(float), hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 }  // namespace
@@ -332,6 +331,7 @@ RD_TERRAIN_API(u64, uint64_t)
                                        float slope_nodata, int w, int h, double cell_x, double cell_y, float *d_out,  \
                                        void *stream) {                                                                \
     return guarded([&] {                                                                                              \
+      spi_cti_check(d_fa, d_slope, d_out, w, h, cell_x, cell_y);                                                      \
       spi_cti_device(d_fa, fa_nodata, d_slope, slope_nodata, w, h, cell_x, cell_y, d_out, CTI, (hipStream_t)stream);  \
     });                                                                                                               \
   }

@@ -336,7 +336,6 @@ static void upslope_host(const uint8_t *dirs, uint8_t nodata, int w, int h, cons
   if (!dirs || !out) throw Error(RDGPU_ERR_ARG, std::string(who) + ": null pointer");
   check_forest_dims(w, h, who);
   const size_t n = (size_t)w * h;
-  Workspace &ws = Workspace::get();
   std::vector<uint32_t> line;
   if (MODE == UP_CELLS) line = upslope_line(w, h, x0, y0, x1, y1, who);
   if (MODE == UP_CATCH && n_seeds) {
@@ -344,24 +343,18 @@ static void upslope_host(const uint8_t *dirs, uint8_t nodata, int w, int h, cons
     for (uint32_t i = 0; i < n_seeds; i++)
       if (cells[i] >= n) throw Error(RDGPU_ERR_ARG, std::string(who) + ": a seed cell lies outside the raster");
   }
-  uint8_t *dd = ws.buf<uint8_t>("host.dirs", n);
-  O *dout = ws.buf<O>("host.upslope", n);
-  RD_HIP(hipMemcpy(dd, dirs, n, hipMemcpyHostToDevice));
+  HostStage st;
+  const uint8_t *dd = st.in("host.dirs", dirs, n);
+  O *dout = st.out("host.upslope", out, n);
   if (MODE == UP_CELLS) {
     upslope_cells_device(dd, nodata, w, h, x0, y0, x1, y1, reinterpret_cast<uint8_t *>(dout), nullptr, who);
   } else {
-    uint32_t *dc = nullptr;
-    int32_t *dl = nullptr;
-    if (MODE == UP_CATCH && n_seeds) {
-      dc = ws.buf<uint32_t>("host.seed_cells", n_seeds);
-      dl = ws.buf<int32_t>("host.seed_labels", n_seeds);
-      RD_HIP(hipMemcpy(dc, cells, (size_t)n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice));
-      RD_HIP(hipMemcpy(dl, labels, (size_t)n_seeds * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
+    const bool seeds = MODE == UP_CATCH && n_seeds;
+    const uint32_t *dc = st.in("host.seed_cells", seeds ? cells : nullptr, n_seeds);
+    const int32_t *dl = st.in("host.seed_labels", seeds ? labels : nullptr, n_seeds);
     upslope_device<MODE>(dd, nodata, w, h, dc, dl, n_seeds, none, dout, nullptr, true, who);
   }
-  RD_HIP(hipStreamSynchronize(nullptr));
-  RD_HIP(hipMemcpy(out, dout, n * sizeof(O), hipMemcpyDeviceToHost));
+  st.finish();
 }
 
 }  // namespace rdgpu

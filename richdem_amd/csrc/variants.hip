@@ -95,11 +95,10 @@ template <class T, class F>
 void with_upload(T *dem, int w, int h, bool copy_back, const char *who, F &&fn) {
   check_raster(dem, w, h, who);
   const size_t n = (size_t)w * h;
-  T *d = Workspace::get().buf<T>("variants.dem", n);
-  RD_HIP(hipMemcpy(d, dem, n * sizeof(T), hipMemcpyHostToDevice));
+  HostStage st;
+  T *d = copy_back ? st.inout("variants.dem", dem, n) : const_cast<T *>(st.in("variants.dem", dem, n));
   fn(d);
-  RD_HIP(hipStreamSynchronize(nullptr));
-  if (copy_back) RD_HIP(hipMemcpy(dem, d, n * sizeof(T), hipMemcpyDeviceToHost));
+  st.finish();
 }
 }  // namespace
 

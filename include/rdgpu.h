@@ -1181,8 +1181,8 @@ int rdgpu_d8_total_upstream_length_dev(const uint8_t *d_dirs, uint8_t dir_nodata
                                        double length_nodata, void *hip_stream);
 
 /* ---- depression inventory: labels and one record per depression of the fill --------------------
- * No reference counterpart (the flat inventory of the lakes FillDepressions produces; the depression hierarchy is not
- * built).  Let W = FillDepressions<topology>(dem) exactly as rdgpu_fill_<T> computes it; NoData is an elevation like any
+ * No reference counterpart (the flat inventory of the lakes FillDepressions produces; the tree of the depressions
+ * inside them is rdgpu_depression_hierarchy_<T> below).  Let W = FillDepressions<topology>(dem) exactly as rdgpu_fill_<T> computes it; NoData is an elevation like any
  * other, as in that entry.  A cell is RAISED iff W > dem.  A DEPRESSION is a connected component of the raised cells
  * under `topology` (8 or 4, the one used for the fill).  Adjacent raised cells share one W: the depression's level.
  *   labels  int32 per cell (nullable): 0 on un-raised cells, 1..N on depressions, numbered by ascending lowest raster
@@ -1226,6 +1226,87 @@ RDGPU_DECL_DEPR(f64, double)
 RDGPU_DECL_DEPR(i64, int64_t)   /* RDGPU_ERR_UNSUPPORTED */
 RDGPU_DECL_DEPR(u64, uint64_t)  /* RDGPU_ERR_UNSUPPORTED */
 #undef RDGPU_DECL_DEPR
+
+/* ---- depression hierarchy: the merge tree of the depressions, leaf labels, levels and volumes ----
+ * Reference: depressions/depression_hierarchy.hpp (GetDepressionHierarchy with its marginal and total volumes), for a
+ * DEM whose border ring is the ocean.  The reference's tree depends on its pop order wherever two elevations are equal
+ * or two outlets share a saddle cell; this contract does not.
+ *
+ * DEFINITIONS.  Let < on cells be the strict total order by (dem value, raster index y * width + x).  NoData is an
+ * elevation like any other, as in rdgpu_fill_<T>.  topology is 8 or 4.
+ *   Descent.  Every interior cell points at its lowest neighbour if that neighbour is lower than itself, otherwise it
+ *     is a PIT.  Cells of the border ring drain OUTSIDE.  leaf(c) is the pit the descent path of c ends in, or outside
+ *     if the path reaches the border ring.
+ *   Edges.  For adjacent cells a, b with leaf(a) != leaf(b) (outside counts as a leaf here): hi is the greater of the
+ *     two cells and lo the lesser under <; the edge key is (dem[hi], hi index, lo index), compared lexicographically;
+ *     the edge between two leaves is the minimum key over all their adjacent cell pairs.  The order is total, so
+ *     nothing below depends on an execution order.
+ *   Tree.  Kruskal over the edges in ascending key, with outside as a node.  An edge whose two ends are in the same set
+ *     is skipped.  If one end's set contains outside, the other set's top node becomes a ROOT: parent = NONE, and the
+ *     set joins outside.  Otherwise the two top nodes A, B get a new parent node N.  The node that is merged or made a
+ *     root takes the edge's spill fields: level = dem[hi], inside_cell (the edge cell that lies in the node) and
+ *     outside_cell (the other one).  lchild is the child with the lower pit_cell under <, and N.pit_cell =
+ *     lchild.pit_cell.
+ *   Numbering.  Leaves are 0..P-1 by ascending pit raster index; internal nodes are P..count-1 in creation order, that
+ *     is ascending edge key, so child id < parent id.  NONE is 0xFFFFFFFF.
+ *   Reductions.  cells(n) = #{c : leaf(c) below n, dem[c] <= level(n)}, and volume(n) is the sum of (level(n) - dem[c])
+ *     over those cells.  Equivalently a cell is charged to its first ancestor-or-self with level >= dem[c] and the
+ *     totals add up the tree: the reference's CalculateMarginalVolumes / CalculateTotalVolumes, including its <=.
+ *     Integer element types sum in 64-bit integers and convert once.  f32 sums in double in no fixed order:
+ *     |volume - exact| <= cells * 2^-52 * exact; every other field is exact and reproducible.
+ *
+ * ENTRIES.  labels (int32 per cell, nullable): the leaf id of leaf(c), -1 where that is outside.  table (nullable):
+ * record i is node i; at most `capacity` records are written, the first ones.  count: the number of nodes, always the
+ * true value; table == NULL with capacity == 0 is the sizing call.  leaves (nullable): P.  A raster without pits gives
+ * count 0, leaves 0 and all labels -1.  Element types u8, i8, i16, u16, i32, u32, f32; the f64, i64 and u64 entries
+ * exist and return RDGPU_ERR_UNSUPPORTED.  Argument checks are those of rdgpu_depressions_<T>: a null dem or count, a
+ * non-positive size, a topology other than 8 or 4, a null table with a non-zero capacity or more than 2^31-65536 cells
+ * is RDGPU_ERR_ARG before any device work, and nothing is written then.  The input is never written.  The _dev forms
+ * take device pointers (d_count, d_leaves one device word each) and are ordered on hip_stream, which they wait for
+ * several times: the tree is built on the host (rdgpu_dephier_stats.builder).  Scratch comes from the workspace pool
+ * under names starting with "dephier.". */
+typedef struct rdgpu_dephier_node {         /* 56 bytes: eight 32-bit words, three doubles */
+  uint32_t parent, lchild, rchild;      /* NONE: root / leaf */
+  uint32_t pit_cell;
+  uint32_t inside_cell, outside_cell;   /* the spill pair; level = max of their dem values */
+  uint32_t geolink;                     /* leaf id of leaf(outside_cell), NONE when that is outside */
+  uint32_t cells;
+  double level, pit_elevation, volume;
+} rdgpu_dephier_node;
+#define RDGPU_DEPHIER_NONE 0xFFFFFFFFu
+#define RDGPU_DECL_DEPHIER(SUF, T)                                                                                     \
+  int rdgpu_depression_hierarchy_##SUF(const T *dem, int width, int height, int topology, int32_t *labels /* nullable */, \
+                                       rdgpu_dephier_node *table /* nullable */, uint32_t capacity, uint32_t *count,  \
+                                       uint32_t *leaves /* nullable */);                                              \
+  int rdgpu_depression_hierarchy_dev_##SUF(const T *d_dem, int width, int height, int topology,                       \
+                                           int32_t *d_labels /* nullable */, rdgpu_dephier_node *d_table /* nullable */, \
+                                           uint32_t capacity, uint32_t *d_count, uint32_t *d_leaves /* nullable */,   \
+                                           void *hip_stream);
+RDGPU_DECL_DEPHIER(u8, uint8_t)
+RDGPU_DECL_DEPHIER(i8, int8_t)
+RDGPU_DECL_DEPHIER(i16, int16_t)
+RDGPU_DECL_DEPHIER(u16, uint16_t)
+RDGPU_DECL_DEPHIER(i32, int32_t)
+RDGPU_DECL_DEPHIER(u32, uint32_t)
+RDGPU_DECL_DEPHIER(f32, float)
+RDGPU_DECL_DEPHIER(f64, double)    /* RDGPU_ERR_UNSUPPORTED */
+RDGPU_DECL_DEPHIER(i64, int64_t)   /* RDGPU_ERR_UNSUPPORTED */
+RDGPU_DECL_DEPHIER(u64, uint64_t)  /* RDGPU_ERR_UNSUPPORTED */
+#undef RDGPU_DECL_DEPHIER
+/* of the calling thread's last hierarchy call (zero pits: only pits and jump_rounds are set) */
+#define RDGPU_DEPHIER_BUILDER_HOST_KRUSKAL 1u   /* serial Kruskal on the host over the sorted edge records */
+typedef struct rdgpu_dephier_stats {
+  uint64_t cell_pairs;       /* (higher cell, lower neighbour) pairs across two leaves */
+  uint64_t edges_raw;        /* edge records emitted and sorted: one per higher cell and neighbouring leaf */
+  uint64_t edges_reduced;    /* after the reduction to the minimum edge per pair of leaves: what the builder reads */
+  uint32_t pits, nodes, roots;
+  uint32_t builder;          /* RDGPU_DEPHIER_BUILDER_* */
+  uint32_t builder_rounds;   /* passes of the builder over the records (1 for the serial one) */
+  uint32_t jump_rounds;      /* pointer-jumping launches of the descent */
+  uint32_t height;           /* edges on the longest leaf-to-root path */
+  uint32_t lift_planes;      /* planes of the lifting table the charging pass walks */
+} rdgpu_dephier_stats;
+int rdgpu_dephier_get_stats(rdgpu_dephier_stats *out);
 
 /* ---- flow distance and drop (HAND) DOWN to the stop cells over D-infinity / MFD proportions ----
  * No reference counterpart (TauDEM's DinfDistDown is the product meant).  Proportions are the reference's nine floats

@@ -1251,4 +1251,41 @@ void Depressions(const A &dem, L &labels, std::vector<rdgpu_depression> &table) 
   if (got != n) throw std::runtime_error("Depressions: the count changed between the sizing call and the full call");
 }
 
+// ---- depression hierarchy (richdem::dephier::GetDepressionHierarchy with the border ring as the ocean; the contract,
+// which fixes every tie, is in rdgpu.h) -----------------------------------------------------------------------------
+namespace detail {
+#define RDGPU_SHIM_DEPHIER(SUF, T)                                                                                   \
+  inline int c_dephier(const T *z, int w, int h, int t, int32_t *l, rdgpu_dephier_node *tab, uint32_t cap, uint32_t *n, \
+                       uint32_t *leaves) {                                                                            \
+    return rdgpu_depression_hierarchy_##SUF(z, w, h, t, l, tab, cap, n, leaves);                                      \
+  }
+RDGPU_SHIM_DEPHIER(u8, uint8_t) RDGPU_SHIM_DEPHIER(i8, int8_t) RDGPU_SHIM_DEPHIER(u16, uint16_t) RDGPU_SHIM_DEPHIER(i16, int16_t)
+RDGPU_SHIM_DEPHIER(u32, uint32_t) RDGPU_SHIM_DEPHIER(i32, int32_t) RDGPU_SHIM_DEPHIER(f32, float)
+RDGPU_SHIM_DEPHIER(f64, double) RDGPU_SHIM_DEPHIER(i64, int64_t) RDGPU_SHIM_DEPHIER(u64, uint64_t)   // (these three are refused by the engine)
+#undef RDGPU_SHIM_DEPHIER
+}  // namespace detail
+
+// The merge tree of the depressions of dem: node i of the returned vector is record i (leaves first, by ascending pit index;
+// RDGPU_DEPHIER_NONE marks a root's parent and a leaf's children).  labels <- the leaf a cell descends to, -1 where it
+// drains off the raster; it takes the DEM's size, geotransform and projection, NoData -1.  topology is 8 or 4.  NoData of
+// the DEM is an elevation like any other.  Two calls of the engine: the sizing call, then the full one.
+template <class A, class L>
+std::vector<rdgpu_dephier_node> DepressionHierarchy(const A &dem, int topology, L &labels) {
+  using T = detail::elem_t<const A>;
+  static_assert(std::is_same<detail::elem_t<L>, int32_t>::value, "DepressionHierarchy: the label raster must be int32_t");
+  labels.resize(dem, -1);
+  labels.setNoData(-1);
+  std::vector<rdgpu_dephier_node> table;
+  if (dem.width() == 0 || dem.height() == 0) return table;
+  uint32_t n = 0, leaves = 0;
+  detail::check(detail::c_dephier((const T *)dem.data(), dem.width(), dem.height(), topology, nullptr, nullptr, 0, &n, &leaves),
+                "DepressionHierarchy");
+  table.resize(n);
+  uint32_t got = 0;
+  detail::check(detail::c_dephier((const T *)dem.data(), dem.width(), dem.height(), topology, labels.data(),
+                                  n ? table.data() : nullptr, n, &got, &leaves), "DepressionHierarchy");
+  if (got != n) throw std::runtime_error("DepressionHierarchy: the count changed between the sizing call and the full call");
+  return table;
+}
+
 }  // namespace rdgpu

@@ -1433,6 +1433,105 @@ def depressions_dev(dem, labels, table, topology="D8"):
     return count
 
 
+# ---- depression hierarchy: merge tree, leaf labels, levels and volumes (csrc/dephier.hip) ------------------------
+DEPHIER_NONE = 0xFFFFFFFF
+DEPHIER_NODE_DTYPE = np.dtype([("parent", np.uint32), ("lchild", np.uint32), ("rchild", np.uint32), ("pit_cell", np.uint32),
+                               ("inside_cell", np.uint32), ("outside_cell", np.uint32), ("geolink", np.uint32),
+                               ("cells", np.uint32), ("level", np.float64), ("pit_elevation", np.float64),
+                               ("volume", np.float64)])   # rdgpu_dephier_node
+
+
+class _DephierStats(ctypes.Structure):   # rdgpu_dephier_stats
+    _fields_ = [("cell_pairs", ctypes.c_uint64), ("edges_raw", ctypes.c_uint64), ("edges_reduced", ctypes.c_uint64),
+                ("pits", ctypes.c_uint32),
+                ("nodes", ctypes.c_uint32), ("roots", ctypes.c_uint32), ("builder", ctypes.c_uint32),
+                ("builder_rounds", ctypes.c_uint32), ("jump_rounds", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("lift_planes", ctypes.c_uint32)]
+
+
+DEPHIER_BUILDERS = {1: "host_kruskal"}
+
+
+def dephier_stats() -> dict:
+    """``rdgpu_dephier_get_stats``: the counts of the calling thread's last hierarchy call; ``builder`` by name."""
+    st = _DephierStats()
+    check(lib().rdgpu_dephier_get_stats(ctypes.byref(st)), "rdgpu_dephier_get_stats")
+    out = {k: int(getattr(st, k)) for k, _ in _DephierStats._fields_}
+    out["builder"] = DEPHIER_BUILDERS.get(out["builder"], "none")
+    return out
+
+
+def depression_hierarchy_into(dem: np.ndarray, labels: np.ndarray | None, table: np.ndarray | None, topology=8):
+    """One call of ``rdgpu_depression_hierarchy_<T>``: ``labels`` (int32, the DEM's shape) and the first ``len(table)``
+    records of ``table`` (``DEPHIER_NODE_DTYPE``) are written where given; returns ``(nodes, leaves)``."""
+    if not isinstance(dem, np.ndarray) or dem.ndim != 2:
+        raise RdgpuError("depression_hierarchy: expected a 2-D numpy array")
+    dem = np.ascontiguousarray(dem)
+    s = _suffix(dem.dtype)
+    h, w = dem.shape
+    if labels is not None and not (isinstance(labels, np.ndarray) and labels.dtype == np.int32 and labels.shape == (h, w)
+                                   and labels.flags["C_CONTIGUOUS"]):
+        raise RdgpuError("depression_hierarchy: labels must be a C-contiguous int32 array of the DEM's shape")
+    if table is not None and not (isinstance(table, np.ndarray) and table.dtype == DEPHIER_NODE_DTYPE and table.ndim == 1
+                                  and table.flags["C_CONTIGUOUS"]):
+        raise RdgpuError("depression_hierarchy: table must be a C-contiguous 1-D array of DEPHIER_NODE_DTYPE")
+    count, leaves = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    check(getattr(lib(), f"rdgpu_depression_hierarchy_{s}")(
+        dem.ctypes.data_as(ctypes.c_void_p), w, h, _topo(topology),
+        None if labels is None else labels.ctypes.data_as(ctypes.c_void_p),
+        None if table is None or len(table) == 0 else table.ctypes.data_as(ctypes.c_void_p),
+        ctypes.c_uint32(0 if table is None else len(table)), ctypes.byref(count), ctypes.byref(leaves)),
+        "rdgpu_depression_hierarchy")
+    return int(count.value), int(leaves.value)
+
+
+def depression_hierarchy(dem: np.ndarray, topology=8, labels: bool = True):
+    """The depression hierarchy of ``dem`` (reference: ``GetDepressionHierarchy`` with the border ring as the ocean; the
+    contract, which fixes every tie, is in ``include/rdgpu.h``): ``(labels, table)``.  ``labels`` (int32; ``None`` when not
+    asked for) is the leaf depression a cell descends to, -1 where it drains off the raster.  ``table``
+    (``DEPHIER_NODE_DTYPE``): the binary merge tree, leaves first (by ascending pit index), then the merged depressions in
+    the order they form; parent / children (``DEPHIER_NONE``: root / leaf), pit cell, the spill pair, ``geolink``, and the
+    cells, level and volume of the node filled to its spill level.  Two calls: the sizing call, then the one that fills
+    the table."""
+    n, _ = depression_hierarchy_into(dem, None, None, topology)
+    lab = np.empty(dem.shape, np.int32) if labels else None
+    table = np.zeros(n, DEPHIER_NODE_DTYPE)
+    got, _ = depression_hierarchy_into(dem, lab, table, topology)
+    if got != n:
+        raise RdgpuError(f"depression_hierarchy: the count changed between the two calls ({n} -> {got})")
+    return lab, table
+
+
+def depression_hierarchy_dev(dem, labels, table, topology=8):
+    """The same on HBM-resident tensors, on torch's current stream: ``labels`` an int32 CUDA tensor of the DEM's shape or
+    ``None``; ``table`` a contiguous CUDA tensor of any element type holding 56 bytes per record (its capacity is its size
+    in bytes // 56; ``.cpu().numpy().view(DEPHIER_NODE_DTYPE)`` reads it) or ``None``.  Returns a two-element int32 CUDA
+    tensor: the number of nodes and of leaves."""
+    import torch
+
+    h, w = _dev2d(dem, "depression_hierarchy_dev")
+    m = {torch.int8: "i8", torch.uint8: "u8", torch.int16: "i16", torch.int32: "i32", torch.float32: "f32", torch.float64: "f64",
+         torch.int64: "i64"}
+    for name, s in (("uint16", "u16"), ("uint32", "u32"), ("uint64", "u64")):
+        if hasattr(torch, name):
+            m[getattr(torch, name)] = s
+    if dem.dtype not in m:
+        raise RdgpuError(f"depression_hierarchy_dev: unsupported elevation dtype {dem.dtype}")
+    if labels is not None and tuple(_dev2d(labels, "depression_hierarchy_dev", torch.int32)) != (h, w):
+        raise RdgpuError("depression_hierarchy_dev: shape mismatch")
+    cap = 0
+    if table is not None:
+        if not (table.is_cuda and table.is_contiguous()):
+            raise RdgpuError("depression_hierarchy_dev: expected a contiguous table tensor on the GPU")
+        cap = table.numel() * table.element_size() // DEPHIER_NODE_DTYPE.itemsize
+    counts = torch.zeros(2, dtype=torch.int32, device=dem.device)
+    check(getattr(lib(), f"rdgpu_depression_hierarchy_dev_{m[dem.dtype]}")(
+        ctypes.c_void_p(dem.data_ptr()), w, h, _topo(topology), None if labels is None else ctypes.c_void_p(labels.data_ptr()),
+        None if cap == 0 else ctypes.c_void_p(table.data_ptr()), ctypes.c_uint32(cap), ctypes.c_void_p(counts.data_ptr()),
+        ctypes.c_void_p(counts.data_ptr() + 4), _stream_ptr()), "rdgpu_depression_hierarchy_dev")
+    return counts
+
+
 # ---- upslope extremes (csrc/extreme.hip) -------------------------------------------------------
 _EXTREME_WANT = ("extreme", "at_cell")
 _EXTREME_SUFFIX = {k: v for k, v in _SUFFIX.items() if v not in ("f64", "i64", "u64")}

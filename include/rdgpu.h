@@ -1308,6 +1308,88 @@ typedef struct rdgpu_dephier_stats {
 } rdgpu_dephier_stats;
 int rdgpu_dephier_get_stats(rdgpu_dephier_stats *out);
 
+/* ---- fill-spill-merge: route surface water through the depression hierarchy ----
+ * Reference: depressions/fill_spill_merge.hpp (FillSpillMerge) with surface water only, for a DEM whose border ring is
+ * the ocean.  The reference floods every lake from its pit with a priority queue; this contract states the same result
+ * without an order of visits, and the two agree on every cell of tie-free inputs (tests/golden/make_golden_fsm.py).
+ *
+ * INPUTS.  dem, width, height; labels and table[count]: what rdgpu_depression_hierarchy_<T> gave for this DEM (either
+ * topology: nothing below looks at a neighbour); water: one double per cell, finite and >= 0.  Groundwater (a negative
+ * value) is out of scope: a negative or non-finite value is RDGPU_ERR_UNSUPPORTED, found by the first pass, before any
+ * output is written.  P, the number of leaves, is the number of records without children; they are records 0..P-1.
+ *   1. GATHER.  leaf_water(l) = the sum of water[c] over the cells with labels[c] == l; the water of the cells labelled
+ *      -1 goes to `ocean`.  Sums in double in no fixed order: |sum - exact| <= cells * 2^-52 * sum.
+ *   2. POUR (serial, on the host, over the node table alone).  w(n), one double per node, starts at 0; n is FULL when
+ *      w(n) >= volume(n).  For the leaves l = 0..P-1 in ascending id with leaf_water(l) > 0, pour(leaf_water(l), l):
+ *        pour(x, n): loop
+ *          if w(n) < volume(n): cap = volume(n) - w(n)
+ *              if x < cap: w(n) += x; return
+ *              w(n) = volume(n); x -= cap
+ *          if x <= 0: return
+ *          p = parent(n)
+ *          if p == NONE: if geolink(n) == NONE: ocean += x; return
+ *                        n = geolink(n); continue             (a root: over its spill into the tree beyond, or lost)
+ *          s = the other child of p
+ *          if s is FULL: if w(p) == 0: w(p) = min(volume(p), volume(lchild(p)) + volume(rchild(p)))
+ *                        n = p                                (the two lakes have merged)
+ *          else: n = geolink(n)                               (a leaf below s: the spill pair's far side)
+ *      w of an internal node is the water of the merged lake, its children's included; it stays 0 until a pour climbs
+ *      into the node.  The engine skips runs of full nodes by path compression; the values are those of the loop above.
+ *   3. LAKES.  f is a LAKE TOP when w(f) > 0 and parent(f) is NONE or w(parent(f)) == 0.  top(n) is the highest
+ *      ancestor-or-self of n that is a lake top, or none; the cells of lake f are those with top(labels[c]) == f.
+ *      h(f) = level(f) if f is FULL.  Otherwise sort the lake's cells with dem < level(f) by (dem, raster index), with
+ *      1-based positions and prefix sums S_k of their elevations in double: h(f) = (w(f) + S_k) / k for the smallest k
+ *      with (w(f) + S_k) / k <= dem of cell k + 1, or k = the last position.
+ *   4. DEPTH.  depth[c] = h(f) - dem[c] where c belongs to lake f and dem[c] < h(f); 0 elsewhere, the border ring
+ *      included.
+ * OUTPUTS.  depth: one double per cell; it must not overlap water.  node_water (nullable): w, one double per node.
+ * result (nullable): water_in (all the water handed in), ocean (what left the raster), standing (the sum of depth), the
+ * number of lake tops and how many of them are full.  water_in = standing + ocean within cells * 2^-52 * water_in.
+ * With count == 0 depth is all zero and all the water goes to the ocean.
+ * ARGUMENTS.  Those of rdgpu_depression_hierarchy_<T>, and: a null labels, water or depth, a null table with count > 0,
+ * depth overlapping water, a label outside [-1, P) (found by the gather), a record whose children are not both below it
+ * or both NONE, whose parent does not list it as a child, or whose geolink is not a leaf (found by the host pass): all
+ * RDGPU_ERR_ARG, and nothing is written.  A table that passes these checks but does not belong to the DEM gives
+ * unspecified values, never an out-of-range access.  Element types u8, i8, i16, u16, i32, u32, f32; the f64, i64 and u64
+ * entries exist and return RDGPU_ERR_UNSUPPORTED.  Inputs are never written.  The _dev forms take device pointers
+ * (d_result: one device struct) and are ordered on hip_stream, which they wait for several times: the pour runs on the
+ * host over 24 bytes per node.  Scratch comes from the workspace pool under names starting with "fsm.". */
+typedef struct rdgpu_fsm_result {           /* 32 bytes */
+  double water_in, ocean, standing;
+  uint32_t lakes, full_lakes;
+} rdgpu_fsm_result;
+#define RDGPU_DECL_FSM(SUF, T)                                                                                         \
+  int rdgpu_fill_spill_merge_##SUF(const T *dem, int width, int height, const int32_t *labels,                        \
+                                   const rdgpu_dephier_node *table, uint32_t count, const double *water, double *depth, \
+                                   double *node_water /* nullable */, rdgpu_fsm_result *result /* nullable */);       \
+  int rdgpu_fill_spill_merge_dev_##SUF(const T *d_dem, int width, int height, const int32_t *d_labels,                \
+                                       const rdgpu_dephier_node *d_table, uint32_t count, const double *d_water,      \
+                                       double *d_depth, double *d_node_water /* nullable */,                          \
+                                       rdgpu_fsm_result *d_result /* nullable */, void *hip_stream);
+RDGPU_DECL_FSM(u8, uint8_t)
+RDGPU_DECL_FSM(i8, int8_t)
+RDGPU_DECL_FSM(i16, int16_t)
+RDGPU_DECL_FSM(u16, uint16_t)
+RDGPU_DECL_FSM(i32, int32_t)
+RDGPU_DECL_FSM(u32, uint32_t)
+RDGPU_DECL_FSM(f32, float)
+RDGPU_DECL_FSM(f64, double)    /* RDGPU_ERR_UNSUPPORTED */
+RDGPU_DECL_FSM(i64, int64_t)   /* RDGPU_ERR_UNSUPPORTED */
+RDGPU_DECL_FSM(u64, uint64_t)  /* RDGPU_ERR_UNSUPPORTED */
+#undef RDGPU_DECL_FSM
+/* of the calling thread's last fill-spill-merge call */
+typedef struct rdgpu_fsm_stats {            /* 48 bytes */
+  uint64_t records;          /* (lake, elevation) records sorted: the cells of the partial lakes below their spill level */
+  double host_ms;            /* the host pass: the two transfers, the checks, the pour, the lake tops */
+  uint32_t nodes, leaves;
+  uint32_t lakes, partial_lakes;
+  uint32_t pours;            /* leaves with water */
+  uint32_t longest_pour;     /* node-to-node hops of the longest pour, a shortcut counting as one */
+  uint32_t shortcut_hits;    /* hops taken over the path-compression table */
+  uint32_t sort_bits;        /* key bits the radix sort ran over */
+} rdgpu_fsm_stats;
+int rdgpu_fsm_get_stats(rdgpu_fsm_stats *out);
+
 /* ---- flow distance and drop (HAND) DOWN to the stop cells over D-infinity / MFD proportions ----
  * No reference counterpart (TauDEM's DinfDistDown is the product meant).  Proportions are the reference's nine floats
  * per cell, [height][width][9]: slot 0 is -2 for NoData, slots 1..8 the shares to the neighbours 1 left, 2 up-left,

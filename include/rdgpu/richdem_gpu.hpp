@@ -1288,4 +1288,39 @@ std::vector<rdgpu_dephier_node> DepressionHierarchy(const A &dem, int topology, 
   return table;
 }
 
+// ---- fill-spill-merge (richdem::FillSpillMerge with surface water only; the contract is in rdgpu.h) ------------------
+namespace detail {
+#define RDGPU_SHIM_FSM(SUF, T)                                                                                       \
+  inline int c_fsm(const T *z, int w, int h, const int32_t *l, const rdgpu_dephier_node *tab, uint32_t n, const double *water, \
+                   double *depth, double *node_water, rdgpu_fsm_result *res) {                                        \
+    return rdgpu_fill_spill_merge_##SUF(z, w, h, l, tab, n, water, depth, node_water, res);                           \
+  }
+RDGPU_SHIM_FSM(u8, uint8_t) RDGPU_SHIM_FSM(i8, int8_t) RDGPU_SHIM_FSM(u16, uint16_t) RDGPU_SHIM_FSM(i16, int16_t)
+RDGPU_SHIM_FSM(u32, uint32_t) RDGPU_SHIM_FSM(i32, int32_t) RDGPU_SHIM_FSM(f32, float)
+RDGPU_SHIM_FSM(f64, double) RDGPU_SHIM_FSM(i64, int64_t) RDGPU_SHIM_FSM(u64, uint64_t)   // (these three are refused by the engine)
+#undef RDGPU_SHIM_FSM
+}  // namespace detail
+
+// Routes the water of wtd (one double per cell, finite and >= 0: surface water only) through the hierarchy that
+// DepressionHierarchy(dem, topology, labels) returned and rewrites wtd in place, as the reference does: the depth of the
+// standing water per cell, 0 where none stands.  One hierarchy serves any number of calls.  node_water, where given,
+// takes the water of every node of the table.
+template <class A, class L, class W>
+rdgpu_fsm_result FillSpillMerge(const A &dem, const L &labels, const std::vector<rdgpu_dephier_node> &table, W &wtd,
+                                std::vector<double> *node_water = nullptr) {
+  using T = detail::elem_t<const A>;
+  static_assert(std::is_same<detail::elem_t<const L>, int32_t>::value, "FillSpillMerge: the label raster must be int32_t");
+  static_assert(std::is_same<detail::elem_t<W>, double>::value, "FillSpillMerge: the water raster must be double");
+  rdgpu_fsm_result res = {};
+  if (dem.width() == 0 || dem.height() == 0) return res;
+  if (labels.width() != dem.width() || labels.height() != dem.height() || wtd.width() != dem.width() || wtd.height() != dem.height())
+    throw std::runtime_error("FillSpillMerge: the label and water rasters must have the DEM's size");
+  const std::vector<double> water(wtd.data(), wtd.data() + (size_t)dem.width() * dem.height());   // (depth must not overlap water)
+  if (node_water) node_water->assign(table.size(), 0.0);
+  detail::check(detail::c_fsm((const T *)dem.data(), dem.width(), dem.height(), (const int32_t *)labels.data(),
+                              table.empty() ? nullptr : table.data(), (uint32_t)table.size(), water.data(), wtd.data(),
+                              node_water && !table.empty() ? node_water->data() : nullptr, &res), "FillSpillMerge");
+  return res;
+}
+
 }  // namespace rdgpu

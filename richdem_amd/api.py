@@ -1532,6 +1532,101 @@ def depression_hierarchy_dev(dem, labels, table, topology=8):
     return counts
 
 
+# ---- fill-spill-merge: water routed through the depression hierarchy (csrc/fsm.hip) ------------------------------
+class _FsmResult(ctypes.Structure):   # rdgpu_fsm_result
+    _fields_ = [("water_in", ctypes.c_double), ("ocean", ctypes.c_double), ("standing", ctypes.c_double),
+                ("lakes", ctypes.c_uint32), ("full_lakes", ctypes.c_uint32)]
+
+
+class _FsmStats(ctypes.Structure):   # rdgpu_fsm_stats
+    _fields_ = [("records", ctypes.c_uint64), ("host_ms", ctypes.c_double), ("nodes", ctypes.c_uint32),
+                ("leaves", ctypes.c_uint32), ("lakes", ctypes.c_uint32), ("partial_lakes", ctypes.c_uint32),
+                ("pours", ctypes.c_uint32), ("longest_pour", ctypes.c_uint32), ("shortcut_hits", ctypes.c_uint32),
+                ("sort_bits", ctypes.c_uint32)]
+
+
+FSM_RESULT_DTYPE = np.dtype([("water_in", np.float64), ("ocean", np.float64), ("standing", np.float64),
+                             ("lakes", np.uint32), ("full_lakes", np.uint32)])   # rdgpu_fsm_result
+
+
+def fsm_stats() -> dict:
+    """``rdgpu_fsm_get_stats``: the counts of the calling thread's last fill-spill-merge call."""
+    st = _FsmStats()
+    check(lib().rdgpu_fsm_get_stats(ctypes.byref(st)), "rdgpu_fsm_get_stats")
+    return {k: (float if k == "host_ms" else int)(getattr(st, k)) for k, _ in _FsmStats._fields_}
+
+
+def fill_spill_merge(dem: np.ndarray, labels: np.ndarray, table: np.ndarray, water: np.ndarray, node_water: bool = True):
+    """Fill-Spill-Merge (reference: ``FillSpillMerge`` with surface water only; the contract is in ``include/rdgpu.h``):
+    ``water`` (float64 per cell, finite and >= 0) runs down into the leaf depressions of ``depression_hierarchy(dem)``,
+    fills them, spills over their saddles and merges; what leaves the raster goes to the ocean.  ``labels`` and ``table``
+    are that call's outputs, so one hierarchy serves any number of water scenarios.  Returns ``(depth, result)``:
+    ``depth`` (float64, the DEM's shape) is the standing water per cell, ``result`` a dict with ``water_in``, ``ocean``,
+    ``standing``, ``lakes``, ``full_lakes`` and, when asked for, ``node_water`` (float64 per node of ``table``)."""
+    if not isinstance(dem, np.ndarray) or dem.ndim != 2:
+        raise RdgpuError("fill_spill_merge: expected a 2-D numpy array")
+    dem = np.ascontiguousarray(dem)
+    s = _suffix(dem.dtype)
+    h, w = dem.shape
+    if not (isinstance(labels, np.ndarray) and labels.dtype == np.int32 and labels.shape == (h, w)):
+        raise RdgpuError("fill_spill_merge: labels must be an int32 array of the DEM's shape")
+    if not (isinstance(table, np.ndarray) and table.dtype == DEPHIER_NODE_DTYPE and table.ndim == 1):
+        raise RdgpuError("fill_spill_merge: table must be a 1-D array of DEPHIER_NODE_DTYPE")
+    if not (isinstance(water, np.ndarray) and water.shape == (h, w)):
+        raise RdgpuError("fill_spill_merge: water must be an array of the DEM's shape")
+    labels, table = np.ascontiguousarray(labels), np.ascontiguousarray(table)
+    water = np.ascontiguousarray(water, dtype=np.float64)
+    depth = np.empty((h, w), np.float64)
+    nw = np.zeros(len(table), np.float64) if node_water else None
+    res = _FsmResult()
+    check(getattr(lib(), f"rdgpu_fill_spill_merge_{s}")(
+        dem.ctypes.data_as(ctypes.c_void_p), w, h, labels.ctypes.data_as(ctypes.c_void_p),
+        table.ctypes.data_as(ctypes.c_void_p) if len(table) else None, ctypes.c_uint32(len(table)),
+        water.ctypes.data_as(ctypes.c_void_p), depth.ctypes.data_as(ctypes.c_void_p),
+        nw.ctypes.data_as(ctypes.c_void_p) if nw is not None and len(nw) else None, ctypes.byref(res)),
+        "rdgpu_fill_spill_merge")
+    out = {k: getattr(res, k) for k, _ in _FsmResult._fields_}
+    if node_water:
+        out["node_water"] = nw
+    return depth, out
+
+
+def fill_spill_merge_dev(dem, labels, table, count: int, water, depth, node_water=None):
+    """The same on HBM-resident tensors, on torch's current stream: ``labels`` int32 and ``water`` / ``depth`` float64
+    CUDA tensors of the DEM's shape, ``table`` the contiguous CUDA tensor ``depression_hierarchy_dev`` filled (56 bytes per
+    record) holding ``count`` records, ``node_water`` a float64 CUDA tensor of ``count`` elements or ``None``.  ``depth``
+    (and ``node_water``) are written; returns a 32-byte uint8 CUDA tensor, ``.cpu().numpy().view(FSM_RESULT_DTYPE)[0]``."""
+    import torch
+
+    h, w = _dev2d(dem, "fill_spill_merge_dev")
+    m = {torch.int8: "i8", torch.uint8: "u8", torch.int16: "i16", torch.int32: "i32", torch.float32: "f32", torch.float64: "f64",
+         torch.int64: "i64"}
+    for name, s in (("uint16", "u16"), ("uint32", "u32"), ("uint64", "u64")):
+        if hasattr(torch, name):
+            m[getattr(torch, name)] = s
+    if dem.dtype not in m:
+        raise RdgpuError(f"fill_spill_merge_dev: unsupported elevation dtype {dem.dtype}")
+    if tuple(_dev2d(labels, "fill_spill_merge_dev", torch.int32)) != (h, w) or \
+            tuple(_dev2d(water, "fill_spill_merge_dev", torch.float64)) != (h, w) or \
+            tuple(_dev2d(depth, "fill_spill_merge_dev", torch.float64)) != (h, w):
+        raise RdgpuError("fill_spill_merge_dev: shape mismatch")
+    count = int(count)
+    if count:
+        if not (table is not None and table.is_cuda and table.is_contiguous()
+                and table.numel() * table.element_size() >= count * DEPHIER_NODE_DTYPE.itemsize):
+            raise RdgpuError("fill_spill_merge_dev: expected a contiguous table tensor on the GPU holding count records")
+    if node_water is not None and not (node_water.is_cuda and node_water.is_contiguous() and node_water.dtype == torch.float64
+                                       and node_water.numel() >= count):
+        raise RdgpuError("fill_spill_merge_dev: node_water must be a contiguous float64 CUDA tensor of count elements")
+    res = torch.zeros(FSM_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dem.device)
+    check(getattr(lib(), f"rdgpu_fill_spill_merge_dev_{m[dem.dtype]}")(
+        ctypes.c_void_p(dem.data_ptr()), w, h, ctypes.c_void_p(labels.data_ptr()),
+        ctypes.c_void_p(table.data_ptr()) if count else None, ctypes.c_uint32(count), ctypes.c_void_p(water.data_ptr()),
+        ctypes.c_void_p(depth.data_ptr()), None if node_water is None or not count else ctypes.c_void_p(node_water.data_ptr()),
+        ctypes.c_void_p(res.data_ptr()), _stream_ptr()), "rdgpu_fill_spill_merge_dev")
+    return res
+
+
 # ---- upslope extremes (csrc/extreme.hip) -------------------------------------------------------
 _EXTREME_WANT = ("extreme", "at_cell")
 _EXTREME_SUFFIX = {k: v for k, v in _SUFFIX.items() if v not in ("f64", "i64", "u64")}

@@ -289,7 +289,13 @@ RDGPU_DECL_WS(u64, uint64_t)
  *                              strictly above the tile's largest key -- a tile wholly under one lake -- is written at
  *                              that level without its elevations or labels being read)
  *   RDGPU_FILL_COUNT_FLOODED=1 the finalize counts the tiles it writes that way, one atomic add each, for
- *                              rdgpu_fill_flooded_tiles (default: no counter, no atomics) */
+ *                              rdgpu_fill_flooded_tiles (default: no counter, no atomics)
+ *   RDGPU_FILL_COARSE=0        no coarse flood; =1: at any raster size (default: from 262 144 descent tiles, 32 768^2 cells).
+ *                              The descent leaves the minima of the 16 x 16 blocks, their fill (a nested fill: two more
+ *                              stream synchronisations, host_syncs 4) is a lower bound of the filled surface, and a 64 x 64
+ *                              tile whose blocks all lie above the tile's largest cell is left out of the pair pass: a
+ *                              star and a ring of pair records stand in for it.  Needs RDGPU_FILL_FLOODED != 0.
+ *   RDGPU_FILL_COUNT_COARSE=1  counts the tiles left out, for rdgpu_fill_coarse_tiles (default: no counter) */
 /* Statistics of the last fill on this process (for DESIGN.md / bench.py reporting). */
 typedef struct rdgpu_fill_stats {
   uint64_t cells;       /* width*height                                   */
@@ -309,6 +315,11 @@ int rdgpu_fill_get_stats(rdgpu_fill_stats *out);
  * RDGPU_FILL_COUNT_FLOODED=1 (else 0, as after a fill with outlets, a shard or RDGPU_FILL_FLOODED=0).  The fill itself
  * does not wait for the count: this call synchronises with the fill's stream. */
 int rdgpu_fill_flooded_tiles(uint64_t *out);
+/* Tiles the coarse flood of the last plain fill of the calling thread left out of the pair pass.  Counted only under
+ * RDGPU_FILL_COUNT_COARSE=1 (else 0, as when no coarse flood ran).  Synchronises with the fill's stream. */
+int rdgpu_fill_coarse_tiles(uint64_t *out);
+/* Edge of the coarse flood's blocks, in cells (16). */
+int rdgpu_fill_coarse_block(void);
 
 /* ---- row-block shards: the tile protocol of programs/parallel_priority_flood over GPUs ---------
  * Mirrors the reference's tiled Priority-Flood (Barnes 2016; programs/parallel_priority_flood/main.cpp:

@@ -89,6 +89,19 @@ def fill_flooded_tiles() -> int:
     return int(n.value)
 
 
+def fill_coarse_tiles() -> int:
+    """64 x 64 tiles the coarse flood of the last plain fill left out of the pair pass; counted only under
+    RDGPU_FILL_COUNT_COARSE=1 (else 0).  Waits for the fill's stream."""
+    n = ctypes.c_uint64(0)
+    check(lib().rdgpu_fill_coarse_tiles(ctypes.byref(n)), "rdgpu_fill_coarse_tiles")
+    return int(n.value)
+
+
+def fill_coarse_block() -> int:
+    """edge of the coarse flood's blocks, in cells"""
+    return int(lib().rdgpu_fill_coarse_block())
+
+
 def profile_enable(on: bool = True) -> None:
     lib().rdgpu_profile_enable(1 if on else 0)
 

@@ -100,6 +100,28 @@ int unlocked(F &&fn) {
 }
 
 // ------------------------------------------------------------------------------------------
+// A driver that runs inside another one of the same kind (the fill's coarse fill, csrc/fill.hip) must not share the outer
+// call's named buffers or its profile entries: while a NameScope lives, Workspace::buf and Profiler::begin of this thread
+// put its prefix before every name ("coarse." + "fused.lab16").  Scopes do not nest.
+// ------------------------------------------------------------------------------------------
+class NameScope {
+public:
+  explicit NameScope(const char *prefix) : saved_(current()) { current() = prefix; }
+  ~NameScope() { current() = saved_; }
+  NameScope(const NameScope &) = delete;
+  NameScope &operator=(const NameScope &) = delete;
+  static std::string apply(const char *name) { return current() ? std::string(current()) + name : std::string(name); }
+  static bool active() { return current() != nullptr; }
+
+private:
+  static const char *&current() {
+    static thread_local const char *p = nullptr;
+    return p;
+  }
+  const char *saved_;
+};
+
+// ------------------------------------------------------------------------------------------
 // grow-only device workspace, cached across calls (bench loops must not hipMalloc per step)
 // ------------------------------------------------------------------------------------------
 class Workspace {

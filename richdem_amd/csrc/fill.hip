@@ -2088,6 +2088,17 @@ __global__ __launch_bounds__(64) void k_stripe_offsets(const unsigned long long 
 
 // maximum / minimum over the 64 lanes, in every lane: a DPP prefix scan (row shifts, then row broadcasts) whose last lane
 // holds the result -- six VALU instructions and a v_readlane
+// Edge of the blocks of the coarse flood: k_descent16 leaves the blocks' minima, their fill is a lower bound
+// of the filled surface (rdgpu_fill_coarse_block).
+constexpr int COARSE_CB = 16;
+// the minimum over each row of 16 lanes, in the row's last lane (the other lanes hold the minimum of the lanes up to them)
+__device__ __forceinline__ uint32_t row_min_u32(uint32_t v) {
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false));   // row_shr:1 (all ones: the identity)
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false));   // row_shr:2
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false));   // row_shr:4
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false));   // row_shr:8
+  return v;
+}
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
   v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false));   // row_shr:1 (0: the identity)
   v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false));   // row_shr:2
@@ -2106,19 +2117,23 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return ~wave_max_
 // included: they get no work -- label 0 everywhere (written once: skip == 1; 2: written before), node 0.
 // CUT: the raster is a row-block shard -- the cells of an open first / last row are frozen terminals (own roots, numbered
 // like pits, never draining), not border cells.
-template <class T, int TOPO, bool VEC, bool OUTLETS = false, bool CUT = false>
+template <class T, int TOPO, bool VEC, bool OUTLETS = false, bool CUT = false, bool COARSE = false>
 __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, FusedBuf fo, int w, int h,
                                                     uint32_t tilesX, uint32_t ntiles, const uint8_t *__restrict__ outlet = nullptr,
                                                     const uint8_t *__restrict__ skip = nullptr,
                                                     const uint32_t *__restrict__ tlist = nullptr, int open_top = 0,
                                                     int open_bottom = 0, int dissolve = 0,
-                                                    uint32_t *__restrict__ tile_max = nullptr) {
+                                                    uint32_t *__restrict__ tile_max = nullptr,
+                                                    uint32_t *__restrict__ coarse = nullptr, uint32_t cbx = 0, uint32_t cby = 0) {
   // tlist (optional, with OUTLETS): the tiles to work on, one block each (ntiles = the raster's tiles all the same)
   // dissolve (block-uniform; the plain fill only): a pit whose lowest neighbour q lies in the tile and does not drain
   // into it is no basin of its own -- it points at q, and its label carries q's direction for the finalize
   // tile_max (optional; the plain fill only): tile_max[t] = the largest key among the tile's cells, for the finalize's
   // flooded-tile test (k_finalize16).  0xFFFFFFFF for a tile that is not interior: it holds a border cell, which is never
   // raised, or cells outside the raster -- such a tile never passes the test.
+  // coarse (with COARSE; the plain fill only -- without it the kernel is the one it was): the cby x cbx raster of the minima of the CB x CB blocks anchored at (0, 0), as
+  // keys, over the blocks' cells inside the raster.  Every tile writes its blocks, the tiles on the raster's rim included: a
+  // wavefront owns CB rows and a DPP row is CB lanes, so a block is one row of lanes of one wavefront.
   constexpr bool DIS_OK = !OUTLETS && !CUT;
   const bool dis = DIS_OK && dissolve != 0;
   __shared__ uint32_t dcnt;
@@ -2226,6 +2241,7 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
   uint32_t codesLo = 0, codesHi = 0;
   uint32_t rootmask = 0, pitmask = 0, outmask = 0;
   uint32_t kmax = 0;   // the largest key of the thread's cells (interior tiles with tile_max: the keys are live only here)
+  uint32_t kmin = 0xFFFFFFFFu;   // the smallest (a cell outside the raster holds 0xFFFFFFFF in sk)
   {
     // packed word of a candidate: [15:0] byte delta + 134, [19:16] exit code, [26:24] column 0 / 1 / 2, [27] row above, [29] row below
     constexpr uint32_t WT0 = 0u | (1u << 16) | (1u << 24) | (1u << 27), WT1 = 2u | (2u << 16) | (1u << 25) | (1u << 27),
@@ -2260,6 +2276,7 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
       triple(ly + 2, ba, bb, bc, bm, bW);
       const uint32_t kc = mb;
       if (DIS_OK && INNER) kmax = max(kmax, kc);
+      if (DIS_OK && COARSE) kmin = min(kmin, kc);
       const bool midfirst = ma <= mc;
       const uint32_t mm = midfirst ? ma : mc;
       const uint32_t bk = min(min(tm, mm), bm);
@@ -2316,6 +2333,12 @@ __global__ __launch_bounds__(NTHR) void k_descent16(const T *__restrict__ z, Fus
   if (DIS_OK && tile_max) {   // (block-uniform) one reduction per wavefront; thread 0 stores the tile's word with its bases
     const uint32_t wm = wave_max_u32(kmax);
     if ((threadIdx.x & 63) == 0) wkmax[wave_s] = wm;
+  }
+  if (DIS_OK && COARSE) {   // the wavefront's four block minima: lane 15 of each row of lanes holds its row's
+    static_assert(COARSE_CB == RPT && COARSE_CB == 16 && DW % COARSE_CB == 0, "a block is a wavefront's rows by a DPP row's lanes");
+    const uint32_t bm = row_min_u32(kmin);
+    const uint32_t bx = (uint32_t)gx / COARSE_CB, by = (uint32_t)(y0 + ly0) / COARSE_CB;
+    if ((lx & (COARSE_CB - 1)) == COARSE_CB - 1 && bx < cbx && by < cby) coarse[(size_t)by * cbx + bx] = bm;
   }
   __syncthreads();
   auto code_of = [codesLo, codesHi](int j) -> int {   // row j's code (j varies per lane)
@@ -2842,6 +2865,14 @@ __device__ unsigned long long *g_probe_pairs_clock = nullptr;
 extern "C" int rdgpu_probe_pairs_clock(unsigned long long *d_clock) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_probe_pairs_clock), &d_clock, sizeof d_clock) == hipSuccess ? 0 : 1;
 }
+// tools/probes/coarse_flood.py: a device array of one byte per descent tile that the plain fill hands to the PAIR PASS ONLY
+// as its `skip` (nullptr: none).  The surface of such a fill is wrong; what the run is for is k_pairs16's traced time
+// without those tiles.
+static const uint8_t *g_probe_pairs_skip = nullptr;
+extern "C" int rdgpu_probe_pairs_skip(const uint8_t *d_skip) {
+  g_probe_pairs_skip = d_skip;
+  return 0;
+}
 #endif
 
 // The kernel is held to 96 SGPRs (it takes all 102 when let, and spills to VGPR lanes either way; no scratch): a CU admits
@@ -3224,12 +3255,226 @@ __global__ __launch_bounds__(NTHR) __attribute__((amdgpu_num_sgpr(96))) void k_p
 #endif
 }
 
+// ==========================================================================================================
+// The coarse flood (r13): tiles the pair pass need not visit.
+//
+// lb = the fill of the raster of block minima that k_descent16 left (COARSE_CB x COARSE_CB blocks): a lower bound of the
+// filled surface, since a path of cells to the border maps to a path of blocks whose maximum is not larger.  An interior
+// descent tile whose blocks all have lb above the tile's largest key is strictly raised everywhere, hence (r11) wholly under
+// one lake at some level L above that key: FLAGGED.  k_pairs16 takes flag[] as its `skip`.
+// ==========================================================================================================
+__global__ __launch_bounds__(NTHR) void k_flag_tiles(const uint32_t *__restrict__ tile_max, const uint32_t *__restrict__ lb,
+                                                     uint32_t dtx, uint32_t dnt, uint32_t cbx, uint8_t *__restrict__ flag,
+                                                     unsigned long long *count) {
+  const uint32_t t = blockIdx.x * NTHR + threadIdx.x;
+  if (t >= dnt) return;
+  const uint32_t km = tile_max[t];
+  bool f = false;
+  if (km != 0xFFFFFFFFu) {   // interior: its DW / COARSE_CB blocks a side all lie in the coarse raster
+    constexpr uint32_t BPT = DW / COARSE_CB;
+    const uint32_t bx0 = (t % dtx) * BPT, by0 = (t / dtx) * BPT;
+    uint32_t m = 0xFFFFFFFFu;
+#pragma unroll
+    for (uint32_t j = 0; j < BPT; j++)
+#pragma unroll
+      for (uint32_t i = 0; i < BPT; i++) m = min(m, lb[(size_t)(by0 + j) * cbx + bx0 + i]);
+    f = m > km;
+  }
+  flag[t] = f ? 1 : 0;
+  // (RDGPU_FILL_COUNT_COARSE=1 only.  A list of the flagged tiles for k_pairs_flooded, appended to with one atomic add per
+  // wavefront, cost this kernel 70 us on its one counter and saved the other nothing: its time is not in the idle wavefronts.)
+  if (count && f) atomicAdd(count, 1ull);
+}
+
+// What stands in for a flagged tile's pair pass.  Every pair the tile's own scan would find joins two basins that end at
+// the tile's level L, below L; such an edge never decides a level (after the last of them a path to the outside goes on from
+// a basin of level L, with a maximum >= L), so they may be replaced by anything below L that keeps those basins connected.
+// With R the first basin of the tile's node table and K = tile_max[t] < L:
+//   star  (R, p, K) for every other basin p of the node table;
+//   ring  (R, basin(b), max(K, key(b))) for every cell b outside the tile that its forward scan meets (D8: the column to
+//         the right, the row below with both corners, the left column from the second row; D4: right column and row below):
+//         the true weight where key(b) >= L, and an edge below L between two basins of level L where not.
+// One record per distinct basin (a table per wavefront in LDS; what finds no slot goes out on its own).  Nothing of the
+// tile's own cells is read.  One wavefront per tile and one trip: every load that needs only the tile's index goes out
+// first, the gathers from the node table second -- the kernel is three round trips to HBM long and lives on the number
+// of wavefronts in flight (a persistent version, 512 blocks walking the tiles, took 1.1 ms at S3: 190 trips of dependent
+// round trips each).  The records go to the segments [seg0, seg0 + nfseg) of the pair list, behind the pair pass's; a
+// segment is shared by the blocks with blockIdx.x % nfseg in common, through its fill count in HBM (one atomic add per
+// tile; zeroed with the pair pass's counts before the launch).
+constexpr int FT_SLOTS = 256, FT_PROBES = 16;
+template <class T, int TOPO>
+__global__ __launch_bounds__(NTHR) void k_pairs_flooded(const T *__restrict__ z, const uint16_t *__restrict__ lab16,
+                                                        const uint32_t *__restrict__ curN, unsigned long long *best, int w,
+                                                        uint32_t dtx, uint32_t dnt, const uint8_t *__restrict__ flag,
+                                                        const uint32_t *__restrict__ tile_max,
+                                                        const uint32_t *__restrict__ tile_base,
+                                                        const uint32_t *__restrict__ tile_count,
+                                                        const uint32_t *__restrict__ edgeK, const uint16_t *__restrict__ edgeS,
+                                                        EdgeOut eo, uint32_t seg0, uint32_t nfseg) {
+  constexpr int NW = NTHR / 64;
+  __shared__ uint32_t tb_id[NW][FT_SLOTS], tb_key[NW][FT_SLOTS];
+  const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+  uint32_t *const ids = tb_id[wave], *const keys = tb_key[wave];
+  const uint32_t seg = seg0 + blockIdx.x % nfseg;
+  const uint32_t t = blockIdx.x * NW + (uint32_t)wave;
+  const bool on = t < dnt && flag[t] != 0;   // (wavefront-uniform)
+  if (on)
+    for (int i = lane; i < FT_SLOTS; i += 64) { ids[i] = 0xFFFFFFFFu; keys[i] = 0xFFFFFFFFu; }
+  // n records of the calling lanes (n: the wavefront's total, has: this lane has one) into the segment
+  auto emit = [&](bool has, uint32_t p, uint32_t key, uint32_t R) {
+    const unsigned long long bal = __ballot(has);
+    if (bal == 0ull) return;
+    const uint32_t n = (uint32_t)__popcll(bal);
+    uint32_t g0 = 0;
+    if (lane == __ffsll((long long)bal) - 1) {
+      g0 = atomicAdd(&eo.segcount[seg], n);
+      if (g0 + n > eo.seglimit) {   // (the count goes back: what reads the list afterwards never sees more than was written)
+        atomicSub(&eo.segcount[seg], n);
+        *eo.overflow = 1;
+        g0 = 0xFFFFFFFFu;
+      }
+    }
+    g0 = __shfl(g0, __ffsll((long long)bal) - 1, 64);
+    if (!has) return;
+    const uint32_t lo = min(R, p), hi = max(R, p);
+    const unsigned long long cl = ((unsigned long long)key << 32) | hi, ch = ((unsigned long long)key << 32) | lo;
+    if (!(lo & CLOSED) && cl < best[lo]) atomicMin(&best[lo], cl);
+    if (!(hi & CLOSED) && ch < best[hi]) atomicMin(&best[hi], ch);
+    if (g0 != 0xFFFFFFFFu) {
+      const size_t i = (size_t)seg * eo.segcap + g0 + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+      eo.a[i] = lo; eo.b[i] = hi; eo.k[i] = key;
+    }
+  };
+  uint32_t R = 0, K = 0;
+  // what a lane brings to the table: up to two nodes of the star (more: the loop below) and three ring cells
+  uint32_t sp[2] = {0, 0}, rp[3] = {0, 0, 0}, rk[3] = {0, 0, 0};
+  bool sh[2] = {false, false}, rh[3] = {false, false, false};
+  uint32_t base = 0, cnt = 0, pB = 0, kB = 0;
+  if (on) {
+    base = tile_base[t]; cnt = tile_count[t]; K = tile_max[t];
+    const int x0 = (int)(t % dtx) * DW, y0 = (int)(t / dtx) * DH;   // (an interior tile: its ring lies in the raster)
+    // first trip: indices, slots and keys
+    const size_t eR = ((size_t)(t + 1) * 2 + 0) * DH + lane;        // the right neighbour's first column
+    const size_t eL = ((size_t)(t - 1) * 2 + 1) * DH + lane;        // the left neighbour's last column
+    const uint32_t tbR = tile_base[t + 1], sR = edgeS[eR];
+    rk[0] = edgeK[eR];
+    uint32_t tbL = 0, sL = 0;
+    rh[0] = true;
+    rh[1] = TOPO == 8 && lane >= 1;
+    if (rh[1]) { tbL = tile_base[t - 1]; sL = edgeS[eL]; rk[1] = edgeK[eL]; }
+    // the row below: columns x0 ... x0 + 63, and with D8 the two corners from lanes 0 (x0 - 1) and 1 (x0 + 64)
+    const int gy = y0 + DH;
+    const size_t gB = (size_t)gy * w + x0 + lane;
+    const uint32_t tB = (uint32_t)(gy / DH) * dtx + (uint32_t)(x0 / DW);
+    const uint32_t tbB = tile_base[tB], sB = (uint32_t)lab16[gB] & LAB16_SLOT;
+    const T zB = z[gB];
+    rh[2] = TOPO == 8 && lane < 2;
+    uint32_t tbC = 0, sC = 0;
+    T zC = T();
+    if (rh[2]) {
+      const size_t gC = (size_t)gy * w + (lane ? x0 + DW : x0 - 1);
+      tbC = tile_base[lane ? tB + 1 : tB - 1];
+      sC = (uint32_t)lab16[gC] & LAB16_SLOT;
+      zC = z[gC];
+    }
+    // second trip: the basins
+    sh[0] = (uint32_t)lane < cnt;
+    sh[1] = (uint32_t)lane + 64u < cnt;
+    if (sh[0]) sp[0] = curN[base + lane];
+    if (sh[1]) sp[1] = curN[base + 64 + lane];
+    rp[0] = curN[tbR + sR];
+    if (rh[1]) rp[1] = curN[tbL + sL];
+    pB = curN[tbB + sB];
+    if (rh[2]) { rp[2] = curN[tbC + sC]; rk[2] = key32_fast<T>(zC); }
+    R = __shfl(sp[0], 0, 64);   // (cnt >= 1: the tile holds a cell)
+    // the row below goes in with the ring cells: lane's own cell first
+    rk[0] = max(K, rk[0]); rk[1] = max(K, rk[1]); rk[2] = max(K, rk[2]);
+    kB = max(K, key32_fast<T>(zB));
+  }
+  __syncthreads();   // (the tables are clear)
+  if (on) {
+    auto put = [&](bool has, uint32_t p, uint32_t key) {   // (R, p, key) into the wavefront's table: the lowest key per basin p
+      bool placed = !has || p == R;
+      if (!placed) {
+        uint32_t sl = (p * 0x9E3779B1u) >> 24;
+        static_assert(FT_SLOTS == 256, "the hash's eight bits");
+        for (int k = 0; k < FT_PROBES && !placed; k++, sl = (sl + 1) & (FT_SLOTS - 1)) {
+          const uint32_t old = atomicCAS(&ids[sl], 0xFFFFFFFFu, p);
+          if (old == 0xFFFFFFFFu || old == p) { atomicMin(&keys[sl], key); placed = true; }
+        }
+      }
+      emit(!placed, p, key, R);   // (no slot within reach: the record goes out on its own; the wavefront calls together)
+    };
+    put(sh[0], sp[0], K);
+    put(sh[1], sp[1], K);
+    for (uint32_t i0 = 128; i0 < cnt; i0 += 64) {   // (wavefront-uniform; a tile of the bench DEM has ~80 nodes)
+      const bool has = i0 + (uint32_t)lane < cnt;
+      put(has, has ? curN[base + i0 + lane] : 0u, K);
+    }
+    put(true, pB, kB);
+#pragma unroll
+    for (int e = 0; e < 3; e++) put(rh[e], rp[e], rk[e]);
+  }
+  __syncthreads();   // (the wavefront's table is complete)
+  if (on) {   // the table's records: one allocation in the segment, one proposal for R, one per other end
+    constexpr int SPL = FT_SLOTS / 64;
+    uint32_t p[SPL], k[SPL], n = 0, before[SPL];
+    unsigned long long mine = ~0ull;   // R's best candidate among this lane's records
+#pragma unroll
+    for (int e = 0; e < SPL; e++) {
+      p[e] = ids[lane + 64 * e];
+      k[e] = keys[lane + 64 * e];
+      const unsigned long long bal = __ballot(p[e] != 0xFFFFFFFFu);
+      before[e] = n + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+      n += (uint32_t)__popcll(bal);
+      if (p[e] != 0xFFFFFFFFu) mine = min(mine, ((unsigned long long)k[e] << 32) | p[e]);
+    }
+    if (n) {   // (wavefront-uniform)
+      uint32_t g0 = 0;
+      if (lane == 0) {
+        g0 = atomicAdd(&eo.segcount[seg], n);
+        if (g0 + n > eo.seglimit) {
+          atomicSub(&eo.segcount[seg], n);
+          *eo.overflow = 1;
+          g0 = 0xFFFFFFFFu;
+        }
+      }
+      g0 = __shfl(g0, 0, 64);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) mine = min(mine, (unsigned long long)__shfl_xor((long long)mine, o, 64));
+      if (lane == 0 && mine < best[R]) atomicMin(&best[R], mine);   // (R is open: a basin of raised cells)
+#pragma unroll
+      for (int e = 0; e < SPL; e++) {
+        if (p[e] == 0xFFFFFFFFu) continue;
+        const uint32_t lo = min(R, p[e]), hi = max(R, p[e]);
+        const unsigned long long c = ((unsigned long long)k[e] << 32) | R;
+        if (!(p[e] & CLOSED) && c < best[p[e]]) atomicMin(&best[p[e]], c);
+        if (g0 != 0xFFFFFFFFu) {
+          const size_t i = (size_t)seg * eo.segcap + g0 + before[e];
+          eo.a[i] = lo; eo.b[i] = hi; eo.k[i] = k[e];
+        }
+      }
+    }
+  }
+}
+
 // tiles the last plain fill of this thread wrote without reading them (RDGPU_FILL_COUNT_FLOODED=1; else 0): the finalize's
 // counter, copied to pinned memory behind the kernel and read once its stream got there
 static thread_local unsigned long long *g_fl_pinned = nullptr;
 static thread_local unsigned long long g_fl_count = 0;
 static thread_local bool g_fl_pending = false;
 static thread_local hipStream_t g_fl_stream = nullptr;
+// tiles the coarse flood flagged in the last plain fill of this thread (RDGPU_FILL_COUNT_COARSE=1; else 0): k_flag_tiles'
+// counter, brought home the same way
+static thread_local unsigned long long *g_co_pinned = nullptr;
+static thread_local unsigned long long g_co_count = 0;
+static thread_local bool g_co_pending = false;
+static thread_local hipStream_t g_co_stream = nullptr;
+static thread_local int g_coarse_depth = 0;   // inside the coarse fill of a fill: that one runs no coarse fill of its own
+// Descent tiles from which the coarse flood runs when RDGPU_FILL_COARSE is not set (=1: at any size, =0: never).  Below,
+// the coarse fill's two host round trips and 28 small launches cost more than the pair pass saves: forced on, G(3) of
+// 16384^2 (65 536 tiles) took 2.68 against 2.53 ms, of 32768^2 (262 144 tiles) 8.98 against 8.97.
+constexpr uint32_t COARSE_MIN_TILES = 262144;
 
 // f(std::true_type()) or f(std::false_type()): a runtime flag becomes a template argument of the launches in f
 template <class F>
@@ -3301,8 +3546,12 @@ template <class T, int TOPO>
 static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outlet = nullptr, const uint8_t *skip = nullptr,
                        const SparseLists *lists = nullptr, FillBuffers *keep = nullptr, BufAlloc *alloc = nullptr,
                        int open_top = 0, int open_bottom = 0) {
-  g_fl_pending = false;
-  g_fl_count = 0;
+  if (g_coarse_depth == 0) {
+    g_fl_pending = false;
+    g_fl_count = 0;
+    g_co_pending = false;
+    g_co_count = 0;
+  }
   const char *env_edges = getenv("RDGPU_FILL_EDGES");
   if (env_edges && env_edges[0] == '0') return false;   // (the raster-round fallback lives in the classic path)
   const uint64_t n64 = (uint64_t)w * (uint64_t)h;
@@ -3363,19 +3612,28 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   if (!outlet && !sharded && !(env_fl && env_fl[0] == '0')) tile_max = ws.buf<uint32_t>("fused.tile_max", dnt);
   // RDGPU_FILL_COUNT_FLOODED=1: the finalize counts those tiles (rdgpu_fill_flooded_tiles; else no atomics on the path)
   unsigned long long *flooded = nullptr;
-  if (!outlet && !sharded && env_flc && env_flc[0] == '1') {
+  if (!outlet && !sharded && env_flc && env_flc[0] == '1' && g_coarse_depth == 0) {
     flooded = ws.buf<unsigned long long>("fused.flooded", 1);
     RD_HIP(hipMemsetAsync(flooded, 0, sizeof(unsigned long long), s));
   }
+  // RDGPU_FILL_COARSE (the plain fill with tile_max only; =0 off, =1 on at any size, unset: from COARSE_MIN_TILES descent
+  // tiles): the descent leaves the minima of the COARSE_CB x COARSE_CB blocks, their fill flags the tiles the pair pass skips
+  const uint32_t cbx = cdiv(w, COARSE_CB), cby = cdiv(h, COARSE_CB);
+  const char *env_co = getenv("RDGPU_FILL_COARSE");
+  uint32_t *coarse = nullptr;
+  if (tile_max && g_coarse_depth == 0 && cbx > 2 && cby > 2 && !(env_co && env_co[0] == '0') &&
+      ((env_co && env_co[0] == '1') || dnt >= COARSE_MIN_TILES))
+    coarse = ws.buf<uint32_t>("fused.coarse", (size_t)cbx * cby);
   // (outlets never come with a cut; the kernel reads outlet, skip and dl only with OUTLETS, the cut rows only with CUT)
   with_flag(vec, [&](auto V) {
-    auto descent = [&](auto OUTLETS, auto CUT) {
-      RD_LAUNCH("fill.descent", (k_descent16<T, TOPO, V, OUTLETS, CUT>), dim3(listed ? lists->n[0] : xcd_grid(dnt)), dim3(NTHR), 0, s,
-                (const T *)d_z, fo, w, h, dtx, dnt, outlet, skip, dl, open_top, open_bottom, dissolve, tile_max);
+    auto descent = [&](auto OUTLETS, auto CUT, auto COARSE) {
+      RD_LAUNCH("fill.descent", (k_descent16<T, TOPO, V, OUTLETS, CUT, COARSE>), dim3(listed ? lists->n[0] : xcd_grid(dnt)), dim3(NTHR), 0, s,
+                (const T *)d_z, fo, w, h, dtx, dnt, outlet, skip, dl, open_top, open_bottom, dissolve, tile_max, coarse, cbx, cby);
     };
-    if (outlet) descent(std::true_type(), std::false_type());
-    else if (sharded) descent(std::false_type(), std::true_type());
-    else descent(std::false_type(), std::false_type());
+    if (outlet) descent(std::true_type(), std::false_type(), std::false_type());
+    else if (sharded) descent(std::false_type(), std::true_type(), std::false_type());
+    else if (coarse) descent(std::false_type(), std::false_type(), std::true_type());
+    else descent(std::false_type(), std::false_type(), std::false_type());
   });
   RD_LAUNCH("fill.stripe_offsets", k_stripe_offsets, dim3(1), dim3(64), 0, s, (const unsigned long long *)fo.counters, nstripes, pitoff,
             dflags + 8, dflags + 6);
@@ -3447,6 +3705,44 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   RD_HIP(hipMemsetAsync(dflags + 2, 0, sizeof(uint32_t), s));
   RD_LAUNCH("fill.init_tables", k_init_tables, dim3(cdiv((uint64_t)B + 1, NTHR)), dim3(NTHR), 0, s, cur, acc, link, rootsA,
             dflags + 2, (const uint32_t *)tid, B);
+  // ---- the coarse flood: the fill of the block minima, in place, by this very function (its buffers and profile entries
+  // under "coarse."; it reads the pinned words, whose values this call holds in locals by now).  k_resolve_nodes and
+  // k_init_tables are in the stream already and run during its host round trips.  Its synchronisations are this fill's.
+  uint8_t *tflag = nullptr;
+  if (coarse) {
+    const rdgpu_fill_stats outer = g_stats;
+    bool ok = false;
+    g_coarse_depth++;
+    try {
+      NameScope scope("coarse.");
+      ok = fill_fused<uint32_t, TOPO>(coarse, (int)cbx, (int)cby, s);
+    } catch (...) {
+      g_coarse_depth--;
+      g_stats = outer;
+      throw;
+    }
+    g_coarse_depth--;
+    const uint32_t syncs = g_stats.host_syncs;
+    g_stats = outer;
+    g_stats.host_syncs += syncs;
+    if (ok) {   // (else: the coarse raster does not fit the compact path -- nothing is flagged, the fill goes on as ever)
+      tflag = ws.buf<uint8_t>("fused.tile_flag", dnt);
+      const char *env_coc = getenv("RDGPU_FILL_COUNT_COARSE");
+      unsigned long long *ccount = nullptr;
+      if (env_coc && env_coc[0] == '1') {
+        ccount = ws.buf<unsigned long long>("fused.coarse_count", 1);
+        RD_HIP(hipMemsetAsync(ccount, 0, sizeof(unsigned long long), s));
+      }
+      RD_LAUNCH("fill.flag_tiles", k_flag_tiles, dim3(cdiv(dnt, NTHR)), dim3(NTHR), 0, s, (const uint32_t *)tile_max,
+                (const uint32_t *)coarse, dtx, dnt, cbx, tflag, ccount);
+      if (ccount) {
+        if (!g_co_pinned) RD_HIP(hipHostMalloc((void **)&g_co_pinned, sizeof(unsigned long long)));
+        RD_HIP(hipMemcpyAsync(g_co_pinned, ccount, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        g_co_pending = true;
+        g_co_stream = s;
+      }
+    }
+  }
   uint32_t nroots0 = B;
   if (sharded) {   // the frozen terminals are no roots: the list was compacted, its length comes back
     RD_HIP(hipMemcpyAsync(hw, dflags + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -3459,8 +3755,11 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
   int &pb = pb_cache[vec ? 1 : 0];
   if (!pb) pb = vec ? pairs_blocks(k_pairs16<T, TOPO, true>) : pairs_blocks(k_pairs16<T, TOPO, false>);
   const uint32_t pgrid = std::max(8u, std::min<uint32_t>(xcd_grid(std::max(nwork1, 1u)), (uint32_t)pb));
-  // the pair list of the one raster pass: capacity as in the classic path, one segment per block of the pair pass
-  const uint32_t nseg = pgrid;
+  // the pair list of the one raster pass: capacity as in the classic path, one segment per block of the pair pass, and
+  // behind them those of k_pairs_flooded (a flagged tile leaves ~40 records, three tiles in ten are flagged at S3: 512
+  // segments fill about as far as the pair pass's 1 792)
+  const uint32_t fseg = tflag ? std::max(1u, std::min(512u, cdiv(dnt, 64u))) : 0u;
+  const uint32_t nseg = pgrid + fseg;
   const char *env_cap = getenv("RDGPU_FILL_EDGE_CAP");
   const uint64_t cap = env_cap ? strtoull(env_cap, nullptr, 10) : std::min<uint64_t>(12ull * B, n / 2) + 2048;
   const uint32_t segcap = cdiv(cdiv(cap, nseg), NTHR * EPT) * (NTHR * EPT);
@@ -3525,12 +3824,21 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
     RD_LAUNCH("fill.best_reset", k_best_reset, dim3(rgrid), dim3(NTHR), 0, s, (const uint32_t *)rootsA, 0u, best, nr, gate);
     if (r == 1) {   // round 1: the one raster pass (components gathered from the node table)
       const uint32_t nwork = listed ? lists->n[1] : ntiles;
+      const uint8_t *pskip = tflag ? tflag : skip;   // (tflag: the plain fill, which has no skip of its own)
+#ifdef RDGPU_PROBES
+      if (!outlet && !sharded && g_probe_pairs_skip) pskip = g_probe_pairs_skip;
+#endif
       if (nwork > 0)   // (none although basins exist cannot happen -- a pit is a wet cell; kept safe)
         with_flag(vec, [&](auto V) {
           RD_LAUNCH("fill.scan", (k_pairs16<T, TOPO, V>), dim3(pgrid), dim3(NTHR), 0, s, (const T *)d_z, (const uint16_t *)fo.lab16,
                     (const uint32_t *)curN, best, w, h, B, tilesX, sl_, nwork, eo, (const uint32_t *)fo.tile_base,
-                    (const uint32_t *)fo.tile_count, dtx, skip, (const uint32_t *)fo.edgeK, (const uint16_t *)fo.edgeS);
+                    (const uint32_t *)fo.tile_count, dtx, pskip, (const uint32_t *)fo.edgeK, (const uint16_t *)fo.edgeS);
         });
+      if (tflag)
+        RD_LAUNCH("fill.pairs_flooded", (k_pairs_flooded<T, TOPO>), dim3(cdiv(dnt, NTHR / 64)), dim3(NTHR), 0, s, (const T *)d_z,
+                  (const uint16_t *)fo.lab16, (const uint32_t *)curN, best, w, dtx, dnt, (const uint8_t *)tflag,
+                  (const uint32_t *)tile_max, (const uint32_t *)fo.tile_base, (const uint32_t *)fo.tile_count,
+                  (const uint32_t *)fo.edgeK, (const uint16_t *)fo.edgeS, eo, pgrid, fseg);
       RD_LAUNCH("fill.sum_segments", k_sum_segments, dim3(1), dim3(NTHR), 0, s, (const uint32_t *)eo.segcount, nseg, rc + 4 * 1 + 1,
                 rc + 4 * 2 + 1);   // (and where round 2's gate reads it)
       g_stats.scan_tiles += ntiles;
@@ -4186,6 +4494,18 @@ extern "C" int rdgpu_fill_max_dep_get_stats(rdgpu_max_dep_stats *out) {
   return RDGPU_OK;
 }
 
+extern "C" int rdgpu_fill_coarse_block(void) { return rdgpu::COARSE_CB; }
+extern "C" int rdgpu_fill_coarse_tiles(uint64_t *out) {
+  using namespace rdgpu;
+  if (!out) return RDGPU_ERR_ARG;
+  if (g_co_pending) {
+    if (hipStreamSynchronize(g_co_stream) != hipSuccess) { set_last_error("rdgpu_fill_coarse_tiles: hipStreamSynchronize failed"); return RDGPU_ERR_HIP; }
+    g_co_count = *g_co_pinned;
+    g_co_pending = false;
+  }
+  *out = g_co_count;
+  return RDGPU_OK;
+}
 extern "C" int rdgpu_fill_flooded_tiles(uint64_t *out) {
   if (!out) return RDGPU_ERR_ARG;
   if (g_fl_pending) {

@@ -61,7 +61,7 @@ void *Workspace::buf(const char *name, size_t bytes) {
   Slot *sp;
   {
     std::lock_guard<std::mutex> g(mu_);
-    sp = &slots_[std::to_string(dev) + ":" + name];   // (map nodes are stable; a slot is only used under its device's API lock)
+    sp = &slots_[std::to_string(dev) + ":" + NameScope::apply(name)];   // (map nodes are stable; a slot is only used under its device's API lock)
   }
   Slot &s = *sp;
   if (bytes > s.cap) {
@@ -142,7 +142,7 @@ void Profiler::begin(const char *name, hipStream_t s) {
   RD_HIP(hipGetDevice(&dev));
   std::lock_guard<std::mutex> g(mu_);
   Pending p;
-  p.name = name;
+  p.name = NameScope::apply(name);
   p.device = dev;
   p.a = take(dev);
   p.b = take(dev);

@@ -1275,7 +1275,21 @@ RDGPU_DECL_DEPR(u64, uint64_t)  /* RDGPU_ERR_UNSUPPORTED */
  * is RDGPU_ERR_ARG before any device work, and nothing is written then.  The input is never written.  The _dev forms
  * take device pointers (d_count, d_leaves one device word each) and are ordered on hip_stream, which they wait for
  * several times: the tree is built on the host (rdgpu_dephier_stats.builder).  Scratch comes from the workspace pool
- * under names starting with "dephier.". */
+ * under names starting with "dephier.".
+ *
+ * A CALLER-GIVEN OCEAN.  rdgpu_depression_hierarchy_ocean_<T> takes the same arguments plus `ocean` after `topology`: one
+ * byte per cell, non-zero means ocean (the reference's label raster with OCEAN marked; rdgpu_bucket_fill_from_edges_<T>
+ * below builds such a mask).  ocean == NULL is the border ring: the entry above, bit for bit.  Otherwise the
+ * DEFINITIONS hold with these differences:
+ *   Ocean set.  O is the set of cells with a non-zero byte.  The border ring is NOT added to it: a caller who wants the
+ *     ring sets it in the mask.
+ *   Descent.  A cell of O drains OUTSIDE.  Every other cell, border cells included, points at its lowest neighbour inside
+ *     the raster under < if that neighbour is lower than itself, otherwise it is a PIT; a neighbour in O counts by its
+ *     value like any other.  leaf(c) is outside when the path reaches a cell of O.
+ *   Edges, keys, Kruskal with the outside as a node, numbering and reductions are unchanged: cells of O are labelled -1
+ *     and are charged to no node; an outside_cell may be an ocean cell, and then geolink is NONE.
+ * O empty is RDGPU_ERR_ARG ("no ocean cells"; the reference throws), found by the first pass, and nothing is written.
+ * All cells in O gives count 0, leaves 0 and all labels -1.  The mask is never written. */
 typedef struct rdgpu_dephier_node {         /* 56 bytes: eight 32-bit words, three doubles */
   uint32_t parent, lchild, rchild;      /* NONE: root / leaf */
   uint32_t pit_cell;
@@ -1292,7 +1306,16 @@ typedef struct rdgpu_dephier_node {         /* 56 bytes: eight 32-bit words, thr
   int rdgpu_depression_hierarchy_dev_##SUF(const T *d_dem, int width, int height, int topology,                       \
                                            int32_t *d_labels /* nullable */, rdgpu_dephier_node *d_table /* nullable */, \
                                            uint32_t capacity, uint32_t *d_count, uint32_t *d_leaves /* nullable */,   \
-                                           void *hip_stream);
+                                           void *hip_stream);                                                         \
+  int rdgpu_depression_hierarchy_ocean_##SUF(const T *dem, int width, int height, int topology,                       \
+                                             const uint8_t *ocean /* nullable: the border ring */,                    \
+                                             int32_t *labels /* nullable */, rdgpu_dephier_node *table /* nullable */, \
+                                             uint32_t capacity, uint32_t *count, uint32_t *leaves /* nullable */);    \
+  int rdgpu_depression_hierarchy_ocean_dev_##SUF(const T *d_dem, int width, int height, int topology,                 \
+                                                 const uint8_t *d_ocean /* nullable: the border ring */,              \
+                                                 int32_t *d_labels /* nullable */,                                    \
+                                                 rdgpu_dephier_node *d_table /* nullable */, uint32_t capacity,       \
+                                                 uint32_t *d_count, uint32_t *d_leaves /* nullable */, void *hip_stream);
 RDGPU_DECL_DEPHIER(u8, uint8_t)
 RDGPU_DECL_DEPHIER(i8, int8_t)
 RDGPU_DECL_DEPHIER(i16, int16_t)
@@ -1319,10 +1342,40 @@ typedef struct rdgpu_dephier_stats {
 } rdgpu_dephier_stats;
 int rdgpu_dephier_get_stats(rdgpu_dephier_stats *out);
 
+/* ---- bucket fill from the edges: paint a mask over the cells of one value that the border reaches ----
+ * Reference: misc/misc_methods.hpp (BucketFillFromEdges<topo>(check, set, check_value, set_value)), with
+ * `set == set_value` read as `mask != 0`.  ELIGIBLE = {c : check[c] == check_value under C++ ==, and mask[c] == 0 on
+ * entry}: NaN equals nothing, -0.0 equals 0.0.  mask[c] becomes 1 for every eligible cell connected under `topology`
+ * (8 or 4), through eligible cells, to an eligible cell of the border ring; every other byte is left as it was.  filled
+ * (nullable): the number of bytes set.  The result depends on no order of visits.  The cells are labelled by a union-find
+ * in four launches whatever the shape of the region; scratch (4 bytes per cell) comes from the workspace pool under names
+ * starting with "bucketfill.".  Every element type is supported (the operation is equality alone).  A null check or
+ * mask, a non-positive size, a topology other than 8 or 4 or more than 2^31-65536 cells is RDGPU_ERR_ARG before any
+ * device work, and nothing is written then.  check is never written.  The _dev form takes device pointers (d_filled one
+ * 64-bit device word) and is ordered on hip_stream without synchronising it. */
+#define RDGPU_DECL_BUCKET(SUF, T)                                                                                      \
+  int rdgpu_bucket_fill_from_edges_##SUF(const T *check, int width, int height, int topology, T check_value,          \
+                                         uint8_t *mask /* in/out */, uint64_t *filled /* nullable */);                \
+  int rdgpu_bucket_fill_from_edges_dev_##SUF(const T *d_check, int width, int height, int topology, T check_value,    \
+                                             uint8_t *d_mask /* in/out */, uint64_t *d_filled /* nullable */,         \
+                                             void *hip_stream);
+RDGPU_DECL_BUCKET(u8, uint8_t)
+RDGPU_DECL_BUCKET(i8, int8_t)
+RDGPU_DECL_BUCKET(i16, int16_t)
+RDGPU_DECL_BUCKET(u16, uint16_t)
+RDGPU_DECL_BUCKET(i32, int32_t)
+RDGPU_DECL_BUCKET(u32, uint32_t)
+RDGPU_DECL_BUCKET(f32, float)
+RDGPU_DECL_BUCKET(f64, double)
+RDGPU_DECL_BUCKET(i64, int64_t)
+RDGPU_DECL_BUCKET(u64, uint64_t)
+#undef RDGPU_DECL_BUCKET
+
 /* ---- fill-spill-merge: route surface water through the depression hierarchy ----
- * Reference: depressions/fill_spill_merge.hpp (FillSpillMerge) with surface water only, for a DEM whose border ring is
- * the ocean.  The reference floods every lake from its pit with a priority queue; this contract states the same result
- * without an order of visits, and the two agree on every cell of tie-free inputs (tests/golden/make_golden_fsm.py).
+ * Reference: depressions/fill_spill_merge.hpp (FillSpillMerge) with surface water only; the ocean is the ocean cells of
+ * the hierarchy call (the border ring, or the mask given to rdgpu_depression_hierarchy_ocean_<T>).  The reference floods
+ * every lake from its pit with a priority queue; this contract states the same result without an order of visits, and
+ * the two agree on every cell of tie-free inputs (tests/golden/make_golden_fsm.py).
  *
  * INPUTS.  dem, width, height; labels and table[count]: what rdgpu_depression_hierarchy_<T> gave for this DEM (either
  * topology: nothing below looks at a neighbour); water: one double per cell, finite and >= 0.  Groundwater (a negative
@@ -1351,8 +1404,8 @@ int rdgpu_dephier_get_stats(rdgpu_dephier_stats *out);
  *      h(f) = level(f) if f is FULL.  Otherwise sort the lake's cells with dem < level(f) by (dem, raster index), with
  *      1-based positions and prefix sums S_k of their elevations in double: h(f) = (w(f) + S_k) / k for the smallest k
  *      with (w(f) + S_k) / k <= dem of cell k + 1, or k = the last position.
- *   4. DEPTH.  depth[c] = h(f) - dem[c] where c belongs to lake f and dem[c] < h(f); 0 elsewhere, the border ring
- *      included.
+ *   4. DEPTH.  depth[c] = h(f) - dem[c] where c belongs to lake f and dem[c] < h(f); 0 elsewhere, the ocean cells of the
+ *      hierarchy call included.
  * OUTPUTS.  depth: one double per cell; it must not overlap water.  node_water (nullable): w, one double per node.
  * result (nullable): water_in (all the water handed in), ocean (what left the raster), standing (the sum of depth), the
  * number of lake tops and how many of them are full.  water_in = standing + ocean within cells * 2^-52 * water_in.

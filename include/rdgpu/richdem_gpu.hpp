@@ -1288,6 +1288,79 @@ std::vector<rdgpu_dephier_node> DepressionHierarchy(const A &dem, int topology, 
   return table;
 }
 
+// ---- the same with a caller-given ocean (the reference's label raster with any set of cells OCEAN) ------------------
+namespace detail {
+#define RDGPU_SHIM_DEPHIER_OCEAN(SUF, T)                                                                             \
+  inline int c_dephier_ocean(const T *z, int w, int h, int t, const uint8_t *o, int32_t *l, rdgpu_dephier_node *tab, \
+                             uint32_t cap, uint32_t *n, uint32_t *leaves) {                                          \
+    return rdgpu_depression_hierarchy_ocean_##SUF(z, w, h, t, o, l, tab, cap, n, leaves);                             \
+  }
+RDGPU_SHIM_DEPHIER_OCEAN(u8, uint8_t) RDGPU_SHIM_DEPHIER_OCEAN(i8, int8_t) RDGPU_SHIM_DEPHIER_OCEAN(u16, uint16_t)
+RDGPU_SHIM_DEPHIER_OCEAN(i16, int16_t) RDGPU_SHIM_DEPHIER_OCEAN(u32, uint32_t) RDGPU_SHIM_DEPHIER_OCEAN(i32, int32_t)
+RDGPU_SHIM_DEPHIER_OCEAN(f32, float)
+RDGPU_SHIM_DEPHIER_OCEAN(f64, double) RDGPU_SHIM_DEPHIER_OCEAN(i64, int64_t) RDGPU_SHIM_DEPHIER_OCEAN(u64, uint64_t)   // (refused by the engine)
+#undef RDGPU_SHIM_DEPHIER_OCEAN
+}  // namespace detail
+
+// ocean: one byte per cell of the DEM, non-zero means ocean.  The border ring is ocean only where the mask says so; a mask
+// without any ocean cell throws (as the reference does).  Labels are -1 on the ocean cells and on what drains into them.
+template <class A, class L, class O>
+std::vector<rdgpu_dephier_node> DepressionHierarchy(const A &dem, int topology, L &labels, const O &ocean) {
+  using T = detail::elem_t<const A>;
+  static_assert(std::is_same<detail::elem_t<L>, int32_t>::value, "DepressionHierarchy: the label raster must be int32_t");
+  static_assert(std::is_same<detail::elem_t<const O>, uint8_t>::value, "DepressionHierarchy: the ocean mask must be uint8_t");
+  if (ocean.width() != dem.width() || ocean.height() != dem.height())
+    throw std::runtime_error("DepressionHierarchy: the ocean mask must have the DEM's size");
+  labels.resize(dem, -1);
+  labels.setNoData(-1);
+  std::vector<rdgpu_dephier_node> table;
+  if (dem.width() == 0 || dem.height() == 0) return table;
+  uint32_t n = 0, leaves = 0;
+  detail::check(detail::c_dephier_ocean((const T *)dem.data(), dem.width(), dem.height(), topology, (const uint8_t *)ocean.data(),
+                                        nullptr, nullptr, 0, &n, &leaves), "DepressionHierarchy");
+  table.resize(n);
+  uint32_t got = 0;
+  detail::check(detail::c_dephier_ocean((const T *)dem.data(), dem.width(), dem.height(), topology, (const uint8_t *)ocean.data(),
+                                        labels.data(), n ? table.data() : nullptr, n, &got, &leaves), "DepressionHierarchy");
+  if (got != n) throw std::runtime_error("DepressionHierarchy: the count changed between the sizing call and the full call");
+  return table;
+}
+
+// ---- BucketFillFromEdges (misc/misc_methods.hpp:317), the reference's signature ---------------------------------------
+namespace detail {
+#define RDGPU_SHIM_BUCKET(SUF, T)                                                                                    \
+  inline int c_bucket(const T *c, int w, int h, int t, T v, uint8_t *m, uint64_t *filled) {                          \
+    return rdgpu_bucket_fill_from_edges_##SUF(c, w, h, t, v, m, filled);                                              \
+  }
+RDGPU_SHIM_BUCKET(u8, uint8_t) RDGPU_SHIM_BUCKET(i8, int8_t) RDGPU_SHIM_BUCKET(u16, uint16_t) RDGPU_SHIM_BUCKET(i16, int16_t)
+RDGPU_SHIM_BUCKET(u32, uint32_t) RDGPU_SHIM_BUCKET(i32, int32_t) RDGPU_SHIM_BUCKET(f32, float)
+RDGPU_SHIM_BUCKET(f64, double) RDGPU_SHIM_BUCKET(i64, int64_t) RDGPU_SHIM_BUCKET(u64, uint64_t)
+#undef RDGPU_SHIM_BUCKET
+}  // namespace detail
+
+// set_raster <- set_value on every cell with check_raster == check_value and set_raster != set_value that such cells
+// connect to one of them on the border ring (TOPO: 8 or 4).  A byte mask of `set_raster == set_value` goes to the engine;
+// set_value is written where the engine set a byte.  Returns the number of cells set.
+template <int TOPO, class A, class S>
+uint64_t BucketFillFromEdges(const A &check_raster, S &set_raster, const detail::elem_t<const A> &check_value,
+                             const detail::elem_t<S> &set_value) {
+  using T = detail::elem_t<const A>;
+  static_assert(TOPO == 8 || TOPO == 4, "BucketFillFromEdges: the topology is 8 or 4");
+  if (check_raster.width() != set_raster.width() || check_raster.height() != set_raster.height())
+    throw std::runtime_error("Rasters must have the same dimension for BucketFill!");   // (the reference's message)
+  const size_t n = (size_t)check_raster.width() * check_raster.height();
+  if (n == 0) return 0;
+  std::vector<uint8_t> mask(n);
+  for (size_t i = 0; i < n; i++) mask[i] = set_raster.data()[i] == set_value ? 1 : 0;
+  const std::vector<uint8_t> before(mask);
+  uint64_t filled = 0;
+  detail::check(detail::c_bucket((const T *)check_raster.data(), check_raster.width(), check_raster.height(), TOPO, check_value,
+                                 mask.data(), &filled), "BucketFillFromEdges");
+  for (size_t i = 0; i < n; i++)
+    if (mask[i] && !before[i]) set_raster.data()[i] = set_value;
+  return filled;
+}
+
 // ---- fill-spill-merge (richdem::FillSpillMerge with surface water only; the contract is in rdgpu.h) ------------------
 namespace detail {
 #define RDGPU_SHIM_FSM(SUF, T)                                                                                       \

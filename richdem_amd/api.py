@@ -1461,9 +1461,17 @@ def dephier_stats() -> dict:
     return out
 
 
-def depression_hierarchy_into(dem: np.ndarray, labels: np.ndarray | None, table: np.ndarray | None, topology=8):
-    """One call of ``rdgpu_depression_hierarchy_<T>``: ``labels`` (int32, the DEM's shape) and the first ``len(table)``
-    records of ``table`` (``DEPHIER_NODE_DTYPE``) are written where given; returns ``(nodes, leaves)``."""
+def _ocean_host(ocean, shape, who):
+    """The ocean mask as a C-contiguous uint8 array of the DEM's shape (bool is taken as it is; non-zero means ocean)."""
+    if not isinstance(ocean, np.ndarray) or ocean.shape != tuple(shape) or ocean.dtype not in (np.dtype(np.uint8), np.dtype(bool)):
+        raise RdgpuError(f"{who}: ocean must be a uint8 or bool array of the DEM's shape")
+    return np.ascontiguousarray(ocean).view(np.uint8)
+
+
+def depression_hierarchy_into(dem: np.ndarray, labels: np.ndarray | None, table: np.ndarray | None, topology=8, ocean=None):
+    """One call of ``rdgpu_depression_hierarchy_<T>`` (``rdgpu_depression_hierarchy_ocean_<T>`` when ``ocean``, a uint8 or
+    bool mask of the DEM's shape, is given): ``labels`` (int32, the DEM's shape) and the first ``len(table)`` records of
+    ``table`` (``DEPHIER_NODE_DTYPE``) are written where given; returns ``(nodes, leaves)``."""
     if not isinstance(dem, np.ndarray) or dem.ndim != 2:
         raise RdgpuError("depression_hierarchy: expected a 2-D numpy array")
     dem = np.ascontiguousarray(dem)
@@ -1476,37 +1484,45 @@ def depression_hierarchy_into(dem: np.ndarray, labels: np.ndarray | None, table:
                                   and table.flags["C_CONTIGUOUS"]):
         raise RdgpuError("depression_hierarchy: table must be a C-contiguous 1-D array of DEPHIER_NODE_DTYPE")
     count, leaves = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    check(getattr(lib(), f"rdgpu_depression_hierarchy_{s}")(
-        dem.ctypes.data_as(ctypes.c_void_p), w, h, _topo(topology),
-        None if labels is None else labels.ctypes.data_as(ctypes.c_void_p),
-        None if table is None or len(table) == 0 else table.ctypes.data_as(ctypes.c_void_p),
-        ctypes.c_uint32(0 if table is None else len(table)), ctypes.byref(count), ctypes.byref(leaves)),
-        "rdgpu_depression_hierarchy")
+    outs = (None if labels is None else labels.ctypes.data_as(ctypes.c_void_p),
+            None if table is None or len(table) == 0 else table.ctypes.data_as(ctypes.c_void_p),
+            ctypes.c_uint32(0 if table is None else len(table)), ctypes.byref(count), ctypes.byref(leaves))
+    if ocean is None:
+        check(getattr(lib(), f"rdgpu_depression_hierarchy_{s}")(
+            dem.ctypes.data_as(ctypes.c_void_p), w, h, _topo(topology), *outs), "rdgpu_depression_hierarchy")
+    else:
+        ocean = _ocean_host(ocean, (h, w), "depression_hierarchy")
+        check(getattr(lib(), f"rdgpu_depression_hierarchy_ocean_{s}")(
+            dem.ctypes.data_as(ctypes.c_void_p), w, h, _topo(topology), ocean.ctypes.data_as(ctypes.c_void_p), *outs),
+            "rdgpu_depression_hierarchy_ocean")
     return int(count.value), int(leaves.value)
 
 
-def depression_hierarchy(dem: np.ndarray, topology=8, labels: bool = True):
-    """The depression hierarchy of ``dem`` (reference: ``GetDepressionHierarchy`` with the border ring as the ocean; the
-    contract, which fixes every tie, is in ``include/rdgpu.h``): ``(labels, table)``.  ``labels`` (int32; ``None`` when not
-    asked for) is the leaf depression a cell descends to, -1 where it drains off the raster.  ``table``
+def depression_hierarchy(dem: np.ndarray, topology=8, labels: bool = True, ocean=None):
+    """The depression hierarchy of ``dem`` (reference: ``GetDepressionHierarchy``; the contract, which fixes every tie, is
+    in ``include/rdgpu.h``): ``(labels, table)``.  The ocean is the border ring, or, when ``ocean`` (a uint8 or bool mask
+    of the DEM's shape, see ``ocean_mask``) is given, exactly its non-zero cells: the ring is then land unless the mask
+    says otherwise, and a mask without any ocean cell is an error.  ``labels`` (int32; ``None`` when not
+    asked for) is the leaf depression a cell descends to, -1 where it drains into the ocean.  ``table``
     (``DEPHIER_NODE_DTYPE``): the binary merge tree, leaves first (by ascending pit index), then the merged depressions in
     the order they form; parent / children (``DEPHIER_NONE``: root / leaf), pit cell, the spill pair, ``geolink``, and the
     cells, level and volume of the node filled to its spill level.  Two calls: the sizing call, then the one that fills
     the table."""
-    n, _ = depression_hierarchy_into(dem, None, None, topology)
+    n, _ = depression_hierarchy_into(dem, None, None, topology, ocean)
     lab = np.empty(dem.shape, np.int32) if labels else None
     table = np.zeros(n, DEPHIER_NODE_DTYPE)
-    got, _ = depression_hierarchy_into(dem, lab, table, topology)
+    got, _ = depression_hierarchy_into(dem, lab, table, topology, ocean)
     if got != n:
         raise RdgpuError(f"depression_hierarchy: the count changed between the two calls ({n} -> {got})")
     return lab, table
 
 
-def depression_hierarchy_dev(dem, labels, table, topology=8):
+def depression_hierarchy_dev(dem, labels, table, topology=8, ocean=None):
     """The same on HBM-resident tensors, on torch's current stream: ``labels`` an int32 CUDA tensor of the DEM's shape or
     ``None``; ``table`` a contiguous CUDA tensor of any element type holding 56 bytes per record (its capacity is its size
-    in bytes // 56; ``.cpu().numpy().view(DEPHIER_NODE_DTYPE)`` reads it) or ``None``.  Returns a two-element int32 CUDA
-    tensor: the number of nodes and of leaves."""
+    in bytes // 56; ``.cpu().numpy().view(DEPHIER_NODE_DTYPE)`` reads it) or ``None``; ``ocean`` a uint8 or bool CUDA tensor
+    of the DEM's shape or ``None`` (the border ring).  Returns a two-element int32 CUDA tensor: the number of nodes and of
+    leaves."""
     import torch
 
     h, w = _dev2d(dem, "depression_hierarchy_dev")
@@ -1525,11 +1541,113 @@ def depression_hierarchy_dev(dem, labels, table, topology=8):
             raise RdgpuError("depression_hierarchy_dev: expected a contiguous table tensor on the GPU")
         cap = table.numel() * table.element_size() // DEPHIER_NODE_DTYPE.itemsize
     counts = torch.zeros(2, dtype=torch.int32, device=dem.device)
-    check(getattr(lib(), f"rdgpu_depression_hierarchy_dev_{m[dem.dtype]}")(
-        ctypes.c_void_p(dem.data_ptr()), w, h, _topo(topology), None if labels is None else ctypes.c_void_p(labels.data_ptr()),
-        None if cap == 0 else ctypes.c_void_p(table.data_ptr()), ctypes.c_uint32(cap), ctypes.c_void_p(counts.data_ptr()),
-        ctypes.c_void_p(counts.data_ptr() + 4), _stream_ptr()), "rdgpu_depression_hierarchy_dev")
+    outs = (None if labels is None else ctypes.c_void_p(labels.data_ptr()),
+            None if cap == 0 else ctypes.c_void_p(table.data_ptr()), ctypes.c_uint32(cap), ctypes.c_void_p(counts.data_ptr()),
+            ctypes.c_void_p(counts.data_ptr() + 4), _stream_ptr())
+    if ocean is None:
+        check(getattr(lib(), f"rdgpu_depression_hierarchy_dev_{m[dem.dtype]}")(
+            ctypes.c_void_p(dem.data_ptr()), w, h, _topo(topology), *outs), "rdgpu_depression_hierarchy_dev")
+    else:
+        if ocean.dtype not in (torch.uint8, torch.bool) or tuple(_dev2d(ocean, "depression_hierarchy_dev")) != (h, w):
+            raise RdgpuError("depression_hierarchy_dev: ocean must be a uint8 or bool CUDA tensor of the DEM's shape")
+        check(getattr(lib(), f"rdgpu_depression_hierarchy_ocean_dev_{m[dem.dtype]}")(
+            ctypes.c_void_p(dem.data_ptr()), w, h, _topo(topology), ctypes.c_void_p(ocean.data_ptr()), *outs),
+            "rdgpu_depression_hierarchy_ocean_dev")
     return counts
+
+
+# ---- bucket fill from the edges, and the ocean mask built with it (csrc/bucketfill.hip) ---------------------------
+_check_rc = check   # (the raster argument below is called `check`, as in the reference)
+
+
+def _check_scalar(s: str, value):
+    """ctypes scalar of the raster's element type for an equality test against `value`: floating types round it as a C
+    cast does; for an integer raster None when no element can equal it (NaN, a fraction, out of range)."""
+    if s in ("f32", "f64"):
+        return _CT[s](float(value))
+    if isinstance(value, (int, np.integer)) and not isinstance(value, (bool, np.bool_)):
+        v = int(value)                       # (exact: a 64-bit integer need not survive a trip through float)
+    else:
+        try:
+            f = float(value)
+            if not np.isfinite(f) or f != int(f):
+                return None
+            v = int(f)
+        except (TypeError, ValueError, OverflowError):
+            return None
+    info = np.iinfo(_NP[s])
+    return _CT[s](v) if info.min <= v <= info.max else None
+
+
+def bucket_fill_from_edges(check: np.ndarray, check_value, mask: np.ndarray | None = None, topology=8):
+    """``BucketFillFromEdges`` (reference: misc/misc_methods.hpp; the contract is in ``include/rdgpu.h``): the cells with
+    ``check == check_value`` and ``mask == 0`` that are connected, through such cells, to one of them on the border ring
+    get ``mask = 1``.  ``mask`` (uint8 or bool, the raster's shape; all zero when left out) is not modified: returns
+    ``(new mask as uint8, number of bytes set)``.  A ``check_value`` no element can equal sets nothing."""
+    if not isinstance(check, np.ndarray) or check.ndim != 2:
+        raise RdgpuError("bucket_fill_from_edges: expected a 2-D numpy array")
+    check_a = np.ascontiguousarray(check)
+    s = _suffix(check_a.dtype)
+    h, w = check_a.shape
+    out = np.zeros((h, w), np.uint8) if mask is None else _ocean_host(mask, (h, w), "bucket_fill_from_edges").copy()
+    topo = _topo(topology)
+    v = _check_scalar(s, check_value)
+    if v is None:
+        return out, 0
+    filled = ctypes.c_uint64(0)
+    _check_rc(getattr(lib(), f"rdgpu_bucket_fill_from_edges_{s}")(
+        check_a.ctypes.data_as(ctypes.c_void_p), w, h, topo, v, out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(filled)),
+        "rdgpu_bucket_fill_from_edges")
+    return out, int(filled.value)
+
+
+def bucket_fill_from_edges_dev(check, check_value, mask, topology=8):
+    """The same on HBM-resident tensors, on torch's current stream: ``mask`` (a uint8 or bool CUDA tensor of the raster's
+    shape) is updated in place.  Returns a one-element int64 CUDA tensor: the number of bytes set."""
+    import torch
+
+    h, w = _dev2d(check, "bucket_fill_from_edges_dev")
+    m = {torch.int8: "i8", torch.uint8: "u8", torch.int16: "i16", torch.int32: "i32", torch.float32: "f32", torch.float64: "f64",
+         torch.int64: "i64"}
+    for name, s in (("uint16", "u16"), ("uint32", "u32"), ("uint64", "u64")):
+        if hasattr(torch, name):
+            m[getattr(torch, name)] = s
+    if check.dtype not in m:
+        raise RdgpuError(f"bucket_fill_from_edges_dev: unsupported dtype {check.dtype}")
+    if mask.dtype not in (torch.uint8, torch.bool) or tuple(_dev2d(mask, "bucket_fill_from_edges_dev")) != (h, w):
+        raise RdgpuError("bucket_fill_from_edges_dev: mask must be a uint8 or bool CUDA tensor of the raster's shape")
+    topo = _topo(topology)
+    filled = torch.zeros(1, dtype=torch.int64, device=check.device)
+    v = _check_scalar(m[check.dtype], check_value)
+    if v is None:
+        return filled
+    _check_rc(getattr(lib(), f"rdgpu_bucket_fill_from_edges_dev_{m[check.dtype]}")(
+        ctypes.c_void_p(check.data_ptr()), w, h, topo, v, ctypes.c_void_p(mask.data_ptr()),
+        ctypes.c_void_p(filled.data_ptr()), _stream_ptr()), "rdgpu_bucket_fill_from_edges_dev")
+    return filled
+
+
+def ocean_mask(dem: np.ndarray, ocean_level=None, nodata=None, border: bool = False, topology=8) -> np.ndarray:
+    """An ocean mask for ``depression_hierarchy(..., ocean=)`` by the rule of the reference's Fill-Spill-Merge app: the
+    cells equal to ``nodata`` (when given), the cells at ``ocean_level`` (when given) that the border reaches through such
+    cells (``bucket_fill_from_edges``, which runs before the NoData cells are added, as in the app), and, with ``border``,
+    the border ring.  uint8, the DEM's shape."""
+    if not isinstance(dem, np.ndarray) or dem.ndim != 2:
+        raise RdgpuError("ocean_mask: expected a 2-D numpy array")
+    h, w = dem.shape
+    if ocean_level is not None:
+        mask, _ = bucket_fill_from_edges(dem, ocean_level, None, topology)
+    else:
+        _topo(topology)
+        mask = np.zeros((h, w), np.uint8)
+    if nodata is not None:
+        v = _check_scalar(_suffix(dem.dtype), nodata)
+        if v is not None:
+            mask[dem == dem.dtype.type(v.value)] = 1
+    if border:
+        mask[0, :] = mask[-1, :] = 1
+        mask[:, 0] = mask[:, -1] = 1
+    return mask
 
 
 # ---- fill-spill-merge: water routed through the depression hierarchy (csrc/fsm.hip) ------------------------------

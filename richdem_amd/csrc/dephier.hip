@@ -7,7 +7,8 @@
 // tiles finish them, keeps one id for the whole outside and, on its fused path, dissolves pits; the contract wants every
 // pit of the plain (value, index) descent and leaves numbered by raster index, so nothing of fb.lab could be kept.
 //   k_dh_descent   one raster pass: every interior cell -> its lowest (key, index) neighbour, itself (a pit), or OUTSIDE
-//                  on the border ring.
+//                  on the border ring.  k_dh_descent_ocean is its twin for a caller-given ocean mask: the cells of the mask
+//                  drain OUTSIDE, every other cell -- the ring's, with their partial neighbourhoods, included -- descends.
 //   k_dh_jump      pointer jumping, eight hops a round, until a round changes nothing.
 //   k_dh_flag + an exclusive scan + k_dh_leaf   the leaves, numbered by ascending pit index; ptr[] becomes leaf[] in place.
 //   k_dh_edges<0/1>  count, scan, emit: every cell, as the HIGHER cell of an edge, one record per neighbouring leaf (the
@@ -87,6 +88,37 @@ __global__ __launch_bounds__(NTHR) void k_dh_descent(const T *__restrict__ z, ui
     }
     ptr[c] = (uint32_t)best;
   }
+}
+
+// The descent for a caller-given ocean: a cell of the mask drains OUTSIDE whatever its value; any other cell looks at the
+// neighbours it has inside the raster (a masked neighbour counts by its value like any other).  *oceans: the number of
+// masked cells, one add per wavefront that saw any.
+template <class T, int TOPO>
+__global__ __launch_bounds__(NTHR) void k_dh_descent_ocean(const T *__restrict__ z, const uint8_t *__restrict__ ocean,
+                                                         uint32_t *__restrict__ ptr, int w, int h, uint32_t *oceans) {
+  const uint64_t n = (uint64_t)w * h, stride = (uint64_t)gridDim.x * NTHR;
+  uint32_t mine = 0;
+  for (uint64_t c = (uint64_t)blockIdx.x * NTHR + threadIdx.x; c < n; c += stride) {
+    if (ocean[c]) {
+      ptr[c] = DH_NONE;
+      mine++;
+      continue;
+    }
+    const int x = (int)(c % (uint64_t)w), y = (int)(c / (uint64_t)w);
+    unsigned long long best = ((unsigned long long)Key32<T>::to(z[c]) << 32) | c;
+#pragma unroll
+    for (int k = 0; k < TOPO; k++) {
+      const int xx = x + dh_dx<TOPO>(k), yy = y + dh_dy<TOPO>(k);
+      if (xx < 0 || xx >= w || yy < 0 || yy >= h) continue;
+      const uint64_t q = (uint64_t)yy * w + xx;
+      const unsigned long long kq = ((unsigned long long)Key32<T>::to(z[q]) << 32) | q;
+      best = kq < best ? kq : best;
+    }
+    ptr[c] = (uint32_t)best;
+  }
+#pragma unroll
+  for (int d = 32; d; d >>= 1) mine += __shfl_down(mine, d, 64);
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(oceans, mine);
 }
 
 // ptr[c] is always an ancestor of c in the descent forest (or OUTSIDE once the path is known to end there), whatever other
@@ -451,7 +483,7 @@ static void dh_upload(uint32_t *d, const std::vector<T> &v, hipStream_t s) {
 }
 
 template <class T, int TOPO>
-static void dephier_device_t(const T *d_z, int w, int h, int32_t *d_labels, rdgpu_dephier_node *d_table, uint32_t capacity,
+static void dephier_device_t(const T *d_z, int w, int h, const uint8_t *d_ocean, int32_t *d_labels, rdgpu_dephier_node *d_table, uint32_t capacity,
                              uint32_t *d_count, uint32_t *d_leaves, hipStream_t s) {
   const uint64_t n = (uint64_t)w * h;
   Workspace &ws = Workspace::get();
@@ -459,17 +491,25 @@ static void dephier_device_t(const T *d_z, int w, int h, int32_t *d_labels, rdgp
   st.builder = RDGPU_DEPHIER_BUILDER_HOST_KRUSKAL;
   const uint32_t rgrid = (uint32_t)std::min<uint64_t>((n + NTHR - 1) / NTHR, 256u * 32u);
   uint32_t *leaf = ws.buf<uint32_t>("dephier.leaf", n), *off = ws.buf<uint32_t>("dephier.off", n);
-  unsigned long long *words = ws.buf<unsigned long long>("dephier.words", 4);   // [0] records kept, [1] raw, [2] lo: changed, [3] lo: pits
+  // [0] records kept, [1] raw, [2] lo: changed, hi: ocean cells (a masked call), [3] lo: pits
+  unsigned long long *words = ws.buf<unsigned long long>("dephier.words", 4);
   uint32_t *changed = reinterpret_cast<uint32_t *>(words + 2), *pits = reinterpret_cast<uint32_t *>(words + 3);
   uint32_t *hw = ws.host_words();
 
-  RD_LAUNCH("dephier.descent", (k_dh_descent<T, TOPO>), dim3(rgrid), dim3(NTHR), 0, s, d_z, leaf, w, h);
+  if (d_ocean) {
+    RD_HIP(hipMemsetAsync(changed + 1, 0, sizeof(uint32_t), s));
+    RD_LAUNCH("dephier.descent_ocean", (k_dh_descent_ocean<T, TOPO>), dim3(rgrid), dim3(NTHR), 0, s, d_z, d_ocean, leaf, w, h,
+              changed + 1);
+  } else {
+    RD_LAUNCH("dephier.descent", (k_dh_descent<T, TOPO>), dim3(rgrid), dim3(NTHR), 0, s, d_z, leaf, w, h);
+  }
   for (;;) {
     RD_HIP(hipMemsetAsync(changed, 0, sizeof(uint32_t), s));
     RD_LAUNCH("dephier.jump", k_dh_jump, dim3(rgrid), dim3(NTHR), 0, s, leaf, n, changed);
     st.jump_rounds++;
-    RD_HIP(hipMemcpyAsync(hw, changed, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    RD_HIP(hipMemcpyAsync(hw, changed, (d_ocean ? 2 : 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // (+ the ocean count)
     RD_HIP(hipStreamSynchronize(s));
+    if (d_ocean && !hw[1]) throw Error(RDGPU_ERR_ARG, "rdgpu_depression_hierarchy_ocean: no ocean cells");
     if (!hw[0]) break;
     if (st.jump_rounds >= 64) throw Error(RDGPU_ERR_HIP, "rdgpu_depression_hierarchy: the descent paths did not resolve");
   }
@@ -629,27 +669,28 @@ static void check_dephier_args(const void *dem, int w, int h, int topology, cons
 }
 
 template <class T>
-static void dephier_device(const T *d_z, int w, int h, int topology, int32_t *d_labels, rdgpu_dephier_node *d_table,
-                           uint32_t capacity, uint32_t *d_count, uint32_t *d_leaves, hipStream_t s) {
+static void dephier_device(const T *d_z, int w, int h, int topology, const uint8_t *d_ocean, int32_t *d_labels,
+                           rdgpu_dephier_node *d_table, uint32_t capacity, uint32_t *d_count, uint32_t *d_leaves, hipStream_t s) {
   check_dephier_args(d_z, w, h, topology, d_table, capacity, d_count);
-  if (topology == 8) dephier_device_t<T, 8>(d_z, w, h, d_labels, d_table, capacity, d_count, d_leaves, s);
-  else dephier_device_t<T, 4>(d_z, w, h, d_labels, d_table, capacity, d_count, d_leaves, s);
+  if (topology == 8) dephier_device_t<T, 8>(d_z, w, h, d_ocean, d_labels, d_table, capacity, d_count, d_leaves, s);
+  else dephier_device_t<T, 4>(d_z, w, h, d_ocean, d_labels, d_table, capacity, d_count, d_leaves, s);
 }
 
 // host-pointer form: H2D, the device form, D2H of the labels, the two counts and the records that were written
 template <class T>
-static void dephier_host(const T *dem, int w, int h, int topology, int32_t *labels, rdgpu_dephier_node *table, uint32_t capacity,
-                         uint32_t *count, uint32_t *leaves) {
+static void dephier_host(const T *dem, int w, int h, int topology, const uint8_t *ocean, int32_t *labels,
+                         rdgpu_dephier_node *table, uint32_t capacity, uint32_t *count, uint32_t *leaves) {
   check_dephier_args(dem, w, h, topology, table, capacity, count);
   const size_t n = (size_t)w * h;
   HostStage st;
   const T *d = st.in("host.dem", dem, n);
+  const uint8_t *doc = st.in("dephier.host.ocean", ocean, n);   // (null: the border ring)
   uint32_t *dc = st.out("dephier.host.count", count, 1);
   uint32_t *dl = st.out("dephier.host.leaves", leaves, 1);
   int32_t *dlab = st.out("dephier.host.labels", labels, n);
   const uint32_t cap = (uint32_t)std::min<uint64_t>(capacity, 2 * n);   // (fewer than two nodes per cell)
   rdgpu_dephier_node *dt = cap ? Workspace::get().buf<rdgpu_dephier_node>("dephier.host.table", cap) : nullptr;   // (fetched: cut to the count)
-  dephier_device<T>(d, w, h, topology, dlab, dt, cap, dc, dl, nullptr);
+  dephier_device<T>(d, w, h, topology, doc, dlab, dt, cap, dc, dl, nullptr);
   st.finish();
   st.fetch(table, dt, std::min(*count, cap));
 }
@@ -662,13 +703,28 @@ using namespace rdgpu;
   extern "C" int rdgpu_depression_hierarchy_##SUF(const T *dem, int w, int h, int topology, int32_t *labels,          \
                                                   rdgpu_dephier_node *table, uint32_t capacity, uint32_t *count,      \
                                                   uint32_t *leaves) {                                                 \
-    return guarded([&] { dephier_host<T>(dem, w, h, topology, labels, table, capacity, count, leaves); });            \
+    return guarded([&] { dephier_host<T>(dem, w, h, topology, nullptr, labels, table, capacity, count, leaves); });   \
+  }                                                                                                                   \
+  extern "C" int rdgpu_depression_hierarchy_ocean_##SUF(const T *dem, int w, int h, int topology, const uint8_t *ocean, \
+                                                        int32_t *labels, rdgpu_dephier_node *table, uint32_t capacity, \
+                                                        uint32_t *count, uint32_t *leaves) {                          \
+    return guarded([&] { dephier_host<T>(dem, w, h, topology, ocean, labels, table, capacity, count, leaves); });     \
   }                                                                                                                   \
   extern "C" int rdgpu_depression_hierarchy_dev_##SUF(const T *d_dem, int w, int h, int topology, int32_t *d_labels,  \
                                                       rdgpu_dephier_node *d_table, uint32_t capacity,                 \
                                                       uint32_t *d_count, uint32_t *d_leaves, void *stream) {          \
     return guarded([&] {                                                                                              \
-      dephier_device<T>(d_dem, w, h, topology, d_labels, d_table, capacity, d_count, d_leaves, (hipStream_t)stream);  \
+      dephier_device<T>(d_dem, w, h, topology, nullptr, d_labels, d_table, capacity, d_count, d_leaves,               \
+                        (hipStream_t)stream);                                                                         \
+    });                                                                                                               \
+  }                                                                                                                   \
+  extern "C" int rdgpu_depression_hierarchy_ocean_dev_##SUF(const T *d_dem, int w, int h, int topology,               \
+                                                            const uint8_t *d_ocean, int32_t *d_labels,                \
+                                                            rdgpu_dephier_node *d_table, uint32_t capacity,           \
+                                                            uint32_t *d_count, uint32_t *d_leaves, void *stream) {    \
+    return guarded([&] {                                                                                              \
+      dephier_device<T>(d_dem, w, h, topology, d_ocean, d_labels, d_table, capacity, d_count, d_leaves,               \
+                        (hipStream_t)stream);                                                                         \
     });                                                                                                               \
   }
 RD_DEPHIER_API(u8, uint8_t)
@@ -688,6 +744,15 @@ RD_DEPHIER_API(f32, float)
   }                                                                                                                   \
   extern "C" int rdgpu_depression_hierarchy_dev_##SUF(const T *, int, int, int, int32_t *, rdgpu_dephier_node *,      \
                                                       uint32_t, uint32_t *, uint32_t *, void *) {                     \
+    return guarded([&] { throw Error(RDGPU_ERR_UNSUPPORTED, "rdgpu_depression_hierarchy: 64-bit elevations are not supported"); }); \
+  }                                                                                                                   \
+  extern "C" int rdgpu_depression_hierarchy_ocean_##SUF(const T *, int, int, int, const uint8_t *, int32_t *,         \
+                                                        rdgpu_dephier_node *, uint32_t, uint32_t *, uint32_t *) {     \
+    return guarded([&] { throw Error(RDGPU_ERR_UNSUPPORTED, "rdgpu_depression_hierarchy: 64-bit elevations are not supported"); }); \
+  }                                                                                                                   \
+  extern "C" int rdgpu_depression_hierarchy_ocean_dev_##SUF(const T *, int, int, int, const uint8_t *, int32_t *,     \
+                                                            rdgpu_dephier_node *, uint32_t, uint32_t *, uint32_t *,   \
+                                                            void *) {                                                 \
     return guarded([&] { throw Error(RDGPU_ERR_UNSUPPORTED, "rdgpu_depression_hierarchy: 64-bit elevations are not supported"); }); \
   }
 RD_DEPHIER_UNSUPPORTED(f64, double)

@@ -1,0 +1,29 @@
+"""rdgpu::DepressionHierarchy with an ocean mask and rdgpu::BucketFillFromEdges of the C++ shim
+(include/rdgpu/richdem_gpu.hpp): tests/cpp/ocean_shim_test checks the side effects and hand-known answers."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CPP = os.path.join(ROOT, "tests", "cpp")
+EXE = os.path.join(CPP, "ocean_shim_test")
+
+
+def _build(force=False):
+    if force or not os.path.exists(EXE):
+        subprocess.check_call(["make", "-C", CPP, "-f", "Makefile.ocean"] + (["-B"] if force else [])
+                              + ["ocean_shim_test"], stdout=subprocess.DEVNULL)
+
+
+def test_ocean_shim_compiles_and_links(rd):
+    _build(force=True)
+    assert os.path.exists(EXE)
+
+
+@pytest.mark.gpu
+def test_ocean_shim_runs_on_gpu(rd):
+    _build()
+    r = subprocess.run(["timeout", "-k", "10", "120", EXE], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "all checks passed" in r.stdout

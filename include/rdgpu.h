@@ -1191,6 +1191,58 @@ int rdgpu_d8_total_upstream_length_dev(const uint8_t *d_dirs, uint8_t dir_nodata
                                        double cell_y, uint32_t *d_steps /* nullable */, double *d_length /* nullable */,
                                        double length_nodata, void *hip_stream);
 
+/* ---- limited accumulation on the D8 direction forest: losses, decay and capacity --------------
+ * The accumulation above with a per-cell limit on what a cell passes on.  It covers the descent of the reference's
+ * MoveWaterIntoPits (depressions/fill_spill_merge.hpp:226-318: a negative wtd is a storage deficit that inflow fills
+ * before anything moves on) and TauDEM's DecayAccum and TransLimAccum.  Participation, contribution (of `supply`,
+ * against supply_nodata), links, loops and the raster limits are those of rdgpu_d8_flow_accum_weighted_<W>, word for
+ * word.  W is f32 or f64; supply, capacity and factor are rasters of W, converted to double exactly, and everything is
+ * computed in double.  s(v) is v's supply where it contributes, else 0.  For a participating cell v off the loops:
+ *   total(v) = s(v) + the sum of out(u) over the cells u whose link ends at v;
+ *   a        = factor ? factor(v) * total(v) : total(v)      a NaN factor counts as 1; any other factor is used as given
+ *                                                            (IEEE arithmetic: a NaN product counts as 0);
+ *   out(v)   = min(max(a, 0), max(capacity(v), 0))           capacity == NULL or a NaN cell: no limit; +inf is allowed;
+ *   kept(v)  = total(v) - out(v)                             positive: deposited, stored or decayed there; negative: a
+ *                                                            deficit that inflow did not fill.
+ * The out of a cell without a link is what leaves the system there (a pit, a flat cell, the raster's edge, a NoData
+ * neighbour).  A LOOP cell never completes: its out is 0, its kept is its own supply plus what its tributaries brought;
+ * the links of a loop carry nothing.  Cells that do not participate get nodata_out in both planes.
+ * OUTPUTS, each nullable; at least one must be requested, and a plane that is not requested is not written:
+ *   out, kept   float64 [height][width]; they must not overlap each other or an input.
+ *   result      supplied: the sum of the contributing supplies of participating cells; left: the sum of out over the
+ *               participating cells without a link; kept_pos / kept_neg: the sums of the positive / negative kept.
+ *               supplied = left + kept_pos + kept_neg up to summation order: the mass balance.
+ * ARITHMETIC.  The sums arrive in an unspecified order; the result is exact, and therefore reproducible, whenever every
+ * partial sum and product is representable (dyadic supplies and factors of moderate range).  With factor NULL or every
+ * factor in [0, 1] each node map is monotone and non-expansive, so a rounding made upstream never grows on its way down:
+ * out(v) and kept(v) lie within g * (sum of |s| over T(v)), g = k u / (1 - k u), u = 2^-53, k the cells of T(v), of their
+ * exact values, plus one rounding for kept (the k - 1 additions of T(v) give this as in the block above; the up to k
+ * products of a factor raster are roundings too, so with a factor what is PROVEN is 2 k in place of k, and the tests hold
+ * the engine to k).  NO bound is given for factors outside [0, 1].  The four sums of result are plain double sums in no
+ * fixed order.
+ * A null dirs or supply, no output requested, a non-positive size or more than 0xFFFF0000 cells returns RDGPU_ERR_ARG
+ * before any device work; nothing is written then.  Inputs are never written.  The _dev forms take device pointers
+ * (d_result: one device struct) and are ordered on hip_stream without synchronising it: three launches and, with
+ * d_result, one memset.  Scratch (4 bytes per cell; 8 more when neither plane is requested) comes from the workspace pool
+ * under names starting with "accum_limited.". */
+typedef struct rdgpu_limited_result {       /* 32 bytes */
+  double supplied, left, kept_pos, kept_neg;
+} rdgpu_limited_result;
+#define RDGPU_DECL_LIMITED(SUF, W)                                                                                        \
+  int rdgpu_d8_flow_accum_limited_##SUF(const uint8_t *dirs, uint8_t dir_nodata, const W *supply, W supply_nodata,       \
+                                        const W *capacity /* nullable */, const W *factor /* nullable */, int width,     \
+                                        int height, double *out /* nullable */, double *kept /* nullable */,             \
+                                        double nodata_out, rdgpu_limited_result *result /* nullable */);                 \
+  int rdgpu_d8_flow_accum_limited_dev_##SUF(const uint8_t *d_dirs, uint8_t dir_nodata, const W *d_supply,                \
+                                            W supply_nodata, const W *d_capacity /* nullable */,                         \
+                                            const W *d_factor /* nullable */, int width, int height,                     \
+                                            double *d_out /* nullable */, double *d_kept /* nullable */,                 \
+                                            double nodata_out, rdgpu_limited_result *d_result /* nullable */,            \
+                                            void *hip_stream);
+RDGPU_DECL_LIMITED(f32, float)
+RDGPU_DECL_LIMITED(f64, double)
+#undef RDGPU_DECL_LIMITED
+
 /* ---- depression inventory: labels and one record per depression of the fill --------------------
  * No reference counterpart (the flat inventory of the lakes FillDepressions produces; the tree of the depressions
  * inside them is rdgpu_depression_hierarchy_<T> below).  Let W = FillDepressions<topology>(dem) exactly as rdgpu_fill_<T> computes it; NoData is an elevation like any

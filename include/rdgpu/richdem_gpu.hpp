@@ -1161,6 +1161,51 @@ void d8_total_upstream_length(const F &flowdirs, G &length) {
   detail::tlen_run(flowdirs, length, nullptr);
 }
 
+// ---- limited accumulation on the D8 forest: losses, decay and capacity (the definition is in rdgpu.h) ----------------
+namespace detail {
+inline int c_limited(const uint8_t *d, uint8_t dnd, const float *s, float snd, const float *cap, const float *fac, int w, int h,
+                     double *out, double *kept, double ond, rdgpu_limited_result *r) {
+  return rdgpu_d8_flow_accum_limited_f32(d, dnd, s, snd, cap, fac, w, h, out, kept, ond, r);
+}
+inline int c_limited(const uint8_t *d, uint8_t dnd, const double *s, double snd, const double *cap, const double *fac, int w, int h,
+                     double *out, double *kept, double ond, rdgpu_limited_result *r) {
+  return rdgpu_d8_flow_accum_limited_f64(d, dnd, s, snd, cap, fac, w, h, out, kept, ond, r);
+}
+}  // namespace detail
+
+// Every cell passes on out = min(max(factor * total, 0), max(capacity, 0)) of the total that reached it along the GIVEN
+// directions, its own supply included, and keeps the rest: a negative supply is a storage deficit that inflow fills first
+// (the descent of richdem::dephier::MoveWaterIntoPits), `factor` a decay, `capacity` a transport limit.  supply is float or
+// double; capacity and factor (each may be null; a NaN cell means "none here") have its type and size.  *out and *kept
+// (double; each may be null) take the directions' size, geotransform and projection; their NoData, written where the
+// direction is NoData, is *out's if it has been set, else *kept's, and defaults to -1.  Returns the four sums of the mass
+// balance: supplied = left + kept_pos + kept_neg.
+template <class F, class V, class G>
+rdgpu_limited_result d8_flow_accum_limited(const F &flowdirs, const V &supply, const V *capacity, const V *factor, G *out, G *kept) {
+  using T = detail::elem_t<const V>;
+  static_assert(std::is_same<detail::elem_t<const F>, uint8_t>::value || std::is_same<detail::elem_t<F>, uint8_t>::value,
+                "d8_flow_accum_limited: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value,
+                "d8_flow_accum_limited: supply, capacity and factor are float or double");
+  static_assert(std::is_same<detail::elem_t<G>, double>::value, "d8_flow_accum_limited: the out and kept rasters must be double");
+  for (const V *a : {&supply, capacity, factor})
+    if (a && (a->width() != flowdirs.width() || a->height() != flowdirs.height()))
+      throw std::runtime_error("d8_flow_accum_limited: supply, capacity and factor must have the directions' size");
+  const double nodata_out = out ? out->noData() : kept ? kept->noData() : -1.0;
+  for (G *g : {out, kept})
+    if (g) {
+      g->resize(flowdirs);
+      g->setNoData(nodata_out);
+    }
+  rdgpu_limited_result r = {0.0, 0.0, 0.0, 0.0};
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return r;
+  detail::check(detail::c_limited(flowdirs.data(), flowdirs.noData(), (const T *)supply.data(), (T)supply.noData(),
+                                  capacity ? (const T *)capacity->data() : nullptr, factor ? (const T *)factor->data() : nullptr,
+                                  flowdirs.width(), flowdirs.height(), out ? out->data() : nullptr, kept ? kept->data() : nullptr,
+                                  nodata_out, &r), "d8_flow_accum_limited");
+  return r;
+}
+
 // ---- upslope extremes on the D8 forest (no reference counterpart; the definition is in rdgpu.h) ----------------------
 namespace detail {
 #define RDGPU_SHIM_EXTREME(SUF, T)                                                                                      \

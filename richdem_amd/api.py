@@ -1963,6 +1963,81 @@ def d8_total_upstream_length_dev(dirs, cell_x: float = 1.0, cell_y: float = 1.0,
                                                    _stream_ptr()), "rdgpu_d8_total_upstream_length_dev")
 
 
+# ---- limited accumulation: losses, decay and capacity (csrc/accum_limited.hip) -------------------
+_LIMITED_WANT = ("out", "kept")
+
+
+class rdgpu_limited_result(ctypes.Structure):
+    _fields_ = [("supplied", ctypes.c_double), ("left", ctypes.c_double), ("kept_pos", ctypes.c_double),
+                ("kept_neg", ctypes.c_double)]
+
+
+def _limited_want(want, who):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if any(k not in _LIMITED_WANT for k in want):
+        raise RdgpuError(f"{who}: want names planes of {_LIMITED_WANT}")
+    return want
+
+
+def d8_flow_accum_limited(dirs: np.ndarray, supply: np.ndarray, supply_nodata, capacity=None, factor=None, dir_nodata: int = 255,
+                          nodata_out: float = -1.0, want=("out", "kept")) -> dict:
+    """D8 accumulation in which a cell passes on out = min(max(factor * total, 0), max(capacity, 0)) of the total that
+    reached it (its own supply included) and keeps the rest (include/rdgpu.h states the definition): a negative supply is
+    a storage deficit that inflow fills first, `factor` a decay, `capacity` a transport limit; both are optional rasters
+    of the supply's type (float32 or float64), NaN meaning "none here".  Returns a dict with the planes named in `want`
+    ("out", "kept": float64, nodata_out where dirs == dir_nodata; `want` may be empty) and "result": the sums supplied,
+    left (the out of the cells without a link), kept_pos and kept_neg, with supplied = left + kept_pos + kept_neg."""
+    who = "d8_flow_accum_limited"
+    dirs = _dirs2d(dirs, who)
+    if not isinstance(supply, np.ndarray) or supply.shape != dirs.shape or supply.dtype not in (np.float32, np.float64):
+        raise RdgpuError(f"{who}: the supply is a float32 or float64 array of the directions' shape")
+    s = _SUFFIX[supply.dtype]
+    planes = [np.ascontiguousarray(supply)]
+    for name, a in (("capacity", capacity), ("factor", factor)):
+        if a is not None and (not isinstance(a, np.ndarray) or a.shape != dirs.shape or a.dtype != supply.dtype):
+            raise RdgpuError(f"{who}: {name} is an array of the supply's shape and element type, or None")
+        planes.append(None if a is None else np.ascontiguousarray(a))
+    want = _limited_want(want, who)
+    h, w = dirs.shape
+    res = {k: np.empty((h, w), np.float64) for k in want}
+    r = rdgpu_limited_result()
+    check(getattr(lib(), f"rdgpu_d8_flow_accum_limited_{s}")(_ptr(dirs), ctypes.c_uint8(dir_nodata), _ptr(planes[0]),
+                                                             _scalar(s, supply_nodata), _ptr(planes[1]), _ptr(planes[2]), w, h,
+                                                             _ptr(res.get("out")), _ptr(res.get("kept")), ctypes.c_double(nodata_out),
+                                                             ctypes.byref(r)), "rdgpu_d8_flow_accum_limited")
+    res["result"] = {k: getattr(r, k) for k, _ in rdgpu_limited_result._fields_}
+    return res
+
+
+def d8_flow_accum_limited_dev(dirs, supply, supply_nodata, capacity=None, factor=None, dir_nodata: int = 255, out=None, kept=None,
+                              nodata_out: float = -1.0, result=None) -> None:
+    """The planes given (float64 CUDA tensors out, kept [h, w]; result: a float64 CUDA tensor of 4 elements that receives
+    supplied, left, kept_pos, kept_neg) <- d8_flow_accum_limited of dirs (uint8 CUDA tensor), supply and the optional
+    capacity and factor (CUDA tensors, all float32 or all float64), on torch's current stream and without synchronising
+    it.  At least one of out, kept, result must be given; what is not given is not written."""
+    import torch
+
+    who = "d8_flow_accum_limited_dev"
+    h, w = _dev2d(dirs, who, torch.uint8)
+    m = {torch.float32: "f32", torch.float64: "f64"}
+    if supply.dtype not in m:
+        raise RdgpuError(f"{who}: unsupported supply dtype {supply.dtype}")
+    if _dev2d(supply, who) != (h, w):
+        raise RdgpuError(f"{who}: shape mismatch")
+    for a in (capacity, factor):
+        if a is not None and (a.dtype != supply.dtype or _dev2d(a, who) != (h, w)):
+            raise RdgpuError(f"{who}: capacity and factor have the supply's shape and element type")
+    if out is None and kept is None and result is None:
+        raise RdgpuError(f"{who}: no output requested")
+    s = m[supply.dtype]
+    check(getattr(lib(), f"rdgpu_d8_flow_accum_limited_dev_{s}")(
+        ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata), ctypes.c_void_p(supply.data_ptr()), _scalar(s, supply_nodata),
+        ctypes.c_void_p(capacity.data_ptr()) if capacity is not None else None,
+        ctypes.c_void_p(factor.data_ptr()) if factor is not None else None, w, h,
+        _dev_plane(out, (h, w), torch.float64, who), _dev_plane(kept, (h, w), torch.float64, who), ctypes.c_double(nodata_out),
+        _dev_plane(result, (4,), torch.float64, who), _stream_ptr()), "rdgpu_d8_flow_accum_limited_dev")
+
+
 # ---- flow distance and drop (HAND) down to the stop cells over D-infinity / MFD proportions (csrc/mfd_distance.hip) ----
 _DIST_WANT = ("dist", "drop")
 _DIST_STAT = {"ave": 0, "min": 1, "max": 2}

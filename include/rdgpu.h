@@ -1573,6 +1573,63 @@ RDGPU_DECL_DINF_DIST(, f64, double) RDGPU_DECL_DINF_DIST(_flats, f64, double)
 RDGPU_DECL_DINF_DIST(, i8, int8_t) RDGPU_DECL_DINF_DIST(_flats, i8, int8_t)
 #undef RDGPU_DECL_DINF_DIST
 
+/* ---- flow distance and rise UP to the sources (the ridge) over D-infinity / MFD proportions ----
+ * No reference counterpart (TauDEM's DinfDistUp is the product meant).  Proportions and neighbour numbering as in the
+ * block above.
+ *   THE GRAPH is the generic accumulation's with a share threshold.  min_share is a float, min_share >= 0, compared in
+ *   float32.  A LINK d -> c exists when d is a data cell that is not on the raster's edge, c is the neighbour n of d, c
+ *   lies inside the raster and is a data cell, and props(d, n) > min_share.  min_share = 0 is the accumulation's graph;
+ *   this is TauDEM's "proportion threshold", whose default there is 0.5.  A share into NoData or out of the raster is
+ *   dropped; it is not an error.
+ *   The DONORS D(c) of a data cell c are the cells with a link into c.  Cells on the raster's edge have donors but are
+ *   never donors.  A SOURCE is a data cell with D(c) empty; its values are 0.  A cell with donors is decided once all its
+ *   donors are decided.  A cell on a cycle of links, or downstream of one, stays UNDECIDED; nothing waits for it.
+ * Outputs, both float64 [height][width], each a nullable pointer (a call must request at least one):
+ *   dist   the increment over the link d -> c is the length of that step: |cell_x| for a link along x (n in {1, 5}),
+ *          |cell_y| for a link along y (n in {3, 7}), diag otherwise; diag = sqrt(cell_x * cell_x + cell_y * cell_y)
+ *          computed once on the host.
+ *   rise   the increment is (double)z(d) - (double)z(c); it needs the elevations.  Not clamped.
+ * Per donor d, v_d = Q(d) + inc: one double addition (for rise, the one subtraction first).  The donors are taken in the
+ * order of their position m = 1..8 around c (d is the neighbour m of c).  stat combines them:
+ *   stat == 1   Q(c) = min v_d, with <;   stat == 2   Q(c) = max v_d, with >;
+ *   stat == 0   with exactly one donor Q(c) = v_d, no multiply and no divide; otherwise num = sum (double)p * v_d and
+ *               den = sum (double)p, p the share of the link d -> c, both over m = 1..8 in that order starting from 0.0,
+ *               every product and every sum rounded on its own (no fused multiply-add), Q(c) = num / den.
+ * Undecided and NoData cells get out_nodata.  Both outputs are functions of the inputs alone: every value is computed
+ * once, from final operands in a fixed order, so they are reproducible bit for bit.
+ * cell_x and cell_y: their sign is ignored; zero or not finite is RDGPU_ERR_ARG.  A negative or non-finite min_share, a
+ * null props9 (dem), no output requested, rise without elev, stat outside 0..2, a non-positive size or more than
+ * 0xFFFF0000 cells returns RDGPU_ERR_ARG before any device work; nothing is written then.  Inputs are never written.
+ * The _dev forms take device pointers and are ordered on hip_stream without synchronising it.
+ * rdgpu_dinf_distance_up_<T> takes a DEM: the proportions are FM_Tarboton's in compact form and the elevations are the
+ * DEM's.  T: u8 i8 i16 u16 i32 u32 f32 f64.  rdgpu_dinf_distance_up_flats_<T> is the same over the proportions of
+ * rdgpu_fm_tarboton_flats_<T>; at most 0x7FFF0000 cells.
+ * rdgpu_mfd_distance_rounds reports the work-list launches of the last call of either direction, and
+ * RDGPU_MFD_DISTANCE_STACK_BELOW is read by both.  Scratch as for the down entries. */
+int rdgpu_mfd_distance_up(const float *props9, int width, int height, const double *elev /* nullable; required iff rise */,
+                          int stat, float min_share, double cell_x, double cell_y, double *dist /* nullable */,
+                          double *rise /* nullable */, double out_nodata);
+int rdgpu_mfd_distance_up_dev(const float *d_props9, int width, int height,
+                              const double *d_elev /* nullable; required iff rise */, int stat, float min_share,
+                              double cell_x, double cell_y, double *d_dist /* nullable */, double *d_rise /* nullable */,
+                              double out_nodata, void *hip_stream);
+#define RDGPU_DECL_DINF_DISTUP(FL, SUF, T)                                                                                \
+  int rdgpu_dinf_distance_up##FL##_##SUF(const T *dem, T nodata, int width, int height, int stat, float min_share,        \
+                                         double cell_x, double cell_y, double *dist /* nullable */,                       \
+                                         double *rise /* nullable */, double out_nodata);                                 \
+  int rdgpu_dinf_distance_up##FL##_dev_##SUF(const T *d_dem, T nodata, int width, int height, int stat, float min_share,  \
+                                             double cell_x, double cell_y, double *d_dist /* nullable */,                 \
+                                             double *d_rise /* nullable */, double out_nodata, void *hip_stream);
+RDGPU_DECL_DINF_DISTUP(, u8, uint8_t) RDGPU_DECL_DINF_DISTUP(_flats, u8, uint8_t)
+RDGPU_DECL_DINF_DISTUP(, i16, int16_t) RDGPU_DECL_DINF_DISTUP(_flats, i16, int16_t)
+RDGPU_DECL_DINF_DISTUP(, u16, uint16_t) RDGPU_DECL_DINF_DISTUP(_flats, u16, uint16_t)
+RDGPU_DECL_DINF_DISTUP(, i32, int32_t) RDGPU_DECL_DINF_DISTUP(_flats, i32, int32_t)
+RDGPU_DECL_DINF_DISTUP(, u32, uint32_t) RDGPU_DECL_DINF_DISTUP(_flats, u32, uint32_t)
+RDGPU_DECL_DINF_DISTUP(, f32, float) RDGPU_DECL_DINF_DISTUP(_flats, f32, float)
+RDGPU_DECL_DINF_DISTUP(, f64, double) RDGPU_DECL_DINF_DISTUP(_flats, f64, double)
+RDGPU_DECL_DINF_DISTUP(, i8, int8_t) RDGPU_DECL_DINF_DISTUP(_flats, i8, int8_t)
+#undef RDGPU_DECL_DINF_DISTUP
+
 /* ---- synthetic input (test/bench input generator) ----------- */
 int rdgpu_synth_dem_dev_f32(float *d_dem, int width, int height, int seed, int x0, int y0,
                             float tilt, void *hip_stream);

@@ -1031,6 +1031,106 @@ void DinfHand_flats(const E &dem, G &hand, const C &channels, const DistanceDown
   DinfDistanceDown_flats(dem, static_cast<G *>(nullptr), &hand, &channels, opt);
 }
 
+// ---- distance and rise UP to the sources over D-infinity / MFD proportions (no reference counterpart; the definition is
+// in rdgpu.h) ------------------------------------------------------------------------------------------------------------
+struct DistanceUpOptions {
+  DistanceStat stat = DistanceStat::Average;   // how a cell's donors are combined
+  float min_share = 0.0f;                      // a share must exceed it to be a link (TauDEM's proportion threshold)
+  double out_nodata = -9999.0;                 // NoData of both outputs: cells without a value
+};
+namespace detail {
+#define RDGPU_SHIM_DINF_DISTUP(SUF, T)                                                                                      \
+  inline int c_dinf_distup(const T *z, T nd, int w, int h, int st, float ms, double cx, double cy, double *d, double *r,    \
+                           double ond) {                                                                                    \
+    return rdgpu_dinf_distance_up_##SUF(z, nd, w, h, st, ms, cx, cy, d, r, ond);                                            \
+  }                                                                                                                         \
+  inline int c_dinf_distup_flats(const T *z, T nd, int w, int h, int st, float ms, double cx, double cy, double *d,         \
+                                 double *r, double ond) {                                                                   \
+    return rdgpu_dinf_distance_up_flats_##SUF(z, nd, w, h, st, ms, cx, cy, d, r, ond);                                      \
+  }
+RDGPU_SHIM_DINF_DISTUP(u8, uint8_t) RDGPU_SHIM_DINF_DISTUP(i8, int8_t) RDGPU_SHIM_DINF_DISTUP(u16, uint16_t)
+RDGPU_SHIM_DINF_DISTUP(i16, int16_t) RDGPU_SHIM_DINF_DISTUP(u32, uint32_t) RDGPU_SHIM_DINF_DISTUP(i32, int32_t)
+RDGPU_SHIM_DINF_DISTUP(f32, float) RDGPU_SHIM_DINF_DISTUP(f64, double)
+#undef RDGPU_SHIM_DINF_DISTUP
+template <class T>
+int c_dinf_distup(const T *, T, int, int, int, float, double, double, double *, double *, double) {
+  unsupported("DinfDistanceUp");
+}
+template <class T>
+int c_dinf_distup_flats(const T *, T, int, int, int, float, double, double, double *, double *, double) {
+  unsupported("DinfDistanceUp_flats");
+}
+}  // namespace detail
+
+// *dist, *rise (each optional, at least one) <- the distance and the rise from every cell up to the sources (the cells
+// without donors) over the proportions `props` (Array3D<float>).  `elevations` (Array2D<double>, required for rise) are
+// taken as they are.  Cell lengths cell_x, cell_y.  The outputs take the proportions' width and height, NoData
+// opt.out_nodata.
+template <class P, class E, class G>
+void FlowDistanceUp(const P &props, const E *elevations, G *dist, G *rise, double cell_x = 1.0, double cell_y = 1.0,
+                    const DistanceUpOptions &opt = DistanceUpOptions()) {
+  static_assert(std::is_same<detail::elem_t<E>, double>::value, "FlowDistanceUp: the elevations must be Array2D<double>");
+  const int w = props.width(), h = props.height();
+  if (!dist && !rise) throw std::runtime_error("FlowDistanceUp: no output requested");
+  if (rise && !elevations) throw std::runtime_error("FlowDistanceUp: the rise needs the elevations");
+  if (elevations && (elevations->width() != w || elevations->height() != h))
+    throw std::runtime_error("FlowDistanceUp: the elevations must have the proportions' size");
+  double *pd = detail::dist_plane(dist, w, h, opt.out_nodata), *pr = detail::dist_plane(rise, w, h, opt.out_nodata);
+  if (w == 0 || h == 0) return;
+  const float *p9 = detail::raw3(const_cast<P &>(props), 0);   // (the reference's accessor is non-const; read only)
+  detail::check(rdgpu_mfd_distance_up(p9, w, h, elevations ? (const double *)elevations->data() : nullptr, (int)opt.stat,
+                                      opt.min_share, cell_x, cell_y, pd, pr, opt.out_nodata), "FlowDistanceUp");
+}
+// the distance alone
+template <class P, class G>
+void FlowDistanceUp(const P &props, G &dist, double cell_x = 1.0, double cell_y = 1.0,
+                    const DistanceUpOptions &opt = DistanceUpOptions()) {
+  const int w = props.width(), h = props.height();
+  double *pd = detail::dist_plane(&dist, w, h, opt.out_nodata);
+  if (w == 0 || h == 0) return;
+  detail::check(rdgpu_mfd_distance_up(detail::raw3(const_cast<P &>(props), 0), w, h, nullptr, (int)opt.stat, opt.min_share,
+                                      cell_x, cell_y, pd, nullptr, opt.out_nodata), "FlowDistanceUp");
+}
+
+// The same over the D-infinity proportions of a DEM (FM_Tarboton, never materialised), elevations and cell lengths
+// (|geotransform[1]|, |geotransform[5]|) the DEM's; the outputs take the DEM's size, geotransform and projection.
+namespace detail {
+template <class E, class G, class Fn>
+void dinf_distance_up(const E &dem, G *dist, G *rise, const DistanceUpOptions &opt, Fn entry, const char *who) {
+  using T = elem_t<E>;
+  const int w = dem.width(), h = dem.height();
+  if (!dist && !rise) throw std::runtime_error(std::string(who) + ": no output requested");
+  double cx, cy;
+  cell_lengths(dem, who, cx, cy);
+  for (G *o : {dist, rise})
+    if (o) {
+      static_assert(std::is_same<elem_t<G>, double>::value, "DinfDistanceUp: the output rasters must be double");
+      o->resize(dem);
+      o->setNoData(opt.out_nodata);
+    }
+  if (w == 0 || h == 0) return;
+  check(entry((const T *)dem.data(), (T)dem.noData(), w, h, (int)opt.stat, opt.min_share, cx, cy, dist ? dist->data() : nullptr,
+              rise ? rise->data() : nullptr, opt.out_nodata), who);
+}
+}  // namespace detail
+template <class E, class G>
+void DinfDistanceUp(const E &dem, G *dist, G *rise, const DistanceUpOptions &opt = DistanceUpOptions()) {
+  using T = detail::elem_t<E>;
+  detail::dinf_distance_up(dem, dist, rise, opt,
+                           [](const T *z, T nd, int w, int h, int st, float ms, double cx, double cy, double *d, double *r,
+                              double ond) { return detail::c_dinf_distup(z, nd, w, h, st, ms, cx, cy, d, r, ond); },
+                           "DinfDistanceUp");
+}
+// over the proportions of FM_Tarboton_flats: the drainable flats of the DEM pass flow on
+template <class E, class G>
+void DinfDistanceUp_flats(const E &dem, G *dist, G *rise, const DistanceUpOptions &opt = DistanceUpOptions()) {
+  using T = detail::elem_t<E>;
+  detail::dinf_distance_up(dem, dist, rise, opt,
+                           [](const T *z, T nd, int w, int h, int st, float ms, double cx, double cy, double *d, double *r,
+                              double ond) { return detail::c_dinf_distup_flats(z, nd, w, h, st, ms, cx, cy, d, r, ond); },
+                           "DinfDistanceUp_flats");
+}
+
 // ---- longest upstream flow path on the D8 forest (no reference counterpart; the definition is in rdgpu.h) -----------
 // length <- the length of the longest flow path that ends at each cell; *from_cell (optional, uint32_t) <- the flat index
 // of that path's head, the lowest on a tie; *on_basin_path (optional, uint8_t) <- 1 on the longest path of every basin,

@@ -2128,7 +2128,8 @@ def dinf_hand_flats(dem: np.ndarray, nodata, chan: np.ndarray, stat="ave", stric
 
 
 def mfd_distance_rounds() -> int:
-    """Work-list launches of the last mfd_distance_down / dinf_distance_down / dinf_hand call or _dev form."""
+    """Work-list launches of the last mfd_distance_down / dinf_distance_down / dinf_hand call or _dev form, or of the last
+    mfd_distance_up / dinf_distance_up call or _dev form: whichever came last."""
     r = ctypes.c_uint32(0)
     check(lib().rdgpu_mfd_distance_rounds(ctypes.byref(r)), "rdgpu_mfd_distance_rounds")
     return r.value
@@ -2204,6 +2205,142 @@ def dinf_hand_dev(dem, nodata, chan, out, stat="ave", strict: bool = True, out_n
 def dinf_hand_flats_dev(dem, nodata, chan, out, stat="ave", strict: bool = True, out_nodata: float = -9999.0) -> None:
     """out (float64 CUDA tensor) <- dinf_hand_flats of dem and the uint8 CUDA channel mask chan."""
     dinf_distance_down_flats_dev(dem, nodata, chan, stat, strict, (1.0, 1.0), out_nodata, drop=out)
+
+
+# ---- flow distance and rise up to the sources over D-infinity / MFD proportions (csrc/mfd_distance_up.hip) ----
+_DISTUP_WANT = ("dist", "rise")
+
+
+def _distup_want(want, who):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in _DISTUP_WANT for k in want):
+        raise RdgpuError(f"{who}: want names at least one of {_DISTUP_WANT}")
+    return want
+
+
+def _distup_stat(stat, who) -> int:
+    s = _dist_stat(stat, who)
+    if s not in (0, 1, 2):
+        raise RdgpuError(f"{who}: stat is one of {tuple(_DIST_STAT)} or 0..2")
+    return s
+
+
+def _min_share(min_share, who):
+    """min_share as the float32 the engine compares with; negative or not finite is refused here as it is there"""
+    try:
+        v = np.float32(min_share)
+    except (TypeError, ValueError):
+        raise RdgpuError(f"{who}: min_share is a number") from None
+    if not np.isfinite(v) or v < 0:
+        raise RdgpuError(f"{who}: min_share must be finite and >= 0")
+    return ctypes.c_float(float(v))
+
+
+def _cell2_checked(cell, who):
+    cx, cy = _cell2(cell, who)
+    if not (np.isfinite(cx.value) and np.isfinite(cy.value)) or cx.value == 0 or cy.value == 0:
+        raise RdgpuError(f"{who}: cell sizes must be finite and non-zero")
+    return cx, cy
+
+
+def mfd_distance_up(props: np.ndarray, elev: np.ndarray | None = None, stat="ave", min_share: float = 0.0, cell=(1.0, 1.0),
+                    out_nodata: float = -1.0, want=("dist",)) -> dict:
+    """Distance ("dist") and rise ("rise", needs elev) up to the sources over a proportions array [h, w, 9]
+    (include/rdgpu.h states the definition): a dict with the float64 planes named in `want`.  stat "ave" / "min" / "max"
+    combines a cell's donors (longest, shortest or share-weighted mean way up to the ridge); min_share: only shares above
+    it are links (TauDEM's proportion threshold; 0: the accumulation's graph); out_nodata where there is no value.  elev of
+    any real dtype is taken as float64."""
+    who = "mfd_distance_up"
+    props = _props3(props, who)
+    h, w = props.shape[:2]
+    want = _distup_want(want, who)
+    if elev is not None:
+        if not isinstance(elev, np.ndarray) or elev.shape != (h, w):
+            raise RdgpuError(f"{who}: elev is an array of the proportions' raster shape")
+        elev = np.ascontiguousarray(elev, dtype=np.float64)
+    elif "rise" in want:
+        raise RdgpuError(f"{who}: rise needs the elevations")
+    st, ms = _distup_stat(stat, who), _min_share(min_share, who)
+    cx, cy = _cell2_checked(cell, who)
+    out = {k: np.empty((h, w), np.float64) for k in _DISTUP_WANT if k in want}
+    check(lib().rdgpu_mfd_distance_up(_ptr(props), w, h, _ptr(elev), st, ms, cx, cy, _ptr(out.get("dist")), _ptr(out.get("rise")),
+                                      ctypes.c_double(out_nodata)), "rdgpu_mfd_distance_up")
+    return out
+
+
+def _dinf_distance_up(who, dem, nodata, stat, min_share, cell, out_nodata, want) -> dict:
+    dem, s = _elev(dem, who, mfd=True)
+    h, w = dem.shape
+    want = _distup_want(want, who)
+    st, ms = _distup_stat(stat, who), _min_share(min_share, who)
+    cx, cy = _cell2_checked(cell, who)
+    nd = _scalar(s, nodata)
+    out = {k: np.empty((h, w), np.float64) for k in _DISTUP_WANT if k in want}
+    check(getattr(lib(), f"rdgpu_{who}_{s}")(_ptr(dem), nd, w, h, st, ms, cx, cy, _ptr(out.get("dist")), _ptr(out.get("rise")),
+                                             ctypes.c_double(out_nodata)), "rdgpu_" + who)
+    return out
+
+
+def dinf_distance_up(dem: np.ndarray, nodata, stat="ave", min_share: float = 0.0, cell=(1.0, 1.0), out_nodata: float = -1.0,
+                     want=("dist",)) -> dict:
+    """mfd_distance_up over the D-infinity proportions of dem (FM_Tarboton, never materialised), elevations the DEM's."""
+    return _dinf_distance_up("dinf_distance_up", dem, nodata, stat, min_share, cell, out_nodata, want)
+
+
+def dinf_distance_up_flats(dem: np.ndarray, nodata, stat="ave", min_share: float = 0.0, cell=(1.0, 1.0), out_nodata: float = -1.0,
+                           want=("dist",)) -> dict:
+    """dinf_distance_up over the proportions of fm_tarboton_flats: the drainable flats of dem pass flow on."""
+    return _dinf_distance_up("dinf_distance_up_flats", dem, nodata, stat, min_share, cell, out_nodata, want)
+
+
+def mfd_distance_up_dev(props, elev=None, stat="ave", min_share: float = 0.0, cell=(1.0, 1.0), out_nodata: float = -1.0, dist=None,
+                        rise=None) -> None:
+    """The planes given (float64 CUDA tensors [h, w]) <- mfd_distance_up of props (float32 CUDA tensor [h, w, 9]), elev a
+    float64 CUDA tensor; on torch's current stream and without synchronising it.  At least one plane must be given."""
+    import torch
+
+    who = "mfd_distance_up_dev"
+    if not (props.is_cuda and props.dim() == 3 and props.shape[2] == 9 and props.is_contiguous() and props.dtype == torch.float32):
+        raise RdgpuError(f"{who}: expected a contiguous float32 tensor [h, w, 9] on the GPU")
+    h, w = props.shape[:2]
+    if dist is None and rise is None:
+        raise RdgpuError(f"{who}: no output requested")
+    if rise is not None and elev is None:
+        raise RdgpuError(f"{who}: rise needs the elevations")
+    st, ms = _distup_stat(stat, who), _min_share(min_share, who)
+    cx, cy = _cell2_checked(cell, who)
+    pe, pd, pr = (_dev_plane(t, (h, w), torch.float64, who) for t in (elev, dist, rise))
+    check(lib().rdgpu_mfd_distance_up_dev(ctypes.c_void_p(props.data_ptr()), w, h, pe, st, ms, cx, cy, pd, pr,
+                                          ctypes.c_double(out_nodata), _stream_ptr()), "rdgpu_mfd_distance_up_dev")
+
+
+def _dinf_distance_up_dev(who, entry, dem, nodata, stat, min_share, cell, out_nodata, dist, rise) -> None:
+    import torch
+
+    h, w = _dev2d(dem, who)
+    s = _torch_mfd_suffix(dem, who)
+    if dist is None and rise is None:
+        raise RdgpuError(f"{who}: no output requested")
+    st, ms = _distup_stat(stat, who), _min_share(min_share, who)
+    cx, cy = _cell2_checked(cell, who)
+    pd, pr = (_dev_plane(t, (h, w), torch.float64, who) for t in (dist, rise))
+    check(getattr(lib(), f"{entry}_{s}")(ctypes.c_void_p(dem.data_ptr()), _scalar(s, nodata), w, h, st, ms, cx, cy, pd, pr,
+                                         ctypes.c_double(out_nodata), _stream_ptr()), entry)
+
+
+def dinf_distance_up_dev(dem, nodata, stat="ave", min_share: float = 0.0, cell=(1.0, 1.0), out_nodata: float = -1.0, dist=None,
+                         rise=None) -> None:
+    """The planes given (float64 CUDA tensors) <- dinf_distance_up of dem (CUDA tensor of any element type torch has of
+    int8 .. uint32, float32, float64), on torch's current stream.  At least one plane must be given."""
+    _dinf_distance_up_dev("dinf_distance_up_dev", "rdgpu_dinf_distance_up_dev", dem, nodata, stat, min_share, cell, out_nodata,
+                          dist, rise)
+
+
+def dinf_distance_up_flats_dev(dem, nodata, stat="ave", min_share: float = 0.0, cell=(1.0, 1.0), out_nodata: float = -1.0,
+                               dist=None, rise=None) -> None:
+    """dinf_distance_up_dev over the proportions of fm_tarboton_flats."""
+    _dinf_distance_up_dev("dinf_distance_up_flats_dev", "rdgpu_dinf_distance_up_flats_dev", dem, nodata, stat, min_share, cell,
+                          out_nodata, dist, rise)
 
 
 # ---- D-infinity across flats (include/rdgpu.h "D-infinity across flats") ---------------------------------------

@@ -203,7 +203,7 @@ __global__ __launch_bounds__(NTHR) void k_dist_finalize(const uint32_t *__restri
     }
 }
 
-static uint32_t g_dist_rounds = 0;
+uint32_t g_dist_rounds = 0;   // mfd_distance_up.hip sets it too: the last call of either direction
 
 struct DistParams {
   int stat, strict;

@@ -1630,6 +1630,71 @@ RDGPU_DECL_DINF_DISTUP(, f64, double) RDGPU_DECL_DINF_DISTUP(_flats, f64, double
 RDGPU_DECL_DINF_DISTUP(, i8, int8_t) RDGPU_DECL_DINF_DISTUP(_flats, i8, int8_t)
 #undef RDGPU_DECL_DINF_DISTUP
 
+/* ---- reverse accumulation, largest weight downslope and upslope dependence over D-infinity / MFD proportions ----
+ * No reference counterpart (TauDEM's DinfRevAccum with its dmax, and DinfUpDependence, are the products meant): a
+ * quantity summed or maximised over everything that lies DOWNSLOPE of a cell, weighted by the shares -- the transpose of
+ * the accumulation.  Proportions, neighbour numbering 1..8 and the graph are those of "flow distance and drop DOWN"
+ * above: the RECEIVERS R(c) of a data cell c are the neighbours n with props(c, n) > 0 that lie inside the raster and
+ * are data cells.  A cell on the raster's edge has R(c) empty.  A share into NoData is dropped.
+ * Inputs:
+ *   dest      uint8 mask, nullable.  A data cell with dest != 0 is ABSORBING: its R(c) is taken as empty, what lies
+ *             below it does not count, and it is never a donor for the counters.
+ *   weights   float64 raster, nullable.  With a raster given, a data cell CONTRIBUTES iff its weight is not
+ *             weight_nodata and is not a NaN (the compare is == on doubles, so -0.0 equals a NoData of 0.0; pass a NaN
+ *             for "no NoData value": rdgpu_d8_flow_accum_weighted's convention).  With weights == NULL, dest is
+ *             required, the weight is 1.0 on absorbing cells and 0.0 elsewhere, and every data cell contributes: the
+ *             upslope dependence, the fraction of a cell's flow that reaches the destination set.  A cell that does not
+ *             contribute still passes on what lies below it.
+ * A cell is DECIDED once every member of R(c) is decided; the thread that decides it computes both planes once, from
+ * final operands, in the fixed order n = 1..8.  A cell on a cycle of positive shares, or one that depends on such a cell,
+ * stays UNDECIDED; nothing waits for it.  An absorbing cell on a cycle is decided and breaks the cycle.
+ * Outputs, both float64 [height][width], each a nullable pointer (a call must request at least one):
+ *   racc   S = w(c) if c contributes, else +0.0; then, for n = 1..8 in that order and each receiver,
+ *          S = S + (double)p_n * racc(n), every product and every sum rounded on its own (no fused multiply-add).
+ *          Infinities are added as IEEE adds them.  With shares that sum to 1 and a per-cell travel time as the weight
+ *          this is the expected travel time to the outlet (with dest given: to the absorbing cells).
+ *   wmax   (needs weights) the largest contributing weight at c or at any cell reachable from c over receivers, stopping
+ *          at absorbing cells: start with w(c) if c contributes; then, for n = 1..8 in that order, take wmax(n) of every
+ *          receiver that HAS a maximum when c has none yet or when it is > the current one.  A decided cell with no
+ *          contributing weight at or below it has no maximum: it gets out_nodata in wmax, while its racc is a plain sum
+ *          (0.0 if nothing contributes).
+ * Undecided and NoData cells get out_nodata in both planes.  Both planes are functions of the inputs alone and are
+ * reproducible bit for bit.
+ * A null props9 (dem), no output requested, wmax without weights, neither weights nor dest, a non-positive size or more
+ * than 0xFFFF0000 cells (0x7FFF0000 for the _flats forms) returns RDGPU_ERR_ARG before any device work; nothing is
+ * written then.  Inputs are never written.  The _dev forms take device pointers and are ordered on hip_stream without
+ * synchronising it.
+ * rdgpu_dinf_reverse_accum_<T> takes a DEM: the proportions are FM_Tarboton's in compact form (5 bytes per cell, the
+ * array is never materialised).  T: u8 i8 i16 u16 i32 u32 f32 f64.  rdgpu_dinf_reverse_accum_flats_<T> is the same over
+ * the proportions of rdgpu_fm_tarboton_flats_<T>.
+ * rdgpu_mfd_distance_rounds reports the work-list launches of the last call of these or of either distance engine, and
+ * RDGPU_MFD_DISTANCE_STACK_BELOW is read here too.  Scratch: the accumulation's 13 bytes per cell, from the workspace
+ * pool. */
+int rdgpu_mfd_reverse_accum(const float *props9, int width, int height, const double *weights /* nullable */,
+                            double weight_nodata, const uint8_t *dest /* nullable */, double *racc /* nullable */,
+                            double *wmax /* nullable */, double out_nodata);
+int rdgpu_mfd_reverse_accum_dev(const float *d_props9, int width, int height, const double *d_weights /* nullable */,
+                                double weight_nodata, const uint8_t *d_dest /* nullable */, double *d_racc /* nullable */,
+                                double *d_wmax /* nullable */, double out_nodata, void *hip_stream);
+#define RDGPU_DECL_DINF_REV(FL, SUF, T)                                                                                   \
+  int rdgpu_dinf_reverse_accum##FL##_##SUF(const T *dem, T nodata, int width, int height,                                 \
+                                           const double *weights /* nullable */, double weight_nodata,                   \
+                                           const uint8_t *dest /* nullable */, double *racc /* nullable */,               \
+                                           double *wmax /* nullable */, double out_nodata);                               \
+  int rdgpu_dinf_reverse_accum##FL##_dev_##SUF(const T *d_dem, T nodata, int width, int height,                           \
+                                               const double *d_weights /* nullable */, double weight_nodata,             \
+                                               const uint8_t *d_dest /* nullable */, double *d_racc /* nullable */,       \
+                                               double *d_wmax /* nullable */, double out_nodata, void *hip_stream);
+RDGPU_DECL_DINF_REV(, u8, uint8_t) RDGPU_DECL_DINF_REV(_flats, u8, uint8_t)
+RDGPU_DECL_DINF_REV(, i16, int16_t) RDGPU_DECL_DINF_REV(_flats, i16, int16_t)
+RDGPU_DECL_DINF_REV(, u16, uint16_t) RDGPU_DECL_DINF_REV(_flats, u16, uint16_t)
+RDGPU_DECL_DINF_REV(, i32, int32_t) RDGPU_DECL_DINF_REV(_flats, i32, int32_t)
+RDGPU_DECL_DINF_REV(, u32, uint32_t) RDGPU_DECL_DINF_REV(_flats, u32, uint32_t)
+RDGPU_DECL_DINF_REV(, f32, float) RDGPU_DECL_DINF_REV(_flats, f32, float)
+RDGPU_DECL_DINF_REV(, f64, double) RDGPU_DECL_DINF_REV(_flats, f64, double)
+RDGPU_DECL_DINF_REV(, i8, int8_t) RDGPU_DECL_DINF_REV(_flats, i8, int8_t)
+#undef RDGPU_DECL_DINF_REV
+
 /* ---- synthetic input (test/bench input generator) ----------- */
 int rdgpu_synth_dem_dev_f32(float *d_dem, int width, int height, int seed, int x0, int y0,
                             float tilt, void *hip_stream);

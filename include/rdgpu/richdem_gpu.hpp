@@ -18,6 +18,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -1129,6 +1130,116 @@ void DinfDistanceUp_flats(const E &dem, G *dist, G *rise, const DistanceUpOption
                            [](const T *z, T nd, int w, int h, int st, float ms, double cx, double cy, double *d, double *r,
                               double ond) { return detail::c_dinf_distup_flats(z, nd, w, h, st, ms, cx, cy, d, r, ond); },
                            "DinfDistanceUp_flats");
+}
+
+// ---- reverse accumulation, largest weight downslope and upslope dependence over D-infinity / MFD proportions (no
+// reference counterpart; the definition is in rdgpu.h) ---------------------------------------------------------------
+struct ReverseAccumOptions {
+  double weight_nodata = std::numeric_limits<double>::quiet_NaN();   // cells with this weight (and NaNs) do not contribute
+  double out_nodata = -9999.0;                                       // NoData of the outputs: cells without a value
+};
+namespace detail {
+#define RDGPU_SHIM_DINF_REV(SUF, T)                                                                                         \
+  inline int c_dinf_rev(const T *z, T nd, int w, int h, const double *wt, double wnd, const uint8_t *de, double *ra,        \
+                        double *wm, double ond) {                                                                           \
+    return rdgpu_dinf_reverse_accum_##SUF(z, nd, w, h, wt, wnd, de, ra, wm, ond);                                           \
+  }                                                                                                                         \
+  inline int c_dinf_rev_flats(const T *z, T nd, int w, int h, const double *wt, double wnd, const uint8_t *de, double *ra,  \
+                              double *wm, double ond) {                                                                     \
+    return rdgpu_dinf_reverse_accum_flats_##SUF(z, nd, w, h, wt, wnd, de, ra, wm, ond);                                     \
+  }
+RDGPU_SHIM_DINF_REV(u8, uint8_t) RDGPU_SHIM_DINF_REV(i8, int8_t) RDGPU_SHIM_DINF_REV(u16, uint16_t)
+RDGPU_SHIM_DINF_REV(i16, int16_t) RDGPU_SHIM_DINF_REV(u32, uint32_t) RDGPU_SHIM_DINF_REV(i32, int32_t)
+RDGPU_SHIM_DINF_REV(f32, float) RDGPU_SHIM_DINF_REV(f64, double)
+#undef RDGPU_SHIM_DINF_REV
+template <class T>
+int c_dinf_rev(const T *, T, int, int, const double *, double, const uint8_t *, double *, double *, double) {
+  unsupported("DinfReverseAccumulation");
+}
+template <class T>
+int c_dinf_rev_flats(const T *, T, int, int, const double *, double, const uint8_t *, double *, double *, double) {
+  unsupported("DinfReverseAccumulation_flats");
+}
+template <class W>
+const double *rev_weights(int w, int h, const W *weights, const char *fn) {
+  if (!weights) return nullptr;
+  static_assert(std::is_same<elem_t<W>, double>::value, "reverse accumulation: the weights must be Array2D<double>");
+  if (weights->width() != w || weights->height() != h)
+    throw std::runtime_error(std::string(fn) + ": the weights must have the raster's size");
+  return weights->data();
+}
+}  // namespace detail
+
+// *racc, *wmax (each optional, at least one; wmax needs weights) <- the reverse accumulation and the largest weight
+// downslope over the proportions `props` (Array3D<float>).  `weights` (Array2D<double>, optional) and `dest`
+// (Array2D<uint8_t>, optional: the absorbing cells); without weights this is the upslope dependence on dest.  The outputs
+// take the proportions' width and height, NoData opt.out_nodata.
+template <class P, class W, class C, class G>
+void FlowReverseAccumulation(const P &props, const W *weights, const C *dest, G *racc, G *wmax,
+                             const ReverseAccumOptions &opt = ReverseAccumOptions()) {
+  const int w = props.width(), h = props.height();
+  if (!racc && !wmax) throw std::runtime_error("FlowReverseAccumulation: no output requested");
+  if (wmax && !weights) throw std::runtime_error("FlowReverseAccumulation: wmax needs the weights");
+  if (!weights && !dest) throw std::runtime_error("FlowReverseAccumulation: neither weights nor dest given");
+  const double *pw = detail::rev_weights(w, h, weights, "FlowReverseAccumulation");
+  const uint8_t *mask = detail::dist_mask(w, h, dest, "FlowReverseAccumulation");
+  double *pa = detail::dist_plane(racc, w, h, opt.out_nodata), *pm = detail::dist_plane(wmax, w, h, opt.out_nodata);
+  if (w == 0 || h == 0) return;
+  const float *p9 = detail::raw3(const_cast<P &>(props), 0);   // (the reference's accessor is non-const; read only)
+  detail::check(rdgpu_mfd_reverse_accum(p9, w, h, pw, opt.weight_nodata, mask, pa, pm, opt.out_nodata), "FlowReverseAccumulation");
+}
+
+// The same over the D-infinity proportions of a DEM (FM_Tarboton, never materialised); the outputs take the DEM's size,
+// geotransform and projection.
+namespace detail {
+template <class E, class W, class C, class G, class Fn>
+void dinf_reverse(const E &dem, const W *weights, const C *dest, G *racc, G *wmax, const ReverseAccumOptions &opt, Fn entry,
+                  const char *who) {
+  using T = elem_t<E>;
+  const int w = dem.width(), h = dem.height();
+  if (!racc && !wmax) throw std::runtime_error(std::string(who) + ": no output requested");
+  if (wmax && !weights) throw std::runtime_error(std::string(who) + ": wmax needs the weights");
+  if (!weights && !dest) throw std::runtime_error(std::string(who) + ": neither weights nor dest given");
+  const double *pw = rev_weights(w, h, weights, who);
+  const uint8_t *mask = dist_mask(w, h, dest, who);
+  for (G *o : {racc, wmax})
+    if (o) {
+      static_assert(std::is_same<elem_t<G>, double>::value, "DinfReverseAccumulation: the output rasters must be double");
+      o->resize(dem);
+      o->setNoData(opt.out_nodata);
+    }
+  if (w == 0 || h == 0) return;
+  check(entry((const T *)dem.data(), (T)dem.noData(), w, h, pw, opt.weight_nodata, mask, racc ? racc->data() : nullptr,
+              wmax ? wmax->data() : nullptr, opt.out_nodata), who);
+}
+}  // namespace detail
+template <class E, class W, class C, class G>
+void DinfReverseAccumulation(const E &dem, const W *weights, const C *dest, G *racc, G *wmax,
+                             const ReverseAccumOptions &opt = ReverseAccumOptions()) {
+  using T = detail::elem_t<E>;
+  detail::dinf_reverse(dem, weights, dest, racc, wmax, opt,
+                       [](const T *z, T nd, int w, int h, const double *wt, double wnd, const uint8_t *de, double *ra, double *wm,
+                          double ond) { return detail::c_dinf_rev(z, nd, w, h, wt, wnd, de, ra, wm, ond); },
+                       "DinfReverseAccumulation");
+}
+// over the proportions of FM_Tarboton_flats: the drainable flats of the DEM pass flow on
+template <class E, class W, class C, class G>
+void DinfReverseAccumulation_flats(const E &dem, const W *weights, const C *dest, G *racc, G *wmax,
+                                   const ReverseAccumOptions &opt = ReverseAccumOptions()) {
+  using T = detail::elem_t<E>;
+  detail::dinf_reverse(dem, weights, dest, racc, wmax, opt,
+                       [](const T *z, T nd, int w, int h, const double *wt, double wnd, const uint8_t *de, double *ra, double *wm,
+                          double ond) { return detail::c_dinf_rev_flats(z, nd, w, h, wt, wnd, de, ra, wm, ond); },
+                       "DinfReverseAccumulation_flats");
+}
+// dep <- the fraction of every cell's flow that reaches the cells of `dest` (TauDEM's DinfUpDependence)
+template <class E, class C, class G>
+void DinfUpslopeDependence(const E &dem, const C &dest, G &dep, const ReverseAccumOptions &opt = ReverseAccumOptions()) {
+  DinfReverseAccumulation(dem, static_cast<const G *>(nullptr), &dest, &dep, static_cast<G *>(nullptr), opt);
+}
+template <class E, class C, class G>
+void DinfUpslopeDependence_flats(const E &dem, const C &dest, G &dep, const ReverseAccumOptions &opt = ReverseAccumOptions()) {
+  DinfReverseAccumulation_flats(dem, static_cast<const G *>(nullptr), &dest, &dep, static_cast<G *>(nullptr), opt);
 }
 
 // ---- longest upstream flow path on the D8 forest (no reference counterpart; the definition is in rdgpu.h) -----------

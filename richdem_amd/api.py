@@ -2343,6 +2343,146 @@ def dinf_distance_up_flats_dev(dem, nodata, stat="ave", min_share: float = 0.0, 
                           out_nodata, dist, rise)
 
 
+# ---- reverse accumulation and upslope dependence over D-infinity / MFD proportions (csrc/mfd_reverse.hip) ----
+_REV_WANT = ("racc", "wmax")
+
+
+def _rev_want(want, who):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in _REV_WANT for k in want):
+        raise RdgpuError(f"{who}: want names at least one of {_REV_WANT}")
+    return want
+
+
+def _rev_inputs(weights, dest, weight_nodata, want, shape, who):
+    """the weights as float64, the mask, weight_nodata as a double (None: a NaN, "no NoData value")"""
+    dest = _mask2d(dest, shape, who)
+    if weights is not None:
+        if not isinstance(weights, np.ndarray) or weights.shape != tuple(shape):
+            raise RdgpuError(f"{who}: weights is an array of the raster's shape")
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+    elif dest is None:
+        raise RdgpuError(f"{who}: neither weights nor dest given")
+    elif "wmax" in want:
+        raise RdgpuError(f"{who}: wmax needs the weights")
+    return weights, dest, ctypes.c_double(float("nan") if weight_nodata is None else float(weight_nodata))
+
+
+def mfd_reverse_accum(props: np.ndarray, weights: np.ndarray | None = None, dest: np.ndarray | None = None, weight_nodata=None,
+                      out_nodata: float = -1.0, want=("racc",)) -> dict:
+    """Reverse accumulation ("racc": the weights summed over everything downslope of a cell, by the shares) and the largest
+    weight downslope ("wmax", needs weights) over a proportions array [h, w, 9] (include/rdgpu.h states the definition): a
+    dict with the float64 planes named in `want`, in that order.  dest: an optional uint8 mask of absorbing cells; weights
+    of any real dtype are taken as float64, cells equal to weight_nodata (None: no such value) and NaNs do not contribute;
+    without weights the weight is 1 on dest and 0 elsewhere (the upslope dependence).  out_nodata where there is no value."""
+    who = "mfd_reverse_accum"
+    props = _props3(props, who)
+    h, w = props.shape[:2]
+    want = _rev_want(want, who)
+    weights, dest, wnd = _rev_inputs(weights, dest, weight_nodata, want, (h, w), who)
+    out = {k: np.empty((h, w), np.float64) for k in want}
+    check(lib().rdgpu_mfd_reverse_accum(_ptr(props), w, h, _ptr(weights), wnd, _ptr(dest), _ptr(out.get("racc")),
+                                        _ptr(out.get("wmax")), ctypes.c_double(out_nodata)), "rdgpu_mfd_reverse_accum")
+    return out
+
+
+def mfd_upslope_dependence(props: np.ndarray, dest: np.ndarray, out_nodata: float = -1.0) -> np.ndarray:
+    """float64 raster: the fraction of every cell's flow that reaches the cells of the uint8 mask dest over the proportions
+    (TauDEM's DinfUpDependence): mfd_reverse_accum's "racc" without weights."""
+    if dest is None:
+        raise RdgpuError("mfd_upslope_dependence: dest is required")
+    return mfd_reverse_accum(props, None, dest, None, out_nodata, ("racc",))["racc"]
+
+
+def _dinf_reverse_accum(who, dem, nodata, weights, dest, weight_nodata, out_nodata, want) -> dict:
+    dem, s = _elev(dem, who, mfd=True)
+    h, w = dem.shape
+    want = _rev_want(want, who)
+    weights, dest, wnd = _rev_inputs(weights, dest, weight_nodata, want, (h, w), who)
+    out = {k: np.empty((h, w), np.float64) for k in want}
+    check(getattr(lib(), f"rdgpu_{who}_{s}")(_ptr(dem), _scalar(s, nodata), w, h, _ptr(weights), wnd, _ptr(dest),
+                                             _ptr(out.get("racc")), _ptr(out.get("wmax")), ctypes.c_double(out_nodata)),
+          "rdgpu_" + who)
+    return out
+
+
+def dinf_reverse_accum(dem: np.ndarray, nodata, weights: np.ndarray | None = None, dest: np.ndarray | None = None,
+                       weight_nodata=None, out_nodata: float = -1.0, want=("racc",)) -> dict:
+    """mfd_reverse_accum over the D-infinity proportions of dem (FM_Tarboton, never materialised)."""
+    return _dinf_reverse_accum("dinf_reverse_accum", dem, nodata, weights, dest, weight_nodata, out_nodata, want)
+
+
+def dinf_reverse_accum_flats(dem: np.ndarray, nodata, weights: np.ndarray | None = None, dest: np.ndarray | None = None,
+                             weight_nodata=None, out_nodata: float = -1.0, want=("racc",)) -> dict:
+    """dinf_reverse_accum over the proportions of fm_tarboton_flats: the drainable flats of dem pass flow on."""
+    return _dinf_reverse_accum("dinf_reverse_accum_flats", dem, nodata, weights, dest, weight_nodata, out_nodata, want)
+
+
+def dinf_upslope_dependence(dem: np.ndarray, nodata, dest: np.ndarray, out_nodata: float = -1.0) -> np.ndarray:
+    """mfd_upslope_dependence over the D-infinity proportions of dem."""
+    if dest is None:
+        raise RdgpuError("dinf_upslope_dependence: dest is required")
+    return dinf_reverse_accum(dem, nodata, None, dest, None, out_nodata, ("racc",))["racc"]
+
+
+def dinf_upslope_dependence_flats(dem: np.ndarray, nodata, dest: np.ndarray, out_nodata: float = -1.0) -> np.ndarray:
+    """dinf_upslope_dependence over the proportions of fm_tarboton_flats."""
+    if dest is None:
+        raise RdgpuError("dinf_upslope_dependence_flats: dest is required")
+    return dinf_reverse_accum_flats(dem, nodata, None, dest, None, out_nodata, ("racc",))["racc"]
+
+
+def _rev_dev_args(weights, dest, weight_nodata, racc, wmax, shape, who):
+    import torch
+
+    if racc is None and wmax is None:
+        raise RdgpuError(f"{who}: no output requested")
+    if weights is None and dest is None:
+        raise RdgpuError(f"{who}: neither weights nor dest given")
+    if wmax is not None and weights is None:
+        raise RdgpuError(f"{who}: wmax needs the weights")
+    return (_dev_plane(weights, shape, torch.float64, who), ctypes.c_double(float("nan") if weight_nodata is None else float(weight_nodata)),
+            _dev_mask(dest, shape, who), _dev_plane(racc, shape, torch.float64, who), _dev_plane(wmax, shape, torch.float64, who))
+
+
+def mfd_reverse_accum_dev(props, weights=None, dest=None, weight_nodata=None, out_nodata: float = -1.0, racc=None, wmax=None) -> None:
+    """The planes given (float64 CUDA tensors [h, w]) <- mfd_reverse_accum of props (float32 CUDA tensor [h, w, 9]), weights
+    an optional float64 CUDA tensor, dest an optional uint8 CUDA mask; on torch's current stream and without synchronising
+    it.  At least one plane must be given."""
+    import torch
+
+    who = "mfd_reverse_accum_dev"
+    if not (props.is_cuda and props.dim() == 3 and props.shape[2] == 9 and props.is_contiguous() and props.dtype == torch.float32):
+        raise RdgpuError(f"{who}: expected a contiguous float32 tensor [h, w, 9] on the GPU")
+    h, w = props.shape[:2]
+    pw, wnd, pd, pa, pm = _rev_dev_args(weights, dest, weight_nodata, racc, wmax, (h, w), who)
+    check(lib().rdgpu_mfd_reverse_accum_dev(ctypes.c_void_p(props.data_ptr()), w, h, pw, wnd, pd, pa, pm, ctypes.c_double(out_nodata),
+                                            _stream_ptr()), "rdgpu_mfd_reverse_accum_dev")
+
+
+def _dinf_reverse_accum_dev(who, entry, dem, nodata, weights, dest, weight_nodata, out_nodata, racc, wmax) -> None:
+    h, w = _dev2d(dem, who)
+    s = _torch_mfd_suffix(dem, who)
+    pw, wnd, pd, pa, pm = _rev_dev_args(weights, dest, weight_nodata, racc, wmax, (h, w), who)
+    check(getattr(lib(), f"{entry}_{s}")(ctypes.c_void_p(dem.data_ptr()), _scalar(s, nodata), w, h, pw, wnd, pd, pa, pm,
+                                         ctypes.c_double(out_nodata), _stream_ptr()), entry)
+
+
+def dinf_reverse_accum_dev(dem, nodata, weights=None, dest=None, weight_nodata=None, out_nodata: float = -1.0, racc=None,
+                           wmax=None) -> None:
+    """The planes given (float64 CUDA tensors) <- dinf_reverse_accum of dem (CUDA tensor of any element type torch has of
+    int8 .. uint32, float32, float64), on torch's current stream.  At least one plane must be given."""
+    _dinf_reverse_accum_dev("dinf_reverse_accum_dev", "rdgpu_dinf_reverse_accum_dev", dem, nodata, weights, dest, weight_nodata,
+                            out_nodata, racc, wmax)
+
+
+def dinf_reverse_accum_flats_dev(dem, nodata, weights=None, dest=None, weight_nodata=None, out_nodata: float = -1.0, racc=None,
+                                 wmax=None) -> None:
+    """dinf_reverse_accum_dev over the proportions of fm_tarboton_flats."""
+    _dinf_reverse_accum_dev("dinf_reverse_accum_flats_dev", "rdgpu_dinf_reverse_accum_flats_dev", dem, nodata, weights, dest,
+                            weight_nodata, out_nodata, racc, wmax)
+
+
 # ---- D-infinity across flats (include/rdgpu.h "D-infinity across flats") ---------------------------------------
 class _DinfFlatsStats(ctypes.Structure):
     _fields_ = [("noflow_cells", ctypes.c_uint64), ("patched_cells", ctypes.c_uint64), ("fallback_cells", ctypes.c_uint64),

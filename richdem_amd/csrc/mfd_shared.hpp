@@ -1,7 +1,7 @@
 // mfd_shared.hpp -- what the engines on D-infinity / MFD proportions share: the neighbour numbering, the two proportions
 // accessors and the compact D-infinity form from a DEM (mfd.hip: accumulation; mfd_distance.hip: distance and drop down
-// to the stop cells; mfd_distance_up.hip: distance and rise up to the sources).  The work list that the engines run on is
-// mfd_worklist.hpp.
+// to the stop cells; mfd_distance_up.hip: distance and rise up to the sources; mfd_reverse.hip: reverse accumulation and
+// upslope dependence).  The work list that the engines run on is mfd_worklist.hpp.
 #pragma once
 
 #include "common.hpp"

@@ -1,6 +1,6 @@
 // mfd_worklist.hpp -- the work list that the engines on D-infinity / MFD proportions run on (mfd.hip: accumulation;
-// mfd_distance.hip: distance and drop down; mfd_distance_up.hip: distance and rise up): the seed compaction, the two
-// kernels and the host loop.  What an engine does to a cell is its STEP, a functor passed to the kernels by value:
+// mfd_distance.hip: distance and drop down; mfd_distance_up.hip: distance and rise up; mfd_reverse.hip: reverse
+// accumulation): the seed compaction, the two kernels and the host loop.  What an engine does to a cell is its STEP, a functor passed to the kernels by value:
 //
 //   uint32_t step(uint32_t c, bool from_list)   one step for the finished cell c; returns the neighbours of c that THIS
 //                                               thread finished by it, as a mask of neighbour numbers (bit m - 1)

@@ -931,6 +931,82 @@ RDGPU_DECL_EXTREME(u32, uint32_t)
 RDGPU_DECL_EXTREME(f32, float)
 #undef RDGPU_DECL_EXTREME
 
+/* ---- breaching along given D8 directions: pit levels carved down the direction forest ---------
+ * The carve of CompleteBreaching_Lindsay2016 (depressions/Lindsay2016.hpp:138-153) on directions the caller gives -- the
+ * flood's tree (rdgpu_breach_d8 below), flat-resolved directions, a channel tree -- stated as a reachability closure, so
+ * that direction loops need no special case.  dirs are uint8 D8 codes as in rdgpu_d8_flow_path (0 NO_FLOW, 1..8,
+ * dir_nodata), dem a raster of T of the same size, pits a uint8 mask (non-zero: the cell is a pit; required).
+ *   A cell PARTICIPATES iff dirs != dir_nodata.  The LINK of a participating cell exists iff its code is 1..8, its target
+ *   lies in the raster and the target participates (the links of the upslope extremes above).
+ *   A PIT is a participating cell with pits != 0 whose value, for f32, is not a NaN.
+ *   final(c) = the least dem(p) over the pits p with a chain of links p -> ... -> c on which every cell, c included, has
+ *              dem >= dem(p) (p == c counts: a pit ends at its own level or below);
+ *            = dem(c) where there is no such pit.
+ *   A cell that does not participate is never a pit, is never changed and ends every chain; so does, for f32, a NaN cell.
+ *   ORDER: integers in their numeric order; f32 in the IEEE total order on the non-NaN values (-0 below +0), as above.
+ * Per-cell outputs, each a nullable pointer (a call must request at least one):
+ *   out   T      final(c): a copy of some cell's value, bit for bit.
+ *   path  uint8  1 where such a pit exists (a walk of the reference carves or passes the cell), else 0.
+ * Every cell of every requested plane is written exactly once, the inputs are not modified, and the result is exact and
+ * identical from run to run.  T: i8 u8 i16 u16 i32 u32 f32.  A null dirs, dem or pits, both outputs null, a non-positive
+ * size or more than 0xFFFF0000 cells returns RDGPU_ERR_ARG before any device work; nothing is written then.  The _dev
+ * forms take device pointers (d_out must not be d_dem) and are ordered on hip_stream without synchronising it.  Scratch
+ * (1.5 bytes per cell) comes from the workspace pool. */
+#define RDGPU_DECL_BREACH_ALONG(SUF, T)                                                                                    \
+  int rdgpu_d8_breach_along_##SUF(const uint8_t *dirs, uint8_t dir_nodata, const T *dem, const uint8_t *pits, int width,  \
+                                  int height, T *out /* nullable */, uint8_t *path /* nullable */);                       \
+  int rdgpu_d8_breach_along_dev_##SUF(const uint8_t *d_dirs, uint8_t dir_nodata, const T *d_dem, const uint8_t *d_pits,   \
+                                      int width, int height, T *d_out /* nullable */, uint8_t *d_path /* nullable */,     \
+                                      void *hip_stream);
+RDGPU_DECL_BREACH_ALONG(i8, int8_t)
+RDGPU_DECL_BREACH_ALONG(u8, uint8_t)
+RDGPU_DECL_BREACH_ALONG(i16, int16_t)
+RDGPU_DECL_BREACH_ALONG(u16, uint16_t)
+RDGPU_DECL_BREACH_ALONG(i32, int32_t)
+RDGPU_DECL_BREACH_ALONG(u32, uint32_t)
+RDGPU_DECL_BREACH_ALONG(f32, float)
+#undef RDGPU_DECL_BREACH_ALONG
+
+/* ---- CompleteBreaching_Lindsay2016<Topology::D8>(Array2D<T>&) -- depressions/Lindsay2016.hpp:48-178 ----
+ * In place.  Three stages: (1) the reference's pit pass as a stencil -- an interior cell not above any neighbour is a pit
+ * and is raised to its lowest neighbour; (2) the Priority-Flood tree of the raised DEM under the reference's queue
+ * conventions (edge cells seeded in raster order, neighbours pushed in the order 1..8, ties popped in insertion order:
+ * rdgpu_pf_flowdirs' machinery with another convention, its bounds and environment switches included); (3)
+ * rdgpu_d8_breach_along on that tree.  Equal to the reference on every cell, equal elevations included, while
+ * stats.unresolved == 0.  f32 compares as the reference does (-0 equals +0; a zero of either sign is written as +0); NaN
+ * elevations are unsupported input.
+ *   dirs_out  uint8, nullable  the flood's tree: every interior cell points at the cell that pushed it (its back link), the
+ *                              edge cells hold 0.
+ *   path_out  uint8, nullable  1 on every cell a walk of the reference carves or passes, the pits included.
+ * width < 3 or height < 3: the DEM is returned unchanged (dirs_out and path_out all 0).
+ * has_nodata != 0 and some cell equal to nodata: RDGPU_ERR_UNSUPPORTED, found by one reduction before anything is written
+ * (the reference seeds the cells next to NoData as well; not built).  has_nodata == 0: nodata is ignored.
+ * A null dem, a non-positive size or more than 0x7FFF0000 cells is RDGPU_ERR_ARG before any device work.  The _dev forms
+ * take device pointers and synchronise hip_stream (the tree is iterated from the host).  D4, the 64-bit element types and
+ * the selective and constrained modes of Lindsay2016() are not declared. */
+typedef struct rdgpu_breach_stats {
+  uint64_t pits;        /* cells the pit pass marked */
+  uint64_t lowered;     /* cells the carve left below the raised DEM */
+  uint64_t raised;      /* cells the pit pass raised */
+  uint64_t unresolved;  /* the tree's rdgpu_pf_flowdirs_stats.unresolved: 0 => the result is the reference's */
+  uint32_t twins;       /* the tree's rdgpu_pf_flowdirs_stats.twins */
+  uint32_t tie_passes;  /* the tree's rdgpu_pf_flowdirs_stats.tie_passes */
+} rdgpu_breach_stats;
+int rdgpu_breach_get_stats(rdgpu_breach_stats *out);
+#define RDGPU_DECL_BREACH(SUF, T)                                                                                          \
+  int rdgpu_breach_d8_##SUF(T *dem /* in place */, T nodata, int has_nodata, int width, int height,                       \
+                            uint8_t *dirs_out /* nullable */, uint8_t *path_out /* nullable */);                          \
+  int rdgpu_breach_d8_dev_##SUF(T *d_dem /* in place */, T nodata, int has_nodata, int width, int height,                 \
+                                uint8_t *d_dirs_out /* nullable */, uint8_t *d_path_out /* nullable */, void *hip_stream);
+RDGPU_DECL_BREACH(i8, int8_t)
+RDGPU_DECL_BREACH(u8, uint8_t)
+RDGPU_DECL_BREACH(i16, int16_t)
+RDGPU_DECL_BREACH(u16, uint16_t)
+RDGPU_DECL_BREACH(i32, int32_t)
+RDGPU_DECL_BREACH(u32, uint32_t)
+RDGPU_DECL_BREACH(f32, float)
+#undef RDGPU_DECL_BREACH
+
 /* ---- channel network and Strahler stream order on the D8 direction forest ---------------------
  * No reference counterpart (include/richdem/methods/strahler.hpp is a commented-out draft).  Directions are uint8 D8
  * codes (0 NO_FLOW, 1..8, dir_nodata); chan is an optional channel mask (uint8, non-zero = channel), and chan == NULL

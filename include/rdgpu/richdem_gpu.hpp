@@ -1473,6 +1473,82 @@ void d8_upslope_extreme(const F &flowdirs, const V &values, E &extreme, int whic
   detail::extreme_run(flowdirs, values, extreme, nullptr, which);
 }
 
+// ---- depression breaching (depressions/Lindsay2016.hpp, depressions/depressions.hpp:24) ---------------------------------
+namespace detail {
+#define RDGPU_SHIM_BREACH(SUF, T)                                                                                          \
+  inline int c_breach(T *z, T nd, int w, int h, uint8_t *dirs, uint8_t *path) { return rdgpu_breach_d8_##SUF(z, nd, 1, w, h, dirs, path); } \
+  inline int c_breach_along(const uint8_t *d, uint8_t dnd, const T *z, const uint8_t *p, int w, int h, T *out, uint8_t *path) { \
+    return rdgpu_d8_breach_along_##SUF(d, dnd, z, p, w, h, out, path);                                                     \
+  }
+RDGPU_SHIM_BREACH(u8, uint8_t) RDGPU_SHIM_BREACH(i8, int8_t) RDGPU_SHIM_BREACH(u16, uint16_t) RDGPU_SHIM_BREACH(i16, int16_t)
+RDGPU_SHIM_BREACH(u32, uint32_t) RDGPU_SHIM_BREACH(i32, int32_t) RDGPU_SHIM_BREACH(f32, float)
+#undef RDGPU_SHIM_BREACH
+template <class T>
+int c_breach(T *, T, int, int, uint8_t *, uint8_t *) { unsupported("CompleteBreaching_Lindsay2016"); }
+template <class T>
+int c_breach_along(const uint8_t *, uint8_t, const T *, const uint8_t *, int, int, T *, uint8_t *) { unsupported("d8_breach_along"); }
+}  // namespace detail
+
+// richdem::CompleteBreaching_Lindsay2016<topo>(Array2D<T>&)   depressions/Lindsay2016.hpp:48-178: in place, equal to the
+// reference, equal elevations included (rdgpu.h; rdgpu_breach_get_stats relays the tie order's passes).  D8 and element types
+// int8 .. uint32 and float; D4 and the 64-bit types throw, and so does a DEM that holds its NoData value (the reference seeds
+// the cells next to NoData: not built).
+template <auto topo, class A>
+void CompleteBreaching_Lindsay2016(A &dem) {
+  using T = detail::elem_t<A>;
+  if (detail::topology_code<topo>() != 8)
+    throw std::runtime_error("CompleteBreaching_Lindsay2016: topology D4 is not supported by the MI355X engine");
+  if (dem.width() == 0 || dem.height() == 0) return;
+  detail::check(detail::c_breach((T *)dem.data(), (T)dem.noData(), dem.width(), dem.height(), nullptr, nullptr),
+                "CompleteBreaching_Lindsay2016");
+  rdgpu_breach_stats st;
+  if (rdgpu_breach_get_stats(&st) == 0 && st.unresolved != 0)
+    std::fprintf(stderr, "W CompleteBreaching_Lindsay2016: the order of %llu of %u equal-elevation cells had not settled when the "
+                         "tie-order passes were stopped (RDGPU_PFD_TIE_PASSES / RDGPU_PFD_TIE_SECONDS); the breach paths are the "
+                         "reference's only where those ties do not decide\n", (unsigned long long)st.unresolved, st.twins);
+}
+
+// richdem::BreachDepressions<topo>(Array2D<T>&)               depressions/depressions.hpp:24
+template <auto topo, class A>
+void BreachDepressions(A &dem) {
+  CompleteBreaching_Lindsay2016<topo>(dem);
+}
+
+// The carve along given directions (no reference counterpart; the definition is in rdgpu.h): out <- for every cell the least
+// level of a pit (pits != 0) whose level reaches it down the directions over cells that are not below it, else the cell's own
+// value; *path (optional, uint8_t) <- 1 where a pit's level arrived.  Both take the directions' size, geotransform and
+// projection; out keeps the DEM's NoData.  Element types: int8 .. uint32 and float; 64-bit values throw.
+namespace detail {
+template <class F, class V, class P, class E>
+void breach_along_run(const F &flowdirs, const V &dem, const P &pits, E &out, uint8_t *path) {
+  using T = elem_t<const V>;
+  static_assert(std::is_same<elem_t<const F>, uint8_t>::value, "d8_breach_along: flow directions must be uint8_t (d8_flowdir_t)");
+  static_assert(std::is_same<elem_t<const P>, uint8_t>::value, "d8_breach_along: the pit mask must be uint8_t");
+  static_assert(std::is_same<elem_t<E>, T>::value, "d8_breach_along: the output has the DEM's element type");
+  if (dem.width() != flowdirs.width() || dem.height() != flowdirs.height() || pits.width() != flowdirs.width() ||
+      pits.height() != flowdirs.height())
+    throw std::runtime_error("d8_breach_along: the DEM and the pit mask must have the directions' size");
+  out.resize(flowdirs);
+  out.setNoData(dem.noData());
+  if (flowdirs.width() == 0 || flowdirs.height() == 0) return;
+  check(c_breach_along(flowdirs.data(), flowdirs.noData(), (const T *)dem.data(), pits.data(), flowdirs.width(), flowdirs.height(),
+                       (T *)out.data(), path), "d8_breach_along");
+}
+}  // namespace detail
+template <class F, class V, class P, class E, class Q>
+void d8_breach_along(const F &flowdirs, const V &dem, const P &pits, E &out, Q *path) {
+  static_assert(std::is_same<detail::elem_t<Q>, uint8_t>::value, "d8_breach_along: the path raster must be uint8_t");
+  if (path) {
+    path->resize(flowdirs);
+    path->setNoData((uint8_t)255);
+  }
+  detail::breach_along_run(flowdirs, dem, pits, out, path && flowdirs.width() && flowdirs.height() ? path->data() : nullptr);
+}
+template <class F, class V, class P, class E>
+void d8_breach_along(const F &flowdirs, const V &dem, const P &pits, E &out) {
+  detail::breach_along_run(flowdirs, dem, pits, out, nullptr);
+}
+
 // ---- depression inventory (no reference counterpart; the definition is in rdgpu.h) ----------------------------------
 namespace detail {
 #define RDGPU_SHIM_DEPR(SUF, T)                                                                                            \

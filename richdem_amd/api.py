@@ -1817,6 +1817,129 @@ def d8_upslope_extreme_dev(dirs, values, which, value_nodata, extreme=None, at_c
         _stream_ptr()), "rdgpu_d8_upslope_extreme_dev")
 
 
+# ---- depression breaching (csrc/breach.hip) -----------------------------------------------------
+_BREACH_WANT = ("out", "path")
+
+
+def _torch_breach_suffix(t, who) -> str:
+    import torch
+
+    m = {torch.int8: "i8", torch.uint8: "u8", torch.int16: "i16", torch.int32: "i32", torch.float32: "f32"}
+    for name, s in (("uint16", "u16"), ("uint32", "u32")):
+        if hasattr(torch, name):
+            m[getattr(torch, name)] = s
+    if t.dtype not in m:
+        raise RdgpuError(f"{who}: unsupported dtype {t.dtype}")
+    return m[t.dtype]
+
+
+def d8_breach_along(dirs: np.ndarray, dem: np.ndarray, pits: np.ndarray, dir_nodata: int = 255, want=("out", "path")) -> dict:
+    """The carve of depression breaching along GIVEN D8 directions (include/rdgpu.h states the definition): every pit (pits
+    != 0) sends its level down the chain of links as far as the cells are not below it, and a cell ends at the least level
+    that reached it.  A dict with the planes named in `want`: "out" (the DEM's element type, copies of cell values) and
+    "path" (uint8: 1 where a pit's level reached the cell).  dem: int8 .. uint32 or float32 of the directions' shape."""
+    who = "d8_breach_along"
+    dirs = _dirs2d(dirs, who)
+    if not isinstance(dem, np.ndarray) or dem.shape != dirs.shape or dem.dtype not in _EXTREME_SUFFIX:
+        raise RdgpuError(f"{who}: the DEM is an array of the directions' shape, element types int8 .. uint32 or float32")
+    if not isinstance(pits, np.ndarray) or pits.shape != dirs.shape or pits.dtype != np.uint8:
+        raise RdgpuError(f"{who}: the pits are a uint8 array of the directions' shape")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in _BREACH_WANT for k in want):
+        raise RdgpuError(f"{who}: want names at least one of {_BREACH_WANT}")
+    s = _EXTREME_SUFFIX[dem.dtype]
+    z, pm = np.ascontiguousarray(dem), np.ascontiguousarray(pits)
+    h, w = dirs.shape
+    out = {}
+    if "out" in want:
+        out["out"] = np.empty((h, w), z.dtype)
+    if "path" in want:
+        out["path"] = np.empty((h, w), np.uint8)
+    check(getattr(lib(), f"rdgpu_d8_breach_along_{s}")(_ptr(dirs), ctypes.c_uint8(dir_nodata), _ptr(z), _ptr(pm), w, h,
+                                                       _ptr(out.get("out")), _ptr(out.get("path"))), "rdgpu_d8_breach_along")
+    return out
+
+
+def d8_breach_along_dev(dirs, dem, pits, out=None, path=None, dir_nodata: int = 255) -> None:
+    """The planes given (CUDA tensors: out of the DEM's dtype and not the DEM itself, path uint8) <- d8_breach_along of dirs
+    and pits (uint8 CUDA tensors) and dem (CUDA tensor of int8 .. uint32 as far as torch has them, or float32), on torch's
+    current stream and without synchronising it.  At least one plane must be given."""
+    import torch
+
+    who = "d8_breach_along_dev"
+    h, w = _dev2d(dirs, who, torch.uint8)
+    s = _torch_breach_suffix(dem, who)
+    if _dev2d(dem, who) != (h, w) or _dev2d(pits, who, torch.uint8) != (h, w):
+        raise RdgpuError(f"{who}: shape mismatch")
+    if out is None and path is None:
+        raise RdgpuError(f"{who}: no output requested")
+    check(getattr(lib(), f"rdgpu_d8_breach_along_dev_{s}")(
+        ctypes.c_void_p(dirs.data_ptr()), ctypes.c_uint8(dir_nodata), ctypes.c_void_p(dem.data_ptr()), ctypes.c_void_p(pits.data_ptr()),
+        w, h, _dev_plane(out, (h, w), dem.dtype, who), _dev_plane(path, (h, w), torch.uint8, who), _stream_ptr()),
+        "rdgpu_d8_breach_along_dev")
+
+
+class _BreachStats(ctypes.Structure):
+    _fields_ = [("pits", ctypes.c_uint64), ("lowered", ctypes.c_uint64), ("raised", ctypes.c_uint64), ("unresolved", ctypes.c_uint64),
+                ("twins", ctypes.c_uint32), ("tie_passes", ctypes.c_uint32)]
+
+
+def breach_stats() -> dict:
+    """of this thread's last breach_depressions / breach_depressions_dev: pits marked, cells raised by the pit pass, cells
+    lowered by the carve, and the flood tree's twins / unresolved / tie_passes (pf_flowdirs_stats)"""
+    st = _BreachStats()
+    check(lib().rdgpu_breach_get_stats(ctypes.byref(st)), "rdgpu_breach_get_stats")
+    return {"pits": st.pits, "lowered": st.lowered, "raised": st.raised, "unresolved": st.unresolved, "twins": st.twins,
+            "tie_passes": st.tie_passes}
+
+
+def _breach_warn(who):
+    st = breach_stats()
+    if st["unresolved"]:
+        import warnings
+
+        warnings.warn(f"{who}: the order of {st['unresolved']} of {st['twins']} equal cells was still moving when the tie-order passes "
+                      f"of the flood's tree were stopped after {st['tie_passes']}: the result is the reference's only where those ties "
+                      "do not decide", RuntimeWarning)
+
+
+def breach_depressions(dem: np.ndarray, nodata=None, want=()):
+    """CompleteBreaching_Lindsay2016<D8> (depressions/Lindsay2016.hpp:48-178): the breached copy of a 2-D array of int8 ..
+    uint32 or float32, equal to the reference's, equal elevations included (breach_stats()["unresolved"] == 0; a
+    RuntimeWarning otherwise).  nodata=None: the raster has no NoData; a raster that does hold its nodata value raises
+    (code 3: breaching with NoData cells as outlets is not built).  want: "dirs" (uint8: the flood's tree, every interior
+    cell pointing at the cell that pushed it) and / or "path" (uint8: 1 on the cells a walk carved or passed); with any of
+    them the result is a dict with "out" and the planes named."""
+    who = "breach_depressions"
+    if not isinstance(dem, np.ndarray) or dem.ndim != 2 or dem.dtype not in _EXTREME_SUFFIX:
+        raise RdgpuError(f"{who}: expected a 2-D numpy array of int8 .. uint32 or float32")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if any(k not in ("dirs", "path") for k in want):
+        raise RdgpuError(f"{who}: want names 'dirs' and / or 'path'")
+    s = _EXTREME_SUFFIX[dem.dtype]
+    work = np.ascontiguousarray(dem).copy()
+    h, w = work.shape
+    planes = {k: np.empty((h, w), np.uint8) for k in want}
+    check(getattr(lib(), f"rdgpu_breach_d8_{s}")(_ptr(work), _scalar(s, 0 if nodata is None else nodata), 0 if nodata is None else 1,
+                                                 w, h, _ptr(planes.get("dirs")), _ptr(planes.get("path"))), "rdgpu_breach_d8")
+    _breach_warn(who)
+    return dict(planes, out=work) if want else work
+
+
+def breach_depressions_dev(dem, nodata=None, dirs=None, path=None) -> None:
+    """breach_depressions in place on a contiguous 2-D CUDA tensor; dirs / path: optional uint8 CUDA tensors of its shape.
+    On torch's current stream, which the call synchronises (the flood's tree is iterated from the host)."""
+    import torch
+
+    who = "breach_depressions_dev"
+    h, w = _dev2d(dem, who)
+    s = _torch_breach_suffix(dem, who)
+    check(getattr(lib(), f"rdgpu_breach_d8_dev_{s}")(
+        ctypes.c_void_p(dem.data_ptr()), _scalar(s, 0 if nodata is None else nodata), 0 if nodata is None else 1, w, h,
+        _dev_plane(dirs, (h, w), torch.uint8, who), _dev_plane(path, (h, w), torch.uint8, who), _stream_ptr()), "rdgpu_breach_d8_dev")
+    _breach_warn(who)
+
+
 # ---- longest upstream flow path (csrc/longest.hip) ---------------------------------------------
 _LONGEST_WANT = ("from_cell", "steps", "length", "on_basin_path")
 

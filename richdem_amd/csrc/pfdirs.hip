@@ -25,6 +25,7 @@
 // in rdgpu_pf_flowdirs_get_stats.  RDGPU_PFD_RANKS=0: ties decided inside the levels by neighbour number (r03).
 // tests/tools/proto_pf_flowdirs.py is the tie-free algorithm in numpy, checked against the oracle.
 #include "common.hpp"
+#include "pfdirs.hpp"
 
 #include <type_traits>
 
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(NT) void k_init_cand(uint8_t *cand, int w, int h) {
 // the directions: the border cells' fixed ones (:508-528), 0 for NoData cells (:545-548), else the one candidate left
 template <class T>
 __global__ __launch_bounds__(NT) void k_finish(const T *__restrict__ z, T nodata, const uint8_t *__restrict__ cand, uint8_t *dirs, int w,
-                                               int h, unsigned long long *unresolved) {
+                                               int h, unsigned long long *unresolved, int keep_nodata) {
   const uint64_t n = (uint64_t)w * h, stride = (uint64_t)gridDim.x * NT;
   uint32_t bad = 0;
   for (uint64_t c = (uint64_t)blockIdx.x * NT + threadIdx.x; c < n; c += stride) {
@@ -234,7 +235,7 @@ __global__ __launch_bounds__(NT) void k_finish(const T *__restrict__ z, T nodata
       if (x == w - 1 && y == 0) d = 4;
       if (x == 0 && y == h - 1) d = 8;
       if (x == w - 1 && y == h - 1) d = 6;
-    } else if (z[c] == nodata) {
+    } else if (!keep_nodata && z[c] == nodata) {
       d = 0;
     } else {
       const uint32_t m = cand[c];
@@ -483,23 +484,43 @@ __global__ __launch_bounds__(NT) void k_tie_ranks_down(const uint32_t *__restric
   R[c] = (p == T_ROOT ? 0u : R[p] + 1u) + R[c];
 }
 
+// The conventions of the stable queue (pfdirs.hpp).  The seeds' keys: PFD_CONV_BARNES numbers the border cells in the order of
+// the reference's two set-up loops, below 2 w + 2 h; PFD_CONV_LINDSAY by their raster index, below w h.  False: an interior cell.
+__device__ __forceinline__ bool tie_seed_key(int x, int y, int w, int h, uint64_t c, int conv, unsigned long long &t) {
+  if (conv == PFD_CONV_LINDSAY) {
+    t = c;
+    return y == 0 || y == h - 1 || x == 0 || x == w - 1;
+  }
+  if (y == 0) t = 2ull * x;
+  else if (y == h - 1) t = 2ull * x + 1;
+  else if (x == 0) t = 2ull * w + 2ull * (y - 1);
+  else if (x == w - 1) t = 2ull * w + 2ull * (y - 1) + 1;
+  else return false;
+  return true;
+}
+__device__ __forceinline__ unsigned long long tie_seed_count(int w, int h, int conv) {
+  return conv == PFD_CONV_LINDSAY ? (unsigned long long)w * (unsigned long long)h : 2ull * w + 2ull * h;
+}
+// the place of the neighbour in direction inv among a popped cell's pushes
+__device__ __forceinline__ int tie_push_pos(int inv, int conv) {
+  if (conv == PFD_CONV_LINDSAY) return inv ? inv - 1 : 0;                    // 1 .. 8
+  return (inv & 1) ? (inv - 1) >> 1 : 4 + ((inv - 2) >> 1);                  // d8_order = 1,3,5,7,2,4,6,8
+}
+
 // discovery time: border cells in the order of the reference's set-up loops (:508-519: for x: (x, 0), (x, h - 1); for
 // y = 1 .. h - 2: (0, y), (w - 1, y)), then (pop rank of the closing cell, position among its pushes in d8_order)
 __global__ __launch_bounds__(NT) void k_tie_tau(const uint8_t *__restrict__ dirs, const uint32_t *__restrict__ par,
-                                                const uint32_t *__restrict__ R, unsigned long long *tau, uint32_t *cells, int w, int h) {
+                                                const uint32_t *__restrict__ R, unsigned long long *tau, uint32_t *cells, int w, int h,
+                                                int conv) {
   const uint64_t n = (uint64_t)w * h, stride = (uint64_t)gridDim.x * NT;
-  const unsigned long long nb = 2ull * w + 2ull * h;
+  const unsigned long long nb = tie_seed_count(w, h, conv);
   for (uint64_t c = (uint64_t)blockIdx.x * NT + threadIdx.x; c < n; c += stride) {
     const int x = (int)(c % (uint64_t)w), y = (int)(c / (uint64_t)w);
     unsigned long long t;
-    if (y == 0) t = 2ull * x;
-    else if (y == h - 1) t = 2ull * x + 1;
-    else if (x == 0) t = 2ull * w + 2ull * (y - 1);
-    else if (x == w - 1) t = 2ull * w + 2ull * (y - 1) + 1;
-    else {
+    if (!tie_seed_key(x, y, w, h, c, conv, t)) {
       const int d = dirs[c];                                  // towards the closing cell; it pushed c in direction inverse(d)
       const int inv = d == 0 ? 0 : ((d + 3) & 7) + 1;         // d8_inverse: 1<->5, 2<->6, 3<->7, 4<->8
-      const int pos = (inv & 1) ? (inv - 1) >> 1 : 4 + ((inv - 2) >> 1);   // d8_order = 1,3,5,7,2,4,6,8
+      const int pos = tie_push_pos(inv, conv);
       const uint32_t p = par[c];
       t = nb + (p == T_ROOT ? 0ull : ((unsigned long long)R[p] + 1ull) * 8ull + (unsigned long long)pos);
     }
@@ -511,18 +532,14 @@ __global__ __launch_bounds__(NT) void k_tie_tau(const uint8_t *__restrict__ dirs
 // tree of directions must be D(c) = the neighbour of least R.  Rewrites the directions of the interior cells to that (counting
 // the cells that change) and forms the discovery times from it: k_tie_tau with the parents read off R.
 __global__ __launch_bounds__(NT) void k_tie_tau_argmin(uint8_t *dirs, const uint32_t *__restrict__ R, unsigned long long *tau, uint32_t *cells,
-                                                       int w, int h, unsigned long long *changed) {
+                                                       int w, int h, unsigned long long *changed, int conv) {
   const uint64_t n = (uint64_t)w * h, stride = (uint64_t)gridDim.x * NT;
-  const unsigned long long nb = 2ull * w + 2ull * h;
+  const unsigned long long nb = tie_seed_count(w, h, conv);
   uint32_t m = 0;
   for (uint64_t c = (uint64_t)blockIdx.x * NT + threadIdx.x; c < n; c += stride) {
     const int x = (int)(c % (uint64_t)w), y = (int)(c / (uint64_t)w);
     unsigned long long t;
-    if (y == 0) t = 2ull * x;
-    else if (y == h - 1) t = 2ull * x + 1;
-    else if (x == 0) t = 2ull * w + 2ull * (y - 1);
-    else if (x == w - 1) t = 2ull * w + 2ull * (y - 1) + 1;
-    else {
+    if (!tie_seed_key(x, y, w, h, c, conv, t)) {
       uint32_t best = 0xFFFFFFFFu;
       int bd = 1;
 #pragma unroll
@@ -533,7 +550,7 @@ __global__ __launch_bounds__(NT) void k_tie_tau_argmin(uint8_t *dirs, const uint
       m += dirs[c] != (uint8_t)bd;
       dirs[c] = (uint8_t)bd;
       const int inv = ((bd + 3) & 7) + 1;                                   // the closing cell pushed c in direction inverse(bd)
-      const int pos = (inv & 1) ? (inv - 1) >> 1 : 4 + ((inv - 2) >> 1);   // d8_order = 1,3,5,7,2,4,6,8
+      const int pos = tie_push_pos(inv, conv);
       t = nb + ((unsigned long long)best + 1ull) * 8ull + (unsigned long long)pos;
     }
     tau[c] = t;
@@ -545,27 +562,24 @@ __global__ __launch_bounds__(NT) void k_tie_tau_argmin(uint8_t *dirs, const uint
 // first tie key, before any flood: a cell on a slope is most likely closed by its LOWEST neighbour, so equal cells are
 // ordered by (that neighbour's key, position among its pushes) -- closer to the insertion order than the cell index, one
 // pass of the fixed point saved where ties are local (float terrain); any start converges
-__global__ __launch_bounds__(NT) void k_tie_tau0(const uint32_t *__restrict__ zkey, unsigned long long *tau, uint32_t *cells, int w, int h) {
+__global__ __launch_bounds__(NT) void k_tie_tau0(const uint32_t *__restrict__ zkey, unsigned long long *tau, uint32_t *cells, int w, int h,
+                                                 int conv) {
   const uint64_t n = (uint64_t)w * h, stride = (uint64_t)gridDim.x * NT;
-  const unsigned long long nb = 2ull * w + 2ull * h;
+  const unsigned long long nb = tie_seed_count(w, h, conv);
   for (uint64_t c = (uint64_t)blockIdx.x * NT + threadIdx.x; c < n; c += stride) {
     const int x = (int)(c % (uint64_t)w), y = (int)(c / (uint64_t)w);
     unsigned long long t;
-    if (y == 0) t = 2ull * x;
-    else if (y == h - 1) t = 2ull * x + 1;
-    else if (x == 0) t = 2ull * w + 2ull * (y - 1);
-    else if (x == w - 1) t = 2ull * w + 2ull * (y - 1) + 1;
-    else {
+    if (!tie_seed_key(x, y, w, h, c, conv, t)) {
       uint32_t bk = 0xFFFFFFFFu;
       int bd = 1;
 #pragma unroll
-      for (int k = 1; k <= 8; k++) {   // in d8_order, so that among equal lowest neighbours the first pusher wins
-        const int d = k <= 4 ? 2 * k - 1 : 2 * (k - 4);
+      for (int k = 1; k <= 8; k++) {   // in the order of the pushes, so that among equal lowest neighbours the first pusher wins
+        const int d = conv == PFD_CONV_LINDSAY ? k : k <= 4 ? 2 * k - 1 : 2 * (k - 4);
         const uint32_t kk = zkey[(size_t)(y + ndy(d)) * w + (x + ndx(d))];
         if (kk < bk) { bk = kk; bd = d; }
       }
       const int inv = ((bd + 3) & 7) + 1;                                   // the direction in which that neighbour pushes c
-      const int pos = (inv & 1) ? (inv - 1) >> 1 : 4 + ((inv - 2) >> 1);
+      const int pos = tie_push_pos(inv, conv);
       t = nb + (unsigned long long)bk * 8ull + (unsigned long long)pos;
     }
     tau[c] = t;
@@ -630,7 +644,7 @@ static void check_args(const void *z, const void *dirs, int w, int h) {
 }
 
 template <class T>
-void pf_flowdirs_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, hipStream_t s) {
+void pf_flowdirs_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, hipStream_t s, int conv = PFD_CONV_BARNES) {
   check_args(d_z, d_dirs, w, h);
   const uint64_t n = (uint64_t)w * h;
   Workspace &ws = Workspace::get();
@@ -658,7 +672,7 @@ void pf_flowdirs_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, h
       // equal cells start in the order of (lowest neighbour's key, push position): sort by that, then stably by the key
       unsigned long long *tau = pool8(1), *stau = pool8(2);
       uint32_t *c0 = pool4(0, 1), *c1 = pool4(0, 0);   // (idx = pool4(0, 1) is overwritten: the cells again)
-      RD_LAUNCH("pfd.tie.tau0", k_tie_tau0, dim3(sgrid(n)), dim3(NT), 0, s, (const uint32_t *)keys, tau, c0, w, h);
+      RD_LAUNCH("pfd.tie.tau0", k_tie_tau0, dim3(sgrid(n)), dim3(NT), 0, s, (const uint32_t *)keys, tau, c0, w, h, conv);
       RD_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, tau, stau, c0, c1, (int)n, 0, 36, s));
       void *tmp0 = ws.buf("pfd.rtmp", tb);
       RD_HIP(hipcub::DeviceRadixSort::SortPairs(tmp0, tb, tau, stau, c0, c1, (int)n, 0, 36, s));
@@ -754,7 +768,7 @@ void pf_flowdirs_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, h
           const bool stop = passes >= max_passes ||
                             (passes && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_tie0).count() > max_seconds);
           if (!exact && (passes == 0 || !tree_iter || stop || since_flood >= reflood)) {
-            pf_flowdirs_device<uint32_t>(rk, 0xFFFFFFFFu, w, h, d_dirs, s);   // (no rank is 2^32 - 1: n < 2^31)
+            pf_flowdirs_device<uint32_t>(rk, 0xFFFFFFFFu, w, h, d_dirs, s, conv);   // (no rank is 2^32 - 1: n < 2^31)
             levels_total += g_stats.levels;
             exact = true;
             since_flood = 0;
@@ -874,10 +888,10 @@ void pf_flowdirs_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, h
           uint32_t *c0 = ucells, *c1 = scells;
           RD_HIP(hipMemsetAsync(counters, 0, 128 * sizeof(unsigned long long), s));
           if (tree_iter)
-            RD_LAUNCH("pfd.tie.tau_argmin", k_tie_tau_argmin, dim3(sgrid(n)), dim3(NT), 0, s, d_dirs, (const uint32_t *)R, tau, c0, w, h, counters);
+            RD_LAUNCH("pfd.tie.tau_argmin", k_tie_tau_argmin, dim3(sgrid(n)), dim3(NT), 0, s, d_dirs, (const uint32_t *)R, tau, c0, w, h, counters, conv);
           else
             RD_LAUNCH("pfd.tie.tau", k_tie_tau, dim3(sgrid(n)), dim3(NT), 0, s, (const uint8_t *)d_dirs, (const uint32_t *)par, (const uint32_t *)R,
-                      tau, c0, w, h);
+                      tau, c0, w, h, conv);
           tb = 0;
           RD_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, tau, stau, c0, c1, (int)n, 0, 36, s));
           tmp = ws.buf("pfd.rtmp", tb);
@@ -917,7 +931,8 @@ void pf_flowdirs_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, h
       g_stats.levels = levels_total;
       g_stats.tie_passes = passes;
       g_stats.unresolved = moved ? moved : dchanged;   // ranks (or, with the order at rest, directions) still moving when the passes ran out (0: the reference's order; no pass at all: the twins)
-      RD_LAUNCH("pfd.nodata_dirs", (k_nodata_dirs<T>), dim3(sgrid(n)), dim3(NT), 0, s, d_z, nodata, d_dirs, w, h);
+      if (conv != PFD_CONV_LINDSAY)   // (that raster has no NoData, and every value of a small type may be in use)
+        RD_LAUNCH("pfd.nodata_dirs", (k_nodata_dirs<T>), dim3(sgrid(n)), dim3(NT), 0, s, d_z, nodata, d_dirs, w, h);
       return;
     }
   }
@@ -986,7 +1001,8 @@ void pf_flowdirs_device(const T *d_z, T nodata, int w, int h, uint8_t *d_dirs, h
       check_rc(Calls<T>::fill_outlets(F, outlet, skip, sparse ? lists : nullptr, stride, hcounts, w, h, (void *)s));
     }
   }
-  RD_LAUNCH("pfd.finish", (k_finish<T>), dim3(sgrid(n)), dim3(NT), 0, s, d_z, nodata, (const uint8_t *)cand, d_dirs, w, h, sums + 2);
+  RD_LAUNCH("pfd.finish", (k_finish<T>), dim3(sgrid(n)), dim3(NT), 0, s, d_z, nodata, (const uint8_t *)cand, d_dirs, w, h, sums + 2,
+            conv == PFD_CONV_LINDSAY ? 1 : 0);
   unsigned long long unres = 0;
   RD_HIP(hipMemcpyAsync(&unres, sums + 2, sizeof unres, hipMemcpyDeviceToHost, s));
   RD_HIP(hipStreamSynchronize(s));
@@ -1003,6 +1019,23 @@ static void pf_flowdirs_host(const T *dem, T nodata, int w, int h, uint8_t *dirs
   pf_flowdirs_device<T>(d, nodata, w, h, dd, nullptr);
   st.finish();
 }
+
+template <class T>
+void pf_tree_device(const T *d_z, int w, int h, uint8_t *d_dirs, int conv, hipStream_t s, rdgpu_pf_flowdirs_stats *stats) {
+  const rdgpu_pf_flowdirs_stats saved = g_stats;
+  try {
+    pf_flowdirs_device<T>(d_z, T(0), w, h, d_dirs, s, conv);
+  } catch (...) {
+    g_stats = saved;
+    throw;
+  }
+  if (stats) *stats = g_stats;
+  g_stats = saved;
+}
+#define RD_PFD_TREE(T) template void pf_tree_device<T>(const T *, int, int, uint8_t *, int, hipStream_t, rdgpu_pf_flowdirs_stats *);
+RD_PFD_TREE(uint8_t) RD_PFD_TREE(int8_t) RD_PFD_TREE(int16_t) RD_PFD_TREE(uint16_t) RD_PFD_TREE(int32_t) RD_PFD_TREE(uint32_t)
+RD_PFD_TREE(float)
+#undef RD_PFD_TREE
 
 }  // namespace pfd
 }  // namespace rdgpu

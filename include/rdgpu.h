@@ -295,6 +295,9 @@ RDGPU_DECL_WS(u64, uint64_t)
  *                              stream synchronisations, host_syncs 4) is a lower bound of the filled surface, and a 64 x 64
  *                              tile whose blocks all lie above the tile's largest cell is left out of the pair pass: a
  *                              star and a ring of pair records stand in for it.  Needs RDGPU_FILL_FLOODED != 0.
+ *   RDGPU_FILL_COARSE_LANE=0   the nested fill runs on the caller's stream, behind the node resolve (default: on a second
+ *                              stream of the library's, beside it; the caller's stream waits for that stream before the
+ *                              pair pass, so the call is ordered on the caller's stream as ever.  Same output either way)
  *   RDGPU_FILL_COUNT_COARSE=1  counts the tiles left out, for rdgpu_fill_coarse_tiles (default: no counter) */
 /* Statistics of the last fill on this process (for DESIGN.md / bench.py reporting). */
 typedef struct rdgpu_fill_stats {

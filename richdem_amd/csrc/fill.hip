@@ -3472,9 +3472,23 @@ static thread_local bool g_co_pending = false;
 static thread_local hipStream_t g_co_stream = nullptr;
 static thread_local int g_coarse_depth = 0;   // inside the coarse fill of a fill: that one runs no coarse fill of its own
 // Descent tiles from which the coarse flood runs when RDGPU_FILL_COARSE is not set (=1: at any size, =0: never).  Below,
-// the coarse fill's two host round trips and 28 small launches cost more than the pair pass saves: forced on, G(3) of
-// 16384^2 (65 536 tiles) took 2.68 against 2.53 ms, of 32768^2 (262 144 tiles) 8.98 against 8.97.
+// the coarse fill's two host round trips and 28 small launches cost more than the pair pass saves, on the side lane too
+// (r14; there the node resolve is too short to hide them): G(3) switched off against forced on, two alternating runs each,
+//    4096^2   (4 096 tiles) 0.37 / 0.37 against 0.61 / 0.59 ms      8192^2  (16 384) 0.81 / 0.82 against 1.02 / 1.02
+//   16384^2  (65 536)       2.52 / 2.52 against 2.61 / 2.61        32768^2 (262 144) 9.00 / 8.96 against 8.88 / 8.85
+// (r13, on the caller's stream: 2.53 against 2.68 and 8.97 against 8.98.)  DESIGN 3a; profiles/fill_coarse_lane_ab.json.
 constexpr uint32_t COARSE_MIN_TILES = 262144;
+// Work on a side lane must not outlive the call that forked it: the workspace is the next call's.  While `stream` is set
+// (from the fork until the caller's stream waits for the join) leaving the scope waits for the lane.
+struct LaneGuard {
+  hipStream_t stream = nullptr;
+  LaneGuard() = default;
+  LaneGuard(const LaneGuard &) = delete;
+  LaneGuard &operator=(const LaneGuard &) = delete;
+  ~LaneGuard() {
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
+};
 
 // f(std::true_type()) or f(std::false_type()): a runtime flag becomes a template argument of the launches in f
 template <class F>
@@ -3692,6 +3706,19 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
               (const uint32_t *)fo.tile_base, (const uint32_t *)fo.G, (const uint32_t *)pitoff, fo.rcap, tid, w, h, dtx, open_top,
               open_bottom);
   }
+  // r14: the coarse flood runs on a side lane of the workspace, beside k_resolve_nodes and k_init_tables.  It
+  // needs nothing but the descent's block minima and tile_max, complete since the synchronisation above; the fork is
+  // recorded on the idle stream BEFORE the two kernels are enqueued, so the lane does not wait for them.
+  // RDGPU_FILL_COARSE_LANE=0: on the caller's stream behind them, as r13 had it.
+  const char *env_lane = getenv("RDGPU_FILL_COARSE_LANE");
+  Workspace::SideLane *lane = coarse && !(env_lane && env_lane[0] == '0') ? &ws.side_lane(0) : nullptr;
+  LaneGuard lane_open;
+  if (lane) {
+    RD_HIP(hipEventRecord(lane->fork, s));
+    RD_HIP(hipStreamWaitEvent(lane->stream, lane->fork, 0));
+    lane_open.stream = lane->stream;
+  }
+  const hipStream_t cs = lane ? lane->stream : s;   // the coarse flood's stream
   RD_LAUNCH("fill.resolve_nodes", k_resolve_nodes, ngrid, dim3(NTHR), 0, s, fo.G, (const unsigned long long *)fo.counters,
             (const uint32_t *)pitoff, fo.rcap, (const uint16_t *)fo.lab16, (const uint32_t *)fo.tile_base, w, dtx, B, curN, dflags,
             (const uint32_t *)tid, (const uint16_t *)fo.edgeS, (const uint16_t *)fo.edgeR);
@@ -3707,7 +3734,11 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
             dflags + 2, (const uint32_t *)tid, B);
   // ---- the coarse flood: the fill of the block minima, in place, by this very function (its buffers and profile entries
   // under "coarse."; it reads the pinned words, whose values this call holds in locals by now).  k_resolve_nodes and
-  // k_init_tables are in the stream already and run during its host round trips.  Its synchronisations are this fill's.
+  // k_init_tables are in the caller's stream already; on the lane (cs != s) its kernels run beside them, its two
+  // synchronisations wait for the lane alone, and the caller's stream waits for the lane's join before anything else is
+  // enqueued on it: whatever follows, every early return included, is ordered behind the lane.  (An exception between the
+  // fork and that wait -- the nested fill's as well -- waits for the lane as it unwinds: lane_open.)  Its synchronisations
+  // are this fill's.
   uint8_t *tflag = nullptr;
   if (coarse) {
     const rdgpu_fill_stats outer = g_stats;
@@ -3715,7 +3746,7 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
     g_coarse_depth++;
     try {
       NameScope scope("coarse.");
-      ok = fill_fused<uint32_t, TOPO>(coarse, (int)cbx, (int)cby, s);
+      ok = fill_fused<uint32_t, TOPO>(coarse, (int)cbx, (int)cby, cs);
     } catch (...) {
       g_coarse_depth--;
       g_stats = outer;
@@ -3725,22 +3756,27 @@ static bool fill_fused(T *d_z, int w, int h, hipStream_t s, const uint8_t *outle
     const uint32_t syncs = g_stats.host_syncs;
     g_stats = outer;
     g_stats.host_syncs += syncs;
+    unsigned long long *ccount = nullptr;
     if (ok) {   // (else: the coarse raster does not fit the compact path -- nothing is flagged, the fill goes on as ever)
       tflag = ws.buf<uint8_t>("fused.tile_flag", dnt);
       const char *env_coc = getenv("RDGPU_FILL_COUNT_COARSE");
-      unsigned long long *ccount = nullptr;
       if (env_coc && env_coc[0] == '1') {
         ccount = ws.buf<unsigned long long>("fused.coarse_count", 1);
-        RD_HIP(hipMemsetAsync(ccount, 0, sizeof(unsigned long long), s));
+        RD_HIP(hipMemsetAsync(ccount, 0, sizeof(unsigned long long), cs));
       }
-      RD_LAUNCH("fill.flag_tiles", k_flag_tiles, dim3(cdiv(dnt, NTHR)), dim3(NTHR), 0, s, (const uint32_t *)tile_max,
+      RD_LAUNCH("fill.flag_tiles", k_flag_tiles, dim3(cdiv(dnt, NTHR)), dim3(NTHR), 0, cs, (const uint32_t *)tile_max,
                 (const uint32_t *)coarse, dtx, dnt, cbx, tflag, ccount);
-      if (ccount) {
-        if (!g_co_pinned) RD_HIP(hipHostMalloc((void **)&g_co_pinned, sizeof(unsigned long long)));
-        RD_HIP(hipMemcpyAsync(g_co_pinned, ccount, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        g_co_pending = true;
-        g_co_stream = s;
-      }
+    }
+    if (lane) {
+      RD_HIP(hipEventRecord(lane->join, cs));
+      RD_HIP(hipStreamWaitEvent(s, lane->join, 0));
+      lane_open.stream = nullptr;
+    }
+    if (ccount) {
+      if (!g_co_pinned) RD_HIP(hipHostMalloc((void **)&g_co_pinned, sizeof(unsigned long long)));
+      RD_HIP(hipMemcpyAsync(g_co_pinned, ccount, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+      g_co_pending = true;
+      g_co_stream = s;
     }
   }
   uint32_t nroots0 = B;
